@@ -13,7 +13,13 @@ Both use 10 samples per work item (nstreams = spp / 10), f64 arithmetic (the
 reference is all-fp64), the fast (FMA-contracted) kernel build and seed 1.
 `--workload moving|suzanne|mesh100k` times another BASELINE config with the same code
 (configs[3] = suzanne 1920x1080x256 spp, configs[4] = 96,800-triangle mesh 1920x1080x1024 spp);
-the default N = 1 run also appends them, shortened to a few steps, as `other_configs`.
+a `--full` N = 1 run also appends them, shortened to a few steps, as `other_configs`.
+
+A plain run does only what its headline needs: it sets up, warms up, times `--steps` steps, writes what the
+last timed step computed when `--dump-outputs DIR` is given, and prints the line.  `--full` adds every other
+measurement of an N = 1 run — end_to_end and multi_handle, reference_boundary, scaling_base, scale_projection,
+two_frames_in_flight, other_configs, cpu_baseline — and the details file; each `--no-…` switch drops its leg from a
+`--full` run.
 
 Launch: `python bench.py --gpus N` starts N ranks itself when it was not started by
 torchrun (WORLD_SIZE unset): the parent spawns N fresh worker processes BEFORE anything
@@ -23,8 +29,8 @@ from the environment.  `--backend gloo` rehearses the N > 1 path on a one-GPU bo
 rank on cuda:0, collectives through host memory; at most 6 ranks).
 
 stdout of rank 0 carries ONE compact JSON line (under 4 KB: the contract's keys, `roofline`, `cpu_baseline` and a
-handful of scalars — raytracing-one-weekend_amd/benchline.py).  The full record of the run goes to `--details-out`
-(default gpurun_out/bench_details.json) and to stderr, with
+handful of scalars — raytracing-one-weekend_amd/benchline.py).  The full record of the run goes to stderr and, in a
+`--full` run or when `--details-out` names a file, to the details file, with
   roofline      — the bound that BINDS: "valu_issue".  `frac` = issue utilisation x lane activity of the
                   trace kernel (share of the chip's vector lane-slots that carried an active lane's
                   instruction), from the committed PMC passes of this very kernel source (null when the
@@ -39,9 +45,9 @@ handful of scalars — raytracing-one-weekend_amd/benchline.py).  The full recor
                   walk's own counted node and primitive tests per second (live), against the
                   78.6 TFLOP/s f64 vector peak; `issue_utilisation` and `lane_activity` come
                   from the committed PMC file named in `pmc_file` (same kernel, same workload).
-  end_to_end    — SURVEY.md §8d's region for one call of the host-buffer entry point
+  end_to_end    — (--full) SURVEY.md §8d's region for one call of the host-buffer entry point
                   (rtow_render: scene upload incl. acceleration build, kernels, D2H of f64 sums).
-  cpu_baseline  — oracle/ (the CPU restatement of the reference's sample loop, same
+  cpu_baseline  — (--full) oracle/ (the CPU restatement of the reference's sample loop, same
                   Philox stream) timed on this host's cores on a bounded sample of
                   the same workload (same scene and resolution, fewer spp).
 """
@@ -125,11 +131,23 @@ def parse():
                     help="gloo = rehearsal of the N>1 path with every rank on cuda:0 (1-GPU box)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--dump-image", default="", help="rank 0: write the gathered f64 sums of the last step (.npy)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0: write what the last timed step computed into DIR (image.npy, f64; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also run every measurement beyond the headline (end to end, multi-device handle, "
+                         "reference boundary, scaling base and projection, frames in flight, other configs, CPU "
+                         "baseline) and write the details file")
     ap.add_argument("--details-out", default="",
                     help="rank 0: where the full record of the run goes (per-rank tables, per-leg rooflines, builders, "
-                         "multi-device handle); default gpurun_out/bench_details.json, the temp directory if that "
-                         "cannot be written.  stdout carries only the compact line (benchline.py)")
-    return ap.parse_args()
+                         "multi-device handle); a plain run writes it only when this is given, a --full run by default "
+                         "to bench_details.json in the repository's git-ignored output folder, or the temp directory "
+                         "if that cannot be written.  stdout carries only the compact line (benchline.py)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 # ------------------------------------------------------------------ launching N ranks ---
@@ -540,6 +558,30 @@ def samples_per_item(ctx, cfg):
     return int(pairs[1]) if n > 0 else 0
 
 
+DUMP_CAP_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(where, image):
+    """--dump-outputs: the framebuffer the timed path left in its last step — H x W x 3 f64 sums of the samples, what
+    render_device hands its caller (rank 0's gathered frame for N > 1) — as DIR/image.npy.  A frame larger than
+    DUMP_CAP_BYTES (a large --width) is written as a fixed sample instead: DIR/image_sample.npy holds the
+    DUMP_SAMPLE_PIXELS pixels whose row-major indices are in DIR/image_sample_index.npy (f64), drawn without
+    replacement by numpy's default_rng(0) and sorted."""
+    import numpy as np
+
+    d = Path(where)
+    d.mkdir(parents=True, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float64)
+    if img.nbytes <= DUMP_CAP_BYTES:
+        np.save(d / "image.npy", img)
+        return
+    flat = img.reshape(-1, img.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(d / "image_sample.npy", flat[idx])
+    np.save(d / "image_sample_index.npy", idx.astype(np.float64))
+
+
 def write_details(out, where):
     """The full record of the run as a JSON file beside the compact line; returns the path written (repo-relative
     when inside the repo) or None."""
@@ -669,11 +711,15 @@ def main():
     samples, segments = float(work[0]), float(work[1])
 
     if rank == 0:
-        if a.dump_image:
+        if a.dump_image or a.dump_outputs:
             import numpy as np
 
-            img = last["image"] if world > 1 else local[: len(rows)]
-            np.save(a.dump_image, img.cpu().numpy())
+            img = (last["image"] if world > 1 else local[: len(rows)]).cpu().numpy()
+            if a.dump_image:
+                np.save(a.dump_image, img)
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, img)
+        full1 = a.full and world == 1  # the measurements beyond the headline (module docstring)
         spp_eff = rtow.spp_effective(cfg)
         assert samples == W * H * spp_eff, (samples, W * H * spp_eff)
         ms_per_step = elapsed / a.steps * 1e3
@@ -708,7 +754,7 @@ def main():
             "walk": walk,
             "roofline_valu": valu,
         }
-        if world == 1 and not a.no_end_to_end:
+        if full1 and not a.no_end_to_end:
             # SURVEY.md §8d's region through the host-buffer entry point: scene upload (incl. the host
             # build of the acceleration structure), kernels, D2H of the f64 sums into caller memory
             import numpy as np
@@ -787,7 +833,7 @@ def main():
                 }
             except rtow.RtowError as e:  # (no librccl.so on this machine: the line says so instead of failing the bench)
                 out["multi_handle"] = {"error": str(e)}
-        if world == 1 and a.workload == "cover" and not a.no_reference_boundary:
+        if full1 and a.workload == "cover" and not a.no_reference_boundary:
             # What a drop-in caller of render(scene, cfg) gets: Config::nthreads = 4 (src/render.h:18) -> nstreams = 4,
             # at the two sample counts of BASELINE configs[1] / [2], device-resident and through the boundary call
             rb = {"nstreams": 4, "note": "the reference's default thread count; fast build: the work items follow the "
@@ -818,7 +864,7 @@ def main():
                                       "kernel_ms": round(kms4, 4), "samples_per_item_strict_would_be": spp_rb // 4,
                                       "value_e2e_rgb8": round(W * H * spp_rb / eb / 1e6, 3), "ms_per_call_e2e": round(eb * 1e3, 4)}
             out["reference_boundary"] = rb
-        if world == 1 and a.workload == "cover" and spp == 100 and not a.no_scaling_base:
+        if full1 and a.workload == "cover" and spp == 100 and not a.no_scaling_base:
             # like-for-like base of the N>1 lines (configs[2], 500 spp): the same frame on this one
             # GPU, measured after the timed region (a longer launch amortises the end-of-launch tail)
             cfg5 = rtow.make_config(W, H, 500, 500 // SAMPLES_PER_ITEM, DEPTH, seed=SEED, precision=precision, kernel=kernel)
@@ -847,7 +893,7 @@ def main():
                         proj = W * H * 500 / ((b["step_ms_max"] + over) * 1e-3) / 1e6
                         b["projected_Msamples_per_s_with_handle"] = round(proj, 1)
                         b["projected_efficiency_with_handle"] = round(proj / (b["n_gpus"] * out["scaling_base"]["value"]), 4)
-        if world == 1 and a.workload == "cover" and spp == 100 and not a.no_scaling_base:
+        if full1 and a.workload == "cover" and spp == 100 and not a.no_scaling_base:
             # A SEQUENCE of frames, two in flight (never `value`, which is one render at a time): two contexts on this
             # device, each with its own stream, workspace and output, frames alternating between them, so that the next
             # frame's workgroups are dispatched onto the CUs the draining frame leaves.  Each
@@ -875,16 +921,16 @@ def main():
                         "`value` is one render at a time",
             }
             ctx_b.close()
-        if world == 1 and a.workload == "cover" and not a.spp and not a.no_other_configs:
+        if full1 and a.workload == "cover" and not a.spp and not a.no_other_configs:
             out["other_configs"] = [other_config(n, a, dev, precision, s)
                                     for n, s in (("moving", 4), ("suzanne", 3), ("mesh100k", 2))]
             out["other_configs"].append(other_config("mesh100k", a, dev, precision, 1, stress=True))
-        if not a.no_cpu_baseline and world == 1:
+        if full1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, label, W, H, DEPTH, a.cpu_seconds)
         else:
             out["cpu_baseline"] = None
         sys.stdout.flush()
-        details_path = write_details(out, a.details_out)
+        details_path = write_details(out, a.details_out) if (a.full or a.details_out) else None
         sys.stderr.write("bench.py details: " + json.dumps(out) + "\n")
         sys.stderr.flush()
         os.write(json_fd, (benchline.dumps(benchline.compact_line(out, details_path)) + "\n").encode())

@@ -50,7 +50,8 @@ def test_bench_stdout_is_one_compact_line_and_the_details_go_to_a_file(tmp_path)
     import benchline
 
     det = tmp_path / "details.json"
-    r = run_bench(["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-scale-projection", "--details-out", str(det)])
+    r = run_bench(["--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-scale-projection",
+                   "--details-out", str(det)])
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout.endswith("\n") and r.stdout.count("\n") == 1, r.stdout[:400]
     assert len(r.stdout.encode()) < benchline.LINE_CAP
@@ -63,6 +64,24 @@ def test_bench_stdout_is_one_compact_line_and_the_details_go_to_a_file(tmp_path)
     details = json.loads(det.read_text())
     assert details["value"] == line["value"] and len(details["other_configs"]) == 4
     assert benchline.compact_line(details, str(det)) == line
+
+
+def test_plain_bench_times_the_headline_only_and_dumps_the_last_frame(ctx, tmp_path):
+    """A plain run (no --full) times --steps steps of configs[1], prints the line without the extra legs, writes no
+    details file, and --dump-outputs holds the frame the timed path computed: the one-call render, bit for bit."""
+    r = run_bench(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+    assert line["config"]["baseline_config"] == "configs[1]"
+    assert line["details"] is None and line["cpu_baseline"] is None and line["other"] is None
+    assert line["value_e2e"] is None and line["scaling_base_value"] is None
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["image.npy"]
+    got = np.load(tmp_path / "out" / "image.npy")
+    scene = rtow.HostScene.cover(11, 1.5, False)
+    whole, _ = ctx.render(scene, rtow.make_config(1200, 800, 100, 10, 50, seed=1, precision=rtow.F64_FAST))
+    assert got.dtype == np.float64 and got.shape == whole.shape == (800, 1200, 3)
+    assert np.array_equal(got, whole), int((got != whole).sum())
 
 
 def test_bench_refuses_more_gpus_than_the_box_has():

@@ -202,6 +202,28 @@ def test_compact_bench_line_from_committed_details_stays_under_the_cap():
         benchline.dumps(fat)
 
 
+def test_bench_dump_outputs_stays_under_its_cap_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: a frame under the cap is written whole; a larger one as the same seeded sample of
+    pixels every time, values and indices together within the cap."""
+    import bench
+
+    small = np.arange(8 * 16 * 3, dtype=np.float64).reshape(8, 16, 3)
+    bench.dump_outputs(tmp_path / "small", small)
+    assert np.array_equal(np.load(tmp_path / "small" / "image.npy"), small)
+    big = np.random.default_rng(3).random((1500, 2000, 3))
+    assert big.nbytes > bench.DUMP_CAP_BYTES
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, big)
+        assert sorted(p.name for p in (tmp_path / d).iterdir()) == ["image_sample.npy", "image_sample_index.npy"]
+        assert sum(p.stat().st_size for p in (tmp_path / d).iterdir()) <= bench.DUMP_CAP_BYTES
+    idx = np.load(tmp_path / "a" / "image_sample_index.npy")
+    vals = np.load(tmp_path / "a" / "image_sample.npy")
+    assert idx.dtype == vals.dtype == np.float64 and len(idx) == len(vals) == bench.DUMP_SAMPLE_PIXELS
+    assert np.all(np.diff(idx) > 0)
+    assert np.array_equal(vals, big.reshape(-1, 3)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "image_sample_index.npy"))
+
+
 def test_committed_bench_line_follows_the_contract():
     """The compact line committed under profiles/ (the driver's command, final sources of the round) has every
     field the driver's contract names, is consistent with BASELINE.json, and carries roofline and cpu_baseline."""
