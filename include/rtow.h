@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RTOW_ABI_VERSION 7
+#define RTOW_ABI_VERSION 8
 
 /* error codes */
 #define RTOW_OK 0
@@ -310,6 +310,59 @@ int rtow_debug_schedule(rtow_ctx *ctx, const rtow_config_t *cfg, uint32_t *out_p
  * 2 / 3 the same of the RTOW_F32 build).  `out` NULL: size query.  The tests compare host-built
  * and device-built images byte for byte with it. */
 int rtow_debug_image(rtow_ctx *ctx, int32_t which, void *out, int64_t capacity, int64_t *size_out);
+
+/* ---- closest-hit ray queries ------------------------------------------------------------------------------------
+ * "What does this ray hit?" against the scene resident in a context: the world hit of the reference
+ * (src/render.cpp:33-34,52-71) for caller rays, with the walks and hit tests the render runs.  The render path is not
+ * involved: a query neither enters the rtow_profile_collect ring nor touches the dropped-sample word, and a render after
+ * any number of queries is bit-identical to one without them. */
+typedef struct rtow_ray_t {   /* 64 B: four 16-byte loads per ray */
+  double origin[3];
+  double time;                /* shutter time: MovingSphere centre = c0 + time*(c1-c0) (src/oo-primitives.h:64-66) */
+  double direction[3];        /* need not be normalised; t is in units of |direction|, like Ray::at */
+  double tmax;                /* the closest hit is reported if it lies in [0.001, tmax] (tmin: src/render.cpp:33) */
+} rtow_ray_t;
+
+typedef struct rtow_hit_t {   /* 72 B */
+  double t;                   /* +inf on a miss */
+  double point[3];            /* origin + t*direction (Ray::at); 0 on a miss */
+  double normal[3];           /* the reference's Hit::normal: spheres normalize(p - c), flipped to face the ray;
+                                 triangles the un-normalised e1 x e2 (src/common-model.cpp:83-90,121); 0 on a miss */
+  int32_t prim;               /* position in the uploaded scene's insertion order (prim_kind / prim_index; class-major
+                                 order — spheres, moving spheres, triangles — for a scene uploaded without one); -1 miss */
+  int32_t kind;               /* RTOW_PRIM_*; -1 miss */
+  int32_t material;           /* index into rtow_scene_t::materials; -1 miss */
+  int32_t front_face;         /* the reference's front_facing (always 1 for a triangle hit); 0 on a miss */
+} rtow_hit_t;
+
+/* Closest hit of n_rays rays against the scene resident in ctx.  d_rays / d_hits are DEVICE pointers (rays 16-byte
+ * aligned, hits 8-byte aligned).  Enqueued on hip_stream with the ordering rule of rtow_render_device (a
+ * hipStreamNonBlocking stream is made to wait for the last rtow_scene_upload); returns without synchronising unless
+ * stats != NULL, in which case it synchronises the stream and fills: segments = n_rays, prim_tests, node_tests,
+ * kernel_ms (HIP events around the query kernel), total_ms, kernel_used; samples = local_rows = 0.
+ *
+ *   precision  RTOW_F64_STRICT: t, point, normal and front_face are bit-identical to the reference's hit tests (the
+ *                               oracle's), under every kernel;
+ *              RTOW_F64_FAST:   the fast build's walks and tests; parity by tolerance (relative 1e-9 on t, with a
+ *                               different primitive only at such near-ties);
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ *   kernel     RTOW_KERNEL_AUTO resolves as a render of the resident scene does; BRUTE, BVH, GRID and BVH4 have the
+ *              render's fallbacks and residency rules (after the lean upload of rtow_render a strategy whose structures
+ *              were not built gives RTOW_ENOSCENE, as rtow_render_device does); kernel_used says what ran.
+ *              RTOW_KERNEL_REFTREE is strict only (RTOW_EINVAL otherwise) and builds the reference's tree on first use.
+ *   tmax       post-filter: the closest hit over [0.001, inf) is reported when its t <= tmax, else a miss (exact: the
+ *              closest hit lies within tmax exactly when any hit does).  The walks are not seeded with tmax, so a
+ *              short tmax prunes nothing.
+ *   time       results are independent of the kernel for time in [0, 1] only: the moving spheres' boxes cover that
+ *              interval (the reference's BVH has the same property).
+ * Errors: RTOW_EINVAL for a NULL ctx, NULL buffers with n_rays > 0, n_rays < 0 or > 2^31 - 64, misaligned buffers, an
+ * unknown precision or kernel; RTOW_ENOSCENE without a resident scene.  n_rays == 0 returns RTOW_OK and launches
+ * nothing.  One call in flight per context, as for the renders. */
+int rtow_intersect_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays,
+                          void *d_hits, void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
+int rtow_intersect(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
+                   rtow_hit_t *hits, rtow_stats_t *stats);
 
 /* Convenience: upload + render + copy this rank's rows to host memory.
  * Lean upload: rtow_render / rtow_render_rgb8 know their config and build only the structures ITS kernel reads

@@ -243,6 +243,13 @@ int grid_build_phase3(void *handle, const float gminf[3], const float cellf[3], 
                       unsigned long long total_ids, unsigned char *blob_dev, uint32_t off_cells, uint32_t off_ids,
                       void *stream, const double *sph, uint32_t off_fat, const double *mov, int ns, uint32_t fat_stride);
 void grid_build_release(void *handle);
+// csrc/rtow_query_{strict,fast}.hip (rtow_query.h)
+int launch_query_strict(const TraceParams &p, const void *rays, void *hits, uint32_t n, const int32_t *map,
+                        unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
+int launch_query_fast(const TraceParams &p, const void *rays, void *hits, uint32_t n, const int32_t *map,
+                      unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
+int query_occupancy_strict(int kernel, int block, unsigned lds_bytes, int *vgprs);
+int query_occupancy_fast(int kernel, int block, unsigned lds_bytes, int *vgprs);
 }  // namespace rtow
 
 // Experiment knobs (RTOW_* environment variables), read ONCE at rtow_ctx_create: nothing on the
@@ -404,6 +411,13 @@ struct rtow_ctx {
   hipEvent_t call_ev[2] = {};
   // pinned host mirror of the counters for stats
   unsigned long long *h_counters = nullptr;
+  // ray queries (rtow_intersect*): counters, events, spill and staging of their own (a query never touches the render's
+  // workspace, profile ring or dropped-sample word); the walk-id -> insertion-index tables are built at the first query
+  // that needs them after an upload (query_map)
+  DevBuf q_counters, q_spill, q_rays, q_hits, q_map[3];
+  bool q_map_ok[3] = {false, false, false};
+  hipEvent_t q_ev[4] = {};
+  unsigned long long *h_qcounters = nullptr;
 };
 
 // BVH4: stack entries per lane (4 B x 1024 lanes each) an image staged whole must leave room for (RTOW_BVH4_STACK_K)
@@ -466,8 +480,12 @@ void rtow_ctx_destroy(rtow_ctx *c) {
   for (DevBuf *b : {&c->sph, &c->sph_r, &c->mov, &c->tri, &c->tri16, &c->prim_mat, &c->mats, &c->blob, &c->cam_dev, &c->gblob,
                     &c->blob32, &c->gblob32, &c->cam32_dev, &c->blob4,
                     &c->partials, &c->stack, &c->counters, &c->spill, &c->out, &c->out8, &c->rtree, &c->counters_init,
-                    &c->dropped})
+                    &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_map[0], &c->q_map[1],
+                    &c->q_map[2]})
     b->release();
+  for (hipEvent_t e : c->q_ev)
+    if (e) (void)hipEventDestroy(e);
+  if (c->h_qcounters) (void)hipHostFree(c->h_qcounters);
   if (c->h_dropped) (void)hipHostFree(c->h_dropped);
   if (c->upload_ev) (void)hipEventDestroy(c->upload_ev);
   if (c->arena.p) (void)hipHostFree(c->arena.p);
@@ -534,6 +552,7 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
   c->built = 0;
   c->have_scene = false;
   c->have_rtree = false;
+  c->q_map_ok[0] = c->q_map_ok[1] = c->q_map_ok[2] = false;  // (the ray queries' id tables belong to the old scene)
   c->build_info.ref_tree_nodes = 0;
   c->build_info.ref_tree_stupid_volume = 0.0;
   const double t_up0 = now_ms();
@@ -1225,25 +1244,16 @@ static int impl_render_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb
   return RTOW_OK;
 }
 
-// One launch: levels [lvl_first, lvl_first + lvl_count) of the plan.
-static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums, void *hip_stream,
-                         rtow_stats_t *stats, const LevelPlan &plan, int lvl_first, int lvl_count, int accumulate) {
-  int rc;
-  hipStream_t st = (hipStream_t)hip_stream;
-  const int rows = rtow_local_rows(cfg);
-  const unsigned long long npix = (unsigned long long)rows * cfg->image_width;
-  const int streams_now = lvl_count;  // levels of this launch
-  const int spt = plan.spt;
-  const int spt_last = lvl_first + lvl_count == plan.count ? plan.last : plan.spt;  // (a ragged schedule ends on a longer level)
-  const unsigned long long n_items = npix * (unsigned long long)streams_now;
-  if (n_items > 0xfffffff0ULL) return fail(RTOW_EINVAL, "too many work items (%llu)", n_items);
-  int kernel = cfg->kernel;
+// The strategy a request resolves to, with the render's fallbacks and residency rules (shared by the render and the
+// ray queries); the first RTOW_KERNEL_REFTREE request builds the reference's tree.
+static int resolve_kernel(rtow_ctx *c, int precision, int requested, int *out) {
+  int kernel = requested;
   // a handful of primitives is cheaper to stream than to walk
   // AUTO: a handful of primitives is cheaper to stream than to walk; sphere scenes walk the
   // grid (measured 1.3x the BVH on the cover scene); triangle meshes walk the BVH (a triangle
   // spans many cells and its test is 3.5x a sphere's, so duplicates are expensive: 0.4x)
-  const bool strict = cfg->precision == RTOW_F64_STRICT;
-  const bool f32 = cfg->precision == RTOW_F32;
+  const bool strict = precision == RTOW_F64_STRICT;
+  const bool f32 = precision == RTOW_F32;
   const bool bvh4_ok = c->have_bvh4 && !f32;  // triangle mesh, host builder, binary64 build
   if (kernel == RTOW_KERNEL_AUTO)
     kernel = c->n_prims <= 16 ? RTOW_KERNEL_BRUTE
@@ -1277,7 +1287,7 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
       const double t0 = now_ms();
       rtow::build_reftree(&hs, rt);
       if (!rt.ok) return fail(RTOW_EINVAL, "reference tree: depth %d exceeds the kernel's stack", rt.depth);
-      if ((rc = upload(c->rtree, rt.blob))) return rc;
+      if (int rc = upload(c->rtree, rt.blob)) return rc;
       c->ds.rtree = (const unsigned char *)c->rtree.p;
       c->ds.rt_off_ids = rt.off_ids;
       c->have_rtree = true;
@@ -1286,9 +1296,25 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
       c->build_info.ref_tree_build_ms = now_ms() - t0;
     }
   }
-  rtow::DevScene scene = f32 ? c->ds32 : c->ds;
-  int block = (kernel >= RTOW_KERNEL_BVH && kernel <= RTOW_KERNEL_BVH4) ? kBvhBlock : kBlock;
-  const bool image_kernel = kernel >= RTOW_KERNEL_BVH && kernel <= RTOW_KERNEL_BVH4;
+  *out = kernel;
+  return RTOW_OK;
+}
+
+// Launch shape of a strategy on the resident scene (shared by the render and the ray queries): workgroup size, LDS
+// bytes and the DevScene fields that go with them (STREAM tiles; BVH4: what is staged, the stack's place and depth).
+struct LaunchShape {
+  rtow::DevScene scene;
+  int block = 0;
+  unsigned lds_bytes = 0;
+  int stack_bound = 0;  // BVH4: traversal stack entries a lane may need (3 x depth + 1)
+  bool image_kernel = false;
+};
+static int launch_shape(rtow_ctx *c, int kernel, bool f32, LaunchShape &s) {
+  s.scene = f32 ? c->ds32 : c->ds;
+  rtow::DevScene &scene = s.scene;
+  int &block = s.block;
+  block = (kernel >= RTOW_KERNEL_BVH && kernel <= RTOW_KERNEL_BVH4) ? kBvhBlock : kBlock;
+  const bool image_kernel = s.image_kernel = kernel >= RTOW_KERNEL_BVH && kernel <= RTOW_KERNEL_BVH4;
   if (image_kernel && c->knobs.bvh_block) block = c->knobs.bvh_block;  // experiment knob
   // the scene image goes to LDS when one copy per workgroup fits (160 KiB per CU)
   const uint32_t image_bytes = kernel == RTOW_KERNEL_GRID ? scene.gblob_bytes : scene.blob_bytes;
@@ -1297,14 +1323,16 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
   if (image_kernel && block == kBvhBlock && image_bytes <= kLdsLimit && 2u * image_bytes > kLdsLimit &&
       !c->knobs.bvh_block)
     block = 1024;
-  unsigned lds_bytes = (image_kernel && image_bytes <= kLdsLimit) ? image_bytes : 0u;
+  unsigned &lds_bytes = s.lds_bytes;
+  lds_bytes = (image_kernel && image_bytes <= kLdsLimit) ? image_bytes : 0u;
   scene.stream_tile_lds = 0u;
   if (kernel == RTOW_KERNEL_BRUTE && scene.n_tri >= kStreamTileMin && !c->knobs.stream_scalar) {
     // the tiled triangle loop of the STREAM kernel (csrc/rtow_trace_hit.h): two 3 KB tiles of LDS per wave
     scene.stream_tile_lds = 2u * 32u * 96u;
     lds_bytes = (unsigned)(block / 64) * scene.stream_tile_lds;
   }
-  int stack_bound = 0;
+  int &stack_bound = s.stack_bound;
+  stack_bound = 0;
   if (kernel == RTOW_KERNEL_BVH4) {
     // One 1024-lane workgroup per CU.  LDS = [image, or the top of its tree][stack: K entries x 4 B per lane].
     // A small mesh is staged whole and the stack takes what is left (at least 8 entries per lane);
@@ -1343,6 +1371,32 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
     scene.b4_stack_k = K;
     lds_bytes = scene.b4_stack_base + K * per_entry;
   }
+  return RTOW_OK;
+}
+
+// One launch: levels [lvl_first, lvl_first + lvl_count) of the plan.
+static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums, void *hip_stream,
+                         rtow_stats_t *stats, const LevelPlan &plan, int lvl_first, int lvl_count, int accumulate) {
+  int rc;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int rows = rtow_local_rows(cfg);
+  const unsigned long long npix = (unsigned long long)rows * cfg->image_width;
+  const int streams_now = lvl_count;  // levels of this launch
+  const int spt = plan.spt;
+  const int spt_last = lvl_first + lvl_count == plan.count ? plan.last : plan.spt;  // (a ragged schedule ends on a longer level)
+  const unsigned long long n_items = npix * (unsigned long long)streams_now;
+  if (n_items > 0xfffffff0ULL) return fail(RTOW_EINVAL, "too many work items (%llu)", n_items);
+  int kernel = 0;
+  if ((rc = resolve_kernel(c, cfg->precision, cfg->kernel, &kernel))) return rc;
+  const bool strict = cfg->precision == RTOW_F64_STRICT;
+  const bool f32 = cfg->precision == RTOW_F32;
+  LaunchShape shape;
+  if ((rc = launch_shape(c, kernel, f32, shape))) return rc;
+  rtow::DevScene &scene = shape.scene;
+  const int block = shape.block;
+  const unsigned lds_bytes = shape.lds_bytes;
+  const int stack_bound = shape.stack_bound;
+  const bool image_kernel = shape.image_kernel;
 
   if (stats) {
     std::memset(stats, 0, sizeof *stats);
@@ -1555,6 +1609,165 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
   return RTOW_OK;
 }
 
+// ---- ray queries (rtow_intersect / rtow_intersect_device) -------------------------------------------------------------
+constexpr int64_t kMaxQueryRays = (1ll << 31) - 64;  // include/rtow.h
+
+// Walk-order primitive id -> insertion index (the uploaded scene's prim_kind / prim_index order; class-major order when
+// the scene came without one).  which: 0 class-major ids (STREAM, GRID, REFTREE walks and a device-built BVH image),
+// 1 the record slots of a host-built mesh BVH image (ds.leaf_direct), 2 the record slots of the 4-wide image.  The
+// leaf-ordered images hold exact copies of the class-ordered triangle records, so a slot's triangle is found by matching
+// its 96 bytes (identical records — duplicate triangles — are paired in order: any one of them gives the same hit).
+// Built on the host at the first query that needs the table after an upload; scene_upload drops them.
+static int query_map(rtow_ctx *c, int which, const int32_t **out) {
+  if (c->q_map_ok[which]) {
+    *out = (const int32_t *)c->q_map[which].p;
+    return RTOW_OK;
+  }
+  const int ns = c->ds.n_sph, nm = c->ds.n_mov, nt = c->ds.n_tri, np = c->n_prims;
+  const rtow_ctx::HostSceneCopy &h = c->host_scene;
+  std::vector<int32_t> cls2ins((size_t)np);
+  for (int i = 0; i < np; ++i) cls2ins[i] = i;
+  if (h.have_order)
+    for (int i = 0; i < np; ++i) {
+      const int k = h.pk[i];
+      const int base = k == RTOW_PRIM_SPHERE ? 0 : (k == RTOW_PRIM_MOVING_SPHERE ? ns : ns + nm);
+      cls2ins[(size_t)base + h.pi[i]] = i;
+    }
+  std::vector<int32_t> table;
+  if (which == 0) {
+    table.swap(cls2ins);
+  } else {
+    const unsigned char *img = which == 1 ? c->ds.blob + c->ds.off_tri : c->ds.blob4 + c->ds.b4_off_tri;
+    const size_t bytes = (size_t)nt * 96u;
+    std::vector<unsigned char> rec_cls(bytes), rec_img(bytes);
+    HIPCHK(hipMemcpy(rec_cls.data(), c->tri.p, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rec_img.data(), img, bytes, hipMemcpyDeviceToHost));
+    std::vector<int32_t> oc((size_t)nt), oi((size_t)nt);
+    for (int i = 0; i < nt; ++i) oc[i] = oi[i] = i;
+    auto by_record = [](const std::vector<unsigned char> &r) {
+      return [&r](int32_t a, int32_t b) {
+        const int m = std::memcmp(&r[(size_t)a * 96u], &r[(size_t)b * 96u], 96);
+        return m != 0 ? m < 0 : a < b;
+      };
+    };
+    std::sort(oc.begin(), oc.end(), by_record(rec_cls));
+    std::sort(oi.begin(), oi.end(), by_record(rec_img));
+    table.assign((size_t)nt, -1);
+    for (int k = 0; k < nt; ++k) {
+      if (std::memcmp(&rec_cls[(size_t)oc[k] * 96u], &rec_img[(size_t)oi[k] * 96u], 96) != 0)
+        return fail(RTOW_EINVAL, "internal error: the %s image's triangle records are not those of the scene",
+                    which == 1 ? "BVH" : "4-wide");
+      table[(size_t)oi[k]] = cls2ins[(size_t)ns + nm + oc[k]];
+    }
+  }
+  DevBuf &b = c->q_map[which];
+  if (int rc = b.ensure(std::max<size_t>(table.size() * sizeof(int32_t), 4))) return rc;
+  if (!table.empty()) HIPCHK(hipMemcpy(b.p, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  c->q_map_ok[which] = true;
+  *out = (const int32_t *)b.p;
+  return RTOW_OK;
+}
+
+static int impl_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_rays, int64_t n_rays,
+                                 void *d_hits, void *hip_stream, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
+  if (n_rays > 0 && (!d_rays || !d_hits)) return fail(RTOW_EINVAL, "NULL ray or hit buffer");
+  if (((uintptr_t)d_rays & 15u) != 0u || ((uintptr_t)d_hits & 7u) != 0u)
+    return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned, hit buffer 8-byte aligned");
+  if (precision == RTOW_F32) return fail(RTOW_EINVAL, "ray queries: RTOW_F32 is not supported (binary64 builds only)");
+  if (precision != RTOW_F64_STRICT && precision != RTOW_F64_FAST) return fail(RTOW_EINVAL, "unknown precision %d", precision);
+  if (kernel_req < RTOW_KERNEL_AUTO || kernel_req > RTOW_KERNEL_REFTREE) return fail(RTOW_EINVAL, "unknown kernel %d", kernel_req);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  int rc, kernel = 0;
+  if ((rc = resolve_kernel(c, precision, kernel_req, &kernel))) return rc;
+  LaunchShape shape;
+  if ((rc = launch_shape(c, kernel, false, shape))) return rc;
+  const bool strict = precision == RTOW_F64_STRICT;
+  if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+    stats->kernel_used = kernel;
+  }
+  if (n_rays == 0) return RTOW_OK;
+
+  const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
+  const int32_t *map = nullptr;
+  if ((rc = query_map(c, which, &map))) return rc;
+  const int block = shape.block;
+  int occ = strict ? rtow::query_occupancy_strict(kernel, block, shape.lds_bytes, nullptr)
+                   : rtow::query_occupancy_fast(kernel, block, shape.lds_bytes, nullptr);
+  if (occ <= 0) return fail(RTOW_EHIP, "query occupancy failed (kernel %d, %u B of LDS)", kernel, shape.lds_bytes);
+  occ = std::min(occ, 8);
+  long long grid = (long long)c->num_cus * occ;
+  const long long need_blocks = (n_rays + block - 1) / block;
+  grid = std::max(std::min(grid, need_blocks), 1ll);
+  const unsigned long long n_lanes = (unsigned long long)grid * block;
+  if ((rc = c->q_counters.ensure(2 * sizeof(unsigned long long)))) return rc;
+  if (kernel == RTOW_KERNEL_BVH4) {
+    const int extra = std::max(shape.stack_bound - (int)shape.scene.b4_stack_k, 0);
+    if ((rc = c->q_spill.ensure(std::max<size_t>((size_t)extra * (size_t)n_lanes * sizeof(uint32_t), 16)))) return rc;
+  }
+  rtow::TraceParams P;
+  std::memset(&P, 0, sizeof P);
+  P.sc = shape.scene;
+  P.n_lanes = (uint32_t)n_lanes;
+  P.spill = (uint32_t *)c->q_spill.p;
+  // every walk runs to completion (cap 0xffffffff); the leaf-phase quorum is the render's
+  const bool b4 = kernel == RTOW_KERNEL_BVH4;
+  P.walk_cap = 0xffffffffu;
+  P.walk_max_open = 64u;
+  P.leaf_votes = (uint32_t)(c->knobs.leaf_votes > 0 ? c->knobs.leaf_votes : (b4 ? 28 : 16));
+
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (stats && !c->q_ev[0]) {
+    for (hipEvent_t &e : c->q_ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipHostMalloc((void **)&c->h_qcounters, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+  }
+  if (st != nullptr) HIPCHK(hipStreamWaitEvent(st, c->upload_ev, 0));  // the scene upload was queued on the null stream
+  if (stats) HIPCHK(hipEventRecord(c->q_ev[0], st));
+  HIPCHK(hipMemsetAsync(c->q_counters.p, 0, 2 * sizeof(unsigned long long), st));
+  if (stats) HIPCHK(hipEventRecord(c->q_ev[1], st));
+  auto *counters = (unsigned long long *)c->q_counters.p;
+  const int lrc = strict ? rtow::launch_query_strict(P, d_rays, d_hits, (uint32_t)n_rays, map, counters, kernel, (int)grid,
+                                                     block, shape.lds_bytes, st)
+                         : rtow::launch_query_fast(P, d_rays, d_hits, (uint32_t)n_rays, map, counters, kernel, (int)grid,
+                                                   block, shape.lds_bytes, st);
+  if (lrc != 0) return fail(RTOW_EHIP, "query kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  if (stats) {
+    HIPCHK(hipEventRecord(c->q_ev[2], st));
+    HIPCHK(hipMemcpyAsync(c->h_qcounters, counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(c->q_ev[3], st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->q_ev[1], c->q_ev[2]));
+    stats->kernel_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, c->q_ev[0], c->q_ev[3]));
+    stats->total_ms = ms;
+    stats->segments = (uint64_t)n_rays;
+    stats->prim_tests = kernel == RTOW_KERNEL_BRUTE ? (uint64_t)n_rays * (uint64_t)c->n_prims : c->h_qcounters[0];
+    stats->node_tests = kernel == RTOW_KERNEL_BRUTE ? 0u : c->h_qcounters[1];
+  }
+  return RTOW_OK;
+}
+
+static int impl_intersect(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
+                          rtow_hit_t *hits, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
+  if (n_rays > 0 && (!rays || !hits)) return fail(RTOW_EINVAL, "NULL ray or hit array");
+  if (n_rays == 0) return impl_intersect_device(c, precision, kernel, nullptr, 0, nullptr, nullptr, stats);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = c->q_rays.ensure((size_t)n_rays * sizeof(rtow_ray_t))) || (rc = c->q_hits.ensure((size_t)n_rays * sizeof(rtow_hit_t))))
+    return rc;
+  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n_rays * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
+  if ((rc = impl_intersect_device(c, precision, kernel, c->q_rays.p, n_rays, c->q_hits.p, nullptr, stats))) return rc;
+  HIPCHK(hipMemcpy(hits, c->q_hits.p, (size_t)n_rays * sizeof(rtow_hit_t), hipMemcpyDeviceToHost));
+  return RTOW_OK;
+}
+
 // Diagnostic: copy a resident scene image to the host (0 BVH, 1 grid, 2 BVH of the f32 build,
 // 3 grid of the f32 build).  Used by the tests to compare host- and device-built images.
 int rtow_debug_image(rtow_ctx *c, int32_t which, void *out, int64_t capacity, int64_t *size_out) {
@@ -1760,6 +1973,15 @@ int rtow_render_rgb8(rtow_ctx *c, const rtow_scene_t *scene, const rtow_config_t
 }
 int rtow_render_device_rgb8(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb8, void *hip_stream, rtow_stats_t *stats) {
   return guarded("rtow_render_device_rgb8", [&] { return impl_render_device_rgb8(c, cfg, d_rgb8, hip_stream, stats); });
+}
+int rtow_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays, void *d_hits,
+                          void *hip_stream, rtow_stats_t *stats) {
+  return guarded("rtow_intersect_device",
+                 [&] { return impl_intersect_device(c, precision, kernel, d_rays, n_rays, d_hits, hip_stream, stats); });
+}
+int rtow_intersect(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, rtow_hit_t *hits,
+                   rtow_stats_t *stats) {
+  return guarded("rtow_intersect", [&] { return impl_intersect(c, precision, kernel, rays, n_rays, hits, stats); });
 }
 int rtow_debug_schedule(rtow_ctx *c, const rtow_config_t *cfg, uint32_t *out, int32_t capacity_pairs) {
   return guarded("rtow_debug_schedule", [&] { return impl_debug_schedule(c, cfg, out, capacity_pairs); });

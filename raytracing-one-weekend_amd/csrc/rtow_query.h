@@ -1,0 +1,342 @@
+// rtow_query.h — the closest-hit ray query kernel (rtow_intersect / rtow_intersect_device, include/rtow.h), included
+// by rtow_query_strict.hip and rtow_query_fast.hip, which differ only in -ffp-contract and in RTOW_SUFFIX.
+//
+// What it computes: for every caller ray, the reference's world hit over [0.001, +inf) (src/render.cpp:33-34,
+// BVHNode::hit) with the same walks the trace kernels run — closest_hit_stream / _bvh / _grid / _bvh4 / _reftree,
+// included read-only below exactly as rtow_trace_body.h includes them — then the winner's hit record rebuilt with the
+// trace kernel's shading expressions (rtow_trace_body.h, the `do_scat` block): Ray::at, the sphere normal faced
+// against the ray, the triangle's un-normalised e1 x e2, the material index from the scene image.  A hit beyond the
+// ray's tmax is then reported as a miss (post-filter: the closest hit in [0.001, inf) lies within tmax exactly when
+// any hit does; the walks are not seeded with tmax, so nothing is pruned by it).
+//
+// Execution model (gfx950, wave64): persistent waves.  The grid is what stays resident (occupancy query below, like
+// trace_occupancy_*), capped by the number of rays; every wave takes 64 consecutive rays per step and strides over the
+// batch.  Lanes past n_rays enter the walks with active = false (the walks vote across the wave: __any / __ballot).
+// A lane reads its 64-byte ray with four 16-byte loads (the wave's loads cover one contiguous 4 KiB run) and writes
+// its 72-byte hit record with 8-byte stores (the 72-byte stride leaves only every other record 16-byte aligned).
+// The scene image is staged in LDS per workgroup once, exactly as the trace kernel stages it for the same strategy.
+//
+// Walk-order primitive ids -> the caller's insertion order: `map` (built by the host on first use after an upload,
+// rtow_capi.cpp).  The STREAM, GRID and REFTREE walks and a device-built BVH return class-major ids; the 4-wide image and
+// a host-built mesh BVH hold their triangle records in leaf order and return record slots.  The kind follows from the
+// class-major ranges either way (a leaf-ordered image is a triangle mesh).
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rtow_device.h"
+
+#ifndef RTOW_SUFFIX
+#error "define RTOW_SUFFIX"
+#endif
+#define RTOW_QCAT2(a, b) a##b
+#define RTOW_QCAT(a, b) RTOW_QCAT2(a, b)
+
+namespace rtow {
+namespace {
+#include "rtow_trace_math.h"
+#include "rtow_trace_hit.h"
+#include "rtow_trace_stamps.h"
+#include "rtow_trace_bvh.h"
+#include "rtow_trace_grid.h"
+#include "rtow_trace_bvh4.h"
+#ifndef RTOW_FAST_MATH
+#include "rtow_trace_reftree.h"
+#endif
+
+// The layouts of rtow_ray_t (64 B) and rtow_hit_t (72 B), include/rtow.h.
+constexpr uint32_t kRayBytes = 64u, kHitBytes = 72u;
+
+struct QueryParams {
+  TraceParams P;               // the scene (P.sc) and the walks' launch fields: spill, n_lanes, leaf_votes, walk_max_open
+  const unsigned char *rays;   // [n][64 B], 16-byte aligned
+  unsigned char *hits;         // [n][72 B], 8-byte aligned
+  uint32_t n;
+  const int32_t *map;          // walk's primitive id -> insertion index
+  unsigned long long *counters;  // [0] primitive tests, [1] node tests
+};
+
+// -0.0 -> +0.0, every other value unchanged (on the bits: the fast build's -fno-signed-zeros would fold `x + 0.0`).
+// The grid walk's DDA takes its step direction from `d >= 0` and its increments from rcp(d) (rtow_trace_grid.h), which
+// disagree for a component of -0.0 (rcp(-0) = -inf): such a ray steps the wrong way and misses.  The render's rays
+// practically never carry an exact -0.0; a caller's axis-parallel ray (-e_z) often does.  The walk itself is the
+// benchmarked kernel's and stays as it is; the query hands it the direction with +0.0 instead.  The hit tests give the
+// same t and primitive for either sign of a zero component (it changes only the sign of products that are exactly
+// zero), and the hit record is built from the caller's direction.
+__device__ __forceinline__ double plus_zero(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return __longlong_as_double((long long)(b == 0x8000000000000000ull ? 0ull : b));
+}
+
+__device__ __forceinline__ unsigned q_lane_id() {
+  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+}
+
+// KERNEL: 1 = STREAM, 2 = BVH, 3 = GRID, 4 = BVH4, 5 = REFTREE (strict build only); LDS: the scene image is staged in
+// LDS (2 and 3; for 4: the whole image, else the top of its tree — the traversal stack is in LDS either way)
+template <int KERNEL, bool LDS>
+__global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
+    RTOW_QCAT(rtow_query_, RTOW_SUFFIX)(const QueryParams Q) {
+  const TraceParams &P = Q.P;
+  const DevScene &sc = P.sc;
+  const unsigned lane = q_lane_id();
+  [[maybe_unused]] const uint32_t lane_g = blockIdx.x * blockDim.x + threadIdx.x;
+
+  // ---- scene image in LDS: what the trace kernel stages for the same strategy (rtow_trace_body.h) ----
+  Image<LDS> im;
+  im.g = KERNEL == 3 ? sc.gblob : sc.blob;
+  [[maybe_unused]] Bvh4Reader<LDS> im4;
+  if constexpr (KERNEL == 4) {
+    im4.g = sc.blob4;
+    im4.lds_limit = sc.b4_lds_limit;
+    im4.aux_src = sc.b4_aux_src;
+    im4.aux_lds = sc.b4_aux_lds;
+    const uint4 *src = reinterpret_cast<const uint4 *>(sc.blob4);
+    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
+    const uint32_t n16 = sc.b4_lds_limit / 16u;
+    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    if (sc.b4_aux_src < sc.blob4_bytes) {
+      const uint4 *asrc = reinterpret_cast<const uint4 *>(sc.blob4 + sc.b4_aux_src);
+      uint4 *adst = reinterpret_cast<uint4 *>(rtow_lds + sc.b4_aux_lds);
+      const uint32_t a16 = (sc.blob4_bytes - sc.b4_aux_src) / 16u;
+      for (uint32_t i = threadIdx.x; i < a16; i += blockDim.x) adst[i] = asrc[i];
+    }
+    __syncthreads();
+  } else if constexpr ((KERNEL == 2 || KERNEL == 3) && LDS) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(im.g);
+    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
+    const uint32_t n16 = (KERNEL == 3 ? sc.gblob_bytes : sc.blob_bytes) / 16u;
+    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    __syncthreads();
+  }
+
+  uint32_t nnode = 0u, nprim = 0u;
+  Stamps<false> stamps;
+  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  // wave-uniform loop: every lane of the wave runs every step (the walks vote across the wave)
+  for (uint32_t base = wave * 64u; base < Q.n; base += n_waves * 64u) {
+    const uint32_t i = base + lane;
+    const bool active = i < Q.n;
+    V3 ro = {0, 0, 0}, rd = {0, 0, 1};
+    real rtime = 0, tmax = 0;
+    if (active) {
+      const vd2 *r = reinterpret_cast<const vd2 *>(Q.rays + (size_t)i * kRayBytes);
+      const vd2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];  // {ox, oy} {oz, time} {dx, dy} {dz, tmax}
+      ro = {r0.x, r0.y, r1.x};
+      rtime = r1.y;
+      rd = {r2.x, r2.y, r3.x};
+      tmax = r3.y;
+    }
+
+    // ---- closest hit over [0.001, inf): the render's walks, run to completion (cap = 0xffffffff) ----
+    Closest best;
+    best.t = (real)__builtin_huge_val();
+    best.prim = -1;
+    if constexpr (KERNEL == 4) {
+      uint32_t w_cur = kRefNone, w_sa = 0u;
+      best = closest_hit_bvh4<LDS, false>(im4, sc, P, ro, rd, rtime, active, lane_g, nnode, nprim, stamps, best, w_cur,
+                                          w_sa, 0xffffffffu, P.walk_max_open);
+    } else if constexpr (KERNEL == 3) {
+      float t_resume = 0.0f;
+      // (the fast build's walk returns t in the caller's parameter already: rtow_trace_grid.h, RTOW_UNIT_RAYS)
+      const V3 rd_walk = {plus_zero(rd.x), plus_zero(rd.y), plus_zero(rd.z)};
+      best = closest_hit_grid<LDS, false>(im, sc, ro, rd_walk, rtime, active, nnode, nprim, stamps, best, t_resume,
+                                          0xffffffffu, P.walk_max_open, P.leaf_votes);
+    } else if constexpr (KERNEL == 2) {
+      best = closest_hit_bvh<LDS, false>(im, sc, ro, rd, rtime, active, nnode, nprim, stamps);
+    } else if constexpr (KERNEL == 5) {
+#ifndef RTOW_FAST_MATH
+      if (active) best = closest_hit_reftree(sc, to_f64(ro), to_f64(rd), (double)rtime, nnode, nprim);
+#endif
+    } else {
+      best = closest_hit_stream(sc, to_f64(ro), to_f64(rd), (double)rtime, active);
+    }
+
+    // ---- the hit record of the winner (rtow_trace_body.h, `do_scat`: the same expressions) ----
+    const bool hit = active && best.prim >= 0 && best.t <= tmax;
+    if (active) {
+      double t = __builtin_huge_val();
+      V3 p = {0, 0, 0}, normal = {0, 0, 0};
+      int32_t prim = -1, kind = -1, mi = -1, front = 0;
+      if (hit) {
+        const int pid = best.prim;
+        t = best.t;
+        p = ro + rd * best.t;  // Ray::at (the trace kernel's scattered origin)
+        bool ff = true;        // triangles: front_facing is always true (src/common-model.cpp:121)
+        kind = pid < sc.n_sph ? 0 : (pid < sc.n_sph + sc.n_mov ? 1 : 2);
+        if constexpr (KERNEL == 4) {
+          const uint32_t r = sc.b4_off_tri + 96u * (uint32_t)pid;
+          const vd2 q4 = im4.t2(r + 64u), q5 = im4.t2(r + 80u);
+          normal = {(real)q4.y, (real)q5.x, (real)q5.y};
+          mi = (int)im4.u32(sc.b4_off_pmat + 4u * (uint32_t)pid);
+        } else if constexpr (KERNEL == 2 || KERNEL == 3) {
+          const uint32_t o_sph = KERNEL == 3 ? sc.g_off_sph : sc.off_sph;
+          const uint32_t o_mov = KERNEL == 3 ? sc.g_off_mov : sc.off_mov;
+          const uint32_t o_tri = KERNEL == 3 ? sc.g_off_tri : sc.off_tri;
+          const uint32_t o_pmat = KERNEL == 3 ? sc.g_off_pmat : sc.off_pmat;
+          if (pid < sc.n_sph + sc.n_mov) {
+            V3 center;
+            bool inward;
+            if (pid < sc.n_sph) {
+              const double2 p0 = im.d2(o_sph + 32u * (uint32_t)pid), p1 = im.d2(o_sph + 32u * (uint32_t)pid + 16u);
+              center = {(real)p0.x, (real)p0.y, (real)p1.x};
+              inward = p1.y < 0.0;
+            } else {
+              const uint32_t r = o_mov + 64u * (uint32_t)(pid - sc.n_sph);
+              const double2 p0 = im.d2(r), p1 = im.d2(r + 16u), p2 = im.d2(r + 32u), p3 = im.d2(r + 48u);
+              center = {p0.x + rtime * p1.y, p0.y + rtime * p2.x, p1.x + rtime * p2.y};
+              inward = p3.x < 0.0;
+            }
+            normal = normalize(p - center);
+            ff = (dot(rd, normal) < real(0.0)) ^ inward;
+            normal = ff ? normal : -normal;
+          } else {
+            const uint32_t r = o_tri + 96u * (uint32_t)(pid - sc.n_sph - sc.n_mov);
+            const double2 q4 = im.d2(r + 64u), q5 = im.d2(r + 80u);
+            normal = {q4.y, q5.x, q5.y};
+          }
+          mi = (int)im.u32(o_pmat + 4u * (uint32_t)pid);
+        } else {
+          if (pid < sc.n_sph + sc.n_mov) {
+            V3 center;
+            bool inward;
+            if (pid < sc.n_sph) {
+              const double *q = sc.sph + 4 * (size_t)pid;
+              center = {(real)q[0], (real)q[1], (real)q[2]};
+              inward = sc.sph_r[pid] < 0.0;
+            } else {
+              const double *q = sc.mov + 8 * (size_t)(pid - sc.n_sph);
+              center = {q[0] + rtime * q[3], q[1] + rtime * q[4], q[2] + rtime * q[5]};
+              inward = q[7] < 0.0;
+            }
+            normal = normalize(p - center);
+            ff = (dot(rd, normal) < real(0.0)) ^ inward;
+            normal = ff ? normal : -normal;
+          } else {
+            const double *q = sc.tri + 12 * (size_t)(pid - sc.n_sph - sc.n_mov);
+            normal = {(real)q[9], (real)q[10], (real)q[11]};
+          }
+          mi = sc.prim_mat[pid];
+        }
+        prim = Q.map[pid];
+        front = ff ? 1 : 0;
+      }
+      double *h = reinterpret_cast<double *>(Q.hits + (size_t)i * kHitBytes);
+      h[0] = t;
+      h[1] = p.x;
+      h[2] = p.y;
+      h[3] = p.z;
+      h[4] = normal.x;
+      h[5] = normal.y;
+      h[6] = normal.z;
+      int32_t *hi = reinterpret_cast<int32_t *>(h + 7);
+      reinterpret_cast<int2 *>(hi)[0] = make_int2(prim, kind);
+      reinterpret_cast<int2 *>(hi)[1] = make_int2(mi, front);
+    }
+  }
+
+  // statistics: one atomic per wave and counter
+  unsigned long long c0 = nprim, c1 = nnode;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    c0 += __shfl_down(c0, off);
+    c1 += __shfl_down(c1, off);
+  }
+  if (lane == 0) {
+    atomicAdd(&Q.counters[0], c0);
+    atomicAdd(&Q.counters[1], c1);
+  }
+}
+
+}  // namespace
+
+template <class Kern>
+static int q_no_static_lds(Kern k) {  // the walks address the dynamic LDS block from 0 (rtow_trace_math.h lds_read)
+  hipFuncAttributes fa;
+  const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k));
+  if (e != hipSuccess) return (int)e;
+  return fa.sharedSizeBytes == 0 ? 0 : (int)hipErrorInvalidValue;
+}
+
+template <int K, bool L>
+static const void *query_fn() {
+  return reinterpret_cast<const void *>(RTOW_QCAT(rtow_query_, RTOW_SUFFIX)<K, L>);
+}
+
+template <int K, bool L>
+static int launch_q(const QueryParams &q, int grid, int block, unsigned lds_bytes, hipStream_t st) {
+  auto k = RTOW_QCAT(rtow_query_, RTOW_SUFFIX)<K, L>;
+  static const int lds_ok = q_no_static_lds(k);
+  if (lds_ok != 0) return lds_ok;
+  if (lds_bytes > 48 * 1024) {
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds_bytes, st, q);
+  return (int)hipGetLastError();
+}
+
+// kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE (strict build).  `lds_bytes` > 0 selects the variant that stages
+// the image in LDS (2, 3); for 4 the image staged whole (b4_half == 0) selects the full-LDS variant, as in the render.
+int RTOW_QCAT(launch_query_, RTOW_SUFFIX)(const TraceParams &p, const void *rays, void *hits, uint32_t n,
+                                          const int32_t *map, unsigned long long *counters, int kernel, int grid,
+                                          int block, unsigned lds_bytes, void *stream) {
+  QueryParams q;
+  q.P = p;
+  q.rays = (const unsigned char *)rays;
+  q.hits = (unsigned char *)hits;
+  q.n = n;
+  q.map = map;
+  q.counters = counters;
+  hipStream_t st = (hipStream_t)stream;
+  const bool lds = lds_bytes > 0;
+  switch (kernel) {
+    case 1: return launch_q<1, false>(q, grid, block, lds_bytes, st);  // (LDS: the tiled triangle loop's per-wave tiles)
+    case 2: return lds ? launch_q<2, true>(q, grid, block, lds_bytes, st) : launch_q<2, false>(q, grid, block, 0, st);
+    case 3: return lds ? launch_q<3, true>(q, grid, block, lds_bytes, st) : launch_q<3, false>(q, grid, block, 0, st);
+    case 4:
+      return p.sc.b4_half == 0u ? launch_q<4, true>(q, grid, block, lds_bytes, st)
+                                : launch_q<4, false>(q, grid, block, lds_bytes, st);
+#ifndef RTOW_FAST_MATH
+    case 5: return launch_q<5, false>(q, grid, block, 0, st);
+#endif
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
+// Workgroups per CU that stay resident (the rule of trace_occupancy_*, rtow_trace_body.h): min over the register file
+// (512 VGPRs per SIMD lane in granules of 8, at most 8 waves per SIMD), the four SIMDs and the 160 KiB of LDS.
+int RTOW_QCAT(query_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+  const bool lds = lds_bytes > 0;
+  const void *fn;
+  switch (kernel) {
+    case 1: fn = query_fn<1, false>(); break;
+    case 2: fn = lds ? query_fn<2, true>() : query_fn<2, false>(); break;
+    case 3: fn = lds ? query_fn<3, true>() : query_fn<3, false>(); break;
+    case 4: fn = query_fn<4, true>(); break;  // (both variants have the same launch bounds)
+#ifndef RTOW_FAST_MATH
+    case 5: fn = query_fn<5, false>(); break;
+#endif
+    default: return -1;
+  }
+  if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
+  if (fa.sharedSizeBytes != 0) return -1;
+  const int regs = fa.numRegs > 0 ? fa.numRegs : 128;
+  if (vgprs) *vgprs = regs;
+  const int alloc = ((regs + 7) / 8) * 8;
+  int waves_per_simd = 512 / alloc;
+  if (waves_per_simd > 8) waves_per_simd = 8;
+  if (waves_per_simd < 1) waves_per_simd = 1;
+  int nb = (waves_per_simd * 4) / (block / 64);
+  if (lds_bytes > 0) {
+    const int by_lds = (int)((160u * 1024u) / lds_bytes);
+    if (by_lds < nb) nb = by_lds;
+  }
+  return nb < 1 ? 1 : nb;
+}
+
+}  // namespace rtow

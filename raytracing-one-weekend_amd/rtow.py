@@ -13,11 +13,13 @@ import ctypes as C
 import os
 from pathlib import Path
 
+import numpy as np
+
 PKG_DIR = Path(__file__).resolve().parent
 REPO_ROOT = PKG_DIR.parent
 LIB_PATH = Path(os.environ.get("RTOW_LIB", PKG_DIR / "librtow.so"))  # RTOW_LIB: A/B against another build
 
-RTOW_ABI_VERSION = 7
+RTOW_ABI_VERSION = 8
 RTOW_OK, RTOW_EINVAL, RTOW_ENODEV, RTOW_EHIP, RTOW_ENOSCENE, RTOW_EEMPTY, RTOW_ENOMEM = 0, -1, -2, -3, -4, -5, -6
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2
 PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_TRIANGLE = 0, 1, 2
@@ -96,6 +98,37 @@ class HostConfig(C.Structure):
     ]
 
 
+class Ray(C.Structure):
+    """rtow_ray_t (64 B): the closest hit in [0.001, tmax] is reported."""
+    _fields_ = [("origin", d3), ("time", C.c_double), ("direction", d3), ("tmax", C.c_double)]
+
+
+class Hit(C.Structure):
+    """rtow_hit_t (72 B): t = inf and prim = kind = material = -1 on a miss."""
+    _fields_ = [
+        ("t", C.c_double), ("point", d3), ("normal", d3),
+        ("prim", C.c_int32), ("kind", C.c_int32), ("material", C.c_int32), ("front_face", C.c_int32),
+    ]
+
+
+# numpy views of the same layouts (arrays of rays / hits for rtow_intersect*)
+RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("time", "<f8"), ("direction", "<f8", (3,)), ("tmax", "<f8")])
+HIT_DTYPE = np.dtype([("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("prim", "<i4"), ("kind", "<i4"),
+                      ("material", "<i4"), ("front_face", "<i4")])
+
+
+def make_rays(origins, directions, time=0.0, tmax=float("inf")):
+    """A RAY_DTYPE array from [n, 3] origins and directions (time and tmax: scalars or [n])."""
+    o = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+    r = np.empty(len(o), dtype=RAY_DTYPE)
+    r["origin"] = o
+    r["direction"] = d
+    r["time"] = time
+    r["tmax"] = tmax
+    return r
+
+
 # every symbol include/rtow.h declares
 EXPORTS = [
     "rtow_abi_version", "rtow_last_error", "rtow_ctx_create", "rtow_ctx_destroy",
@@ -108,6 +141,7 @@ EXPORTS = [
     "rtow_multi_create", "rtow_multi_set_builder", "rtow_multi_upload", "rtow_multi_build_info",
     "rtow_multi_render", "rtow_multi_destroy", "rtow_host_reftree_info",
     "rtow_render_device_rgb8", "rtow_multi_render_rgb8", "rtow_multi_frame_breakdown",
+    "rtow_intersect_device", "rtow_intersect",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -184,6 +218,11 @@ def lib():
         L.rtow_multi_render_rgb8.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.POINTER(Stats)]
         L.rtow_render_device_rgb8.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.rtow_render_rgb8.argtypes = [C.c_void_p, C.POINTER(Scene), C.POINTER(Config), C.c_void_p, C.POINTER(Stats)]
+    if hasattr(L, "rtow_intersect"):
+        L.rtow_intersect_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_void_p, C.POINTER(Stats)]
+        L.rtow_intersect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.POINTER(Stats)]
     L.rtow_profile_collect.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     if hasattr(L, "rtow_debug_schedule"):  # (absent from older builds loaded through RTOW_LIB for A/B runs)
         L.rtow_debug_schedule.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(C.c_uint32), C.c_int32]
@@ -371,6 +410,27 @@ class Context:
         st = Stats() if want_stats else None
         check(lib().rtow_render_device_rgb8(self._h, C.byref(cfg), C.c_void_p(d_ptr), C.c_void_p(stream),
                                             C.byref(st) if st is not None else None), "rtow_render_device_rgb8")
+        return st
+
+    def intersect(self, rays, precision=F64_FAST, kernel=KERNEL_AUTO, want_stats=False):
+        """Closest hit of every ray (a RAY_DTYPE array, host memory) against the resident scene: a HIT_DTYPE array,
+        and Stats with `want_stats` (rtow_intersect)."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        hits = np.empty(len(r), dtype=HIT_DTYPE)
+        st = Stats() if want_stats else None
+        check(lib().rtow_intersect(self._h, precision, kernel, r.ctypes.data_as(C.c_void_p), len(r),
+                                   hits.ctypes.data_as(C.c_void_p), C.byref(st) if st is not None else None),
+              "rtow_intersect")
+        return (hits, st) if want_stats else hits
+
+    def intersect_device(self, d_rays: int, n: int, d_hits: int, precision=F64_FAST, kernel=KERNEL_AUTO,
+                         stream: int = 0, want_stats=False):
+        """The same on device buffers (raw pointers: n x 64-byte rays, n x 72-byte hits), enqueued on `stream`
+        (rtow_intersect_device); returns Stats with `want_stats` (then synchronised), else None."""
+        st = Stats() if want_stats else None
+        check(lib().rtow_intersect_device(self._h, precision, kernel, C.c_void_p(d_rays), n, C.c_void_p(d_hits),
+                                          C.c_void_p(stream), C.byref(st) if st is not None else None),
+              "rtow_intersect_device")
         return st
 
     def profile_collect(self):
