@@ -307,8 +307,12 @@ int rtow_debug_counters(rtow_ctx *ctx, unsigned long long *out48);
 int rtow_debug_schedule(rtow_ctx *ctx, const rtow_config_t *cfg, uint32_t *out_pairs, int32_t capacity_pairs);
 
 /* Diagnostic only: copies a resident scene image to the host (which: 0 BVH image, 1 grid image,
- * 2 / 3 the same of the RTOW_F32 build).  `out` NULL: size query.  The tests compare host-built
- * and device-built images byte for byte with it. */
+ * 2 / 3 the same of the RTOW_F32 build, 4 the 4-wide BVH image of a triangle mesh, 5 the 48-byte frame record
+ * of the 4-wide walk: double c[3], float is[3] (binary16 planes decode as c + h * is per axis), uint32_t half
+ * (1: 64-byte nodes with binary16 planes), uint32_t lds_limit (the resident scene's; every launch sets the bytes it
+ * stages on its own copy), 4 bytes of padding).  Size 0 for an image that is not
+ * resident (4 and 5 without a 4-wide image).  `out` NULL: size query.  The tests compare host-built and
+ * device-built images byte for byte with it and check them against the geometry. */
 int rtow_debug_image(rtow_ctx *ctx, int32_t which, void *out, int64_t capacity, int64_t *size_out);
 
 /* ---- closest-hit ray queries ------------------------------------------------------------------------------------

@@ -529,7 +529,11 @@ static int validate_scene(const rtow_scene_t *s) {
 }
 
 static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need);
-static int impl_scene_upload(rtow_ctx *c, const rtow_scene_t *s) { return scene_upload(c, s, kNeedAll); }
+static int impl_scene_upload(rtow_ctx *c, const rtow_scene_t *s) {
+  // AUTO knows no config here: the host builder (include/rtow.h), whatever an earlier rtow_render resolved AUTO to
+  if (c && c->builder_req == RTOW_BUILDER_AUTO) c->builder = RTOW_BUILDER_HOST_SAH;
+  return scene_upload(c, s, kNeedAll);
+}
 
 static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
   if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
@@ -1769,22 +1773,49 @@ static int impl_intersect(rtow_ctx *c, int32_t precision, int32_t kernel, const 
 }
 
 // Diagnostic: copy a resident scene image to the host (0 BVH, 1 grid, 2 BVH of the f32 build,
-// 3 grid of the f32 build).  Used by the tests to compare host- and device-built images.
+// 3 grid of the f32 build, 4 the 4-wide BVH, 5 the 48-byte frame record of the 4-wide walk: Bvh4Frame).
+// Used by the tests to compare host- and device-built images and to check them against the geometry.
+struct Bvh4Frame {   // rtow_debug_image(5): what the 4-wide walk decodes binary16 planes with (world = c + h * is)
+  double c[3];       // DevScene::b4_c
+  float is[3];       // DevScene::b4_is, as stored
+  uint32_t half;     // DevScene::b4_half: 64-byte nodes with binary16 planes
+  uint32_t lds_limit;  // DevScene::b4_lds_limit of the resident scene (the launches set their own copy's)
+  uint32_t pad_;
+};
+static_assert(sizeof(Bvh4Frame) == 48, "rtow_debug_image(5) record");
+
 int rtow_debug_image(rtow_ctx *c, int32_t which, void *out, int64_t capacity, int64_t *size_out) {
   if (!c || !size_out) return fail(RTOW_EINVAL, "NULL argument");
   if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
   const void *src = nullptr;
   int64_t bytes = 0;
+  Bvh4Frame frame{};
   switch (which) {
     case 0: src = c->blob.p; bytes = c->ds.blob_bytes; break;
     case 1: src = c->gblob.p; bytes = c->ds.gblob_bytes; break;
     case 2: src = c->blob32.p; bytes = c->ds32.blob_bytes; break;
     case 3: src = c->gblob32.p; bytes = c->ds32.gblob_bytes; break;
+    case 4: src = c->blob4.p; bytes = c->have_bvh4 ? c->ds.blob4_bytes : 0; break;
+    case 5:
+      if (c->have_bvh4) {
+        for (int k = 0; k < 3; ++k) {
+          frame.c[k] = c->ds.b4_c[k];
+          frame.is[k] = c->ds.b4_is[k];
+        }
+        frame.half = c->ds.b4_half;
+        frame.lds_limit = c->ds.b4_lds_limit;
+        bytes = (int64_t)sizeof frame;
+      }
+      break;
     default: return fail(RTOW_EINVAL, "unknown image %d", which);
   }
   *size_out = bytes;
   if (!out) return RTOW_OK;  // size query
   if (capacity < bytes) return fail(RTOW_EINVAL, "buffer too small (%lld < %lld)", (long long)capacity, (long long)bytes);
+  if (which == 5) {
+    if (bytes) std::memcpy(out, &frame, sizeof frame);
+    return RTOW_OK;
+  }
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipDeviceSynchronize());
   if (bytes) HIPCHK(hipMemcpy(out, src, (size_t)bytes, hipMemcpyDeviceToHost));

@@ -352,7 +352,9 @@ class Context:
         check(lib().rtow_ctx_set_builder(self._h, builder), "rtow_ctx_set_builder")
 
     def debug_image(self, which: int) -> bytes:
-        """A resident scene image (0 BVH, 1 grid, 2/3 the f32 build's), for tests."""
+        """A resident scene image, for tests: 0 BVH, 1 grid, 2/3 the f32 build's, 4 the 4-wide BVH, 5 the 4-wide
+        walk's 48-byte frame record (double c[3], float is[3], uint32 half, uint32 lds_limit, pad).  b"" when that
+        image is not resident."""
         n = C.c_int64()
         check(lib().rtow_debug_image(self._h, which, None, 0, C.byref(n)), "rtow_debug_image")
         buf = (C.c_ubyte * max(n.value, 1))()
