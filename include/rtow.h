@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RTOW_ABI_VERSION 8
+#define RTOW_ABI_VERSION 9
 
 /* error codes */
 #define RTOW_OK 0
@@ -367,6 +367,35 @@ int rtow_intersect_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, cons
 /* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
 int rtow_intersect(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
                    rtow_hit_t *hits, rtow_stats_t *stats);
+
+/* ---- any-hit (occlusion) ray queries --------------------------------------------------------------------------------
+ * "Is there anything between here and there?" — the shadow / visibility test: for every ray, occluded[i] = 1 if some
+ * primitive's hit test accepts a t in [0.001, tmax], else 0.  Exactly when rtow_intersect with the same precision and
+ * kernel reports a hit (hits[i].t <= tmax), but the walks are seeded with tmax (box and cell culling prune at it from the
+ * first node) and a ray stops at its first accepted hit, so a short or occluded ray pays for what it needs only.
+ * d_rays: the rtow_ray_t rays of rtow_intersect_device (DEVICE memory, 16-byte aligned); d_occluded: n_rays bytes of
+ * DEVICE memory (no alignment; a torch.bool tensor), each written 0 or 1 — nothing beyond n_rays is written.  Enqueued on
+ * hip_stream with the ordering rule of rtow_intersect_device; returns without synchronising unless stats != NULL, which
+ * synchronises and fills segments = n_rays, prim_tests and node_tests (the tests the any-hit walks ran: BRUTE counts
+ * its primitive tests too), kernel_ms, total_ms, kernel_used; samples = local_rows = 0.
+ *
+ *   precision  RTOW_F64_STRICT: occluded[i] == (rtow_intersect(...).t <= tmax) for every ray, under every kernel (and
+ *                               the same under BRUTE, BVH, GRID and BVH4 for time in [0, 1]);
+ *              RTOW_F64_FAST:   the fast build's walks; may differ from the fast closest hit's t <= tmax only where
+ *                               |t - tmax| <= 1e-9 * max(1, tmax);
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ *   kernel     as rtow_intersect_device: the same resolution, fallbacks, residency rules (RTOW_ENOSCENE after a lean
+ *              upload) and kernel_used; RTOW_KERNEL_REFTREE is strict only (it runs the reference tree's closest hit and
+ *              compares it with tmax).
+ *   tmax       +inf: "hits anything"; below 0.001, or NaN: 0 (the ray skips the walk).
+ * Errors: those of rtow_intersect_device (the result buffer has no alignment requirement).  n_rays == 0 returns RTOW_OK
+ * and launches nothing.  The first call after an upload does no host work (no primitive ids to translate).  One call in
+ * flight per context, as for the renders; the render path is not involved. */
+int rtow_occluded_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays,
+                         void *d_occluded /* uint8_t[n_rays] */, void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
+int rtow_occluded(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
+                  uint8_t *occluded, rtow_stats_t *stats);
 
 /* Convenience: upload + render + copy this rank's rows to host memory.
  * Lean upload: rtow_render / rtow_render_rgb8 know their config and build only the structures ITS kernel reads

@@ -250,6 +250,13 @@ int launch_query_fast(const TraceParams &p, const void *rays, void *hits, uint32
                       unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
 int query_occupancy_strict(int kernel, int block, unsigned lds_bytes, int *vgprs);
 int query_occupancy_fast(int kernel, int block, unsigned lds_bytes, int *vgprs);
+// csrc/rtow_occlude_{strict,fast}.hip (rtow_occlude.h)
+int launch_occlude_strict(const TraceParams &p, const void *rays, void *occluded, uint32_t n, unsigned long long *counters,
+                          int kernel, int grid, int block, unsigned lds_bytes, void *stream);
+int launch_occlude_fast(const TraceParams &p, const void *rays, void *occluded, uint32_t n, unsigned long long *counters,
+                        int kernel, int grid, int block, unsigned lds_bytes, void *stream);
+int occlude_occupancy_strict(int kernel, int block, unsigned lds_bytes, int *vgprs);
+int occlude_occupancy_fast(int kernel, int block, unsigned lds_bytes, int *vgprs);
 }  // namespace rtow
 
 // Experiment knobs (RTOW_* environment variables), read ONCE at rtow_ctx_create: nothing on the
@@ -411,10 +418,10 @@ struct rtow_ctx {
   hipEvent_t call_ev[2] = {};
   // pinned host mirror of the counters for stats
   unsigned long long *h_counters = nullptr;
-  // ray queries (rtow_intersect*): counters, events, spill and staging of their own (a query never touches the render's
-  // workspace, profile ring or dropped-sample word); the walk-id -> insertion-index tables are built at the first query
-  // that needs them after an upload (query_map)
-  DevBuf q_counters, q_spill, q_rays, q_hits, q_map[3];
+  // ray queries (rtow_intersect*, rtow_occluded*): counters, events, spill and staging of their own (a query never
+  // touches the render's workspace, profile ring or dropped-sample word); the walk-id -> insertion-index tables are built
+  // at the first closest-hit query that needs them after an upload (query_map)
+  DevBuf q_counters, q_spill, q_rays, q_hits, q_occ, q_map[3];
   bool q_map_ok[3] = {false, false, false};
   hipEvent_t q_ev[4] = {};
   unsigned long long *h_qcounters = nullptr;
@@ -480,7 +487,7 @@ void rtow_ctx_destroy(rtow_ctx *c) {
   for (DevBuf *b : {&c->sph, &c->sph_r, &c->mov, &c->tri, &c->tri16, &c->prim_mat, &c->mats, &c->blob, &c->cam_dev, &c->gblob,
                     &c->blob32, &c->gblob32, &c->cam32_dev, &c->blob4,
                     &c->partials, &c->stack, &c->counters, &c->spill, &c->out, &c->out8, &c->rtree, &c->counters_init,
-                    &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_map[0], &c->q_map[1],
+                    &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_occ, &c->q_map[0], &c->q_map[1],
                     &c->q_map[2]})
     b->release();
   for (hipEvent_t e : c->q_ev)
@@ -1672,49 +1679,54 @@ static int query_map(rtow_ctx *c, int which, const int32_t **out) {
   return RTOW_OK;
 }
 
-static int impl_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_rays, int64_t n_rays,
-                                 void *d_hits, void *hip_stream, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
-  if (n_rays > 0 && (!d_rays || !d_hits)) return fail(RTOW_EINVAL, "NULL ray or hit buffer");
-  if (((uintptr_t)d_rays & 15u) != 0u || ((uintptr_t)d_hits & 7u) != 0u)
-    return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned, hit buffer 8-byte aligned");
+// What the two ray queries (rtow_intersect*, rtow_occluded*) share around their kernels.  query_begin: the argument
+// checks after the buffers', the strategy (the render's resolution and residency rules), the launch shape, the stats
+// header.  query_launch: the grid from the kernel's occupancy, the BVH4 spill, the walk fields, and the launch between
+// events on the caller's stream (ordered behind the last upload); with stats, the counters and times.
+struct QueryRun {
+  int kernel = 0;
+  bool strict = false;
+  LaunchShape shape;
+};
+static int query_begin(rtow_ctx *c, int32_t precision, int32_t kernel_req, rtow_stats_t *stats, QueryRun &q) {
   if (precision == RTOW_F32) return fail(RTOW_EINVAL, "ray queries: RTOW_F32 is not supported (binary64 builds only)");
   if (precision != RTOW_F64_STRICT && precision != RTOW_F64_FAST) return fail(RTOW_EINVAL, "unknown precision %d", precision);
   if (kernel_req < RTOW_KERNEL_AUTO || kernel_req > RTOW_KERNEL_REFTREE) return fail(RTOW_EINVAL, "unknown kernel %d", kernel_req);
   if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
   HIPCHK(hipSetDevice(c->device));
-  int rc, kernel = 0;
-  if ((rc = resolve_kernel(c, precision, kernel_req, &kernel))) return rc;
-  LaunchShape shape;
-  if ((rc = launch_shape(c, kernel, false, shape))) return rc;
-  const bool strict = precision == RTOW_F64_STRICT;
+  int rc;
+  if ((rc = resolve_kernel(c, precision, kernel_req, &q.kernel))) return rc;
+  if ((rc = launch_shape(c, q.kernel, false, q.shape))) return rc;
+  q.strict = precision == RTOW_F64_STRICT;
   if (stats) {
     std::memset(stats, 0, sizeof *stats);
-    stats->kernel_used = kernel;
+    stats->kernel_used = q.kernel;
   }
-  if (n_rays == 0) return RTOW_OK;
+  return RTOW_OK;
+}
 
-  const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
-  const int32_t *map = nullptr;
-  if ((rc = query_map(c, which, &map))) return rc;
-  const int block = shape.block;
-  int occ = strict ? rtow::query_occupancy_strict(kernel, block, shape.lds_bytes, nullptr)
-                   : rtow::query_occupancy_fast(kernel, block, shape.lds_bytes, nullptr);
-  if (occ <= 0) return fail(RTOW_EHIP, "query occupancy failed (kernel %d, %u B of LDS)", kernel, shape.lds_bytes);
+// occ: workgroups per CU of the query's kernel (<= 0: the occupancy query failed); launch(P, counters, grid): enqueue
+// the kernel on `st`, returning 0 or a hipError_t
+extern "C++" template <class Launch>
+static int query_launch(rtow_ctx *c, const QueryRun &q, int64_t n_rays, int occ, void *hip_stream, rtow_stats_t *stats,
+                        Launch &&launch) {
+  const int kernel = q.kernel;
+  if (occ <= 0) return fail(RTOW_EHIP, "query occupancy failed (kernel %d, %u B of LDS)", kernel, q.shape.lds_bytes);
   occ = std::min(occ, 8);
+  const int block = q.shape.block;
   long long grid = (long long)c->num_cus * occ;
   const long long need_blocks = (n_rays + block - 1) / block;
   grid = std::max(std::min(grid, need_blocks), 1ll);
   const unsigned long long n_lanes = (unsigned long long)grid * block;
+  int rc;
   if ((rc = c->q_counters.ensure(2 * sizeof(unsigned long long)))) return rc;
   if (kernel == RTOW_KERNEL_BVH4) {
-    const int extra = std::max(shape.stack_bound - (int)shape.scene.b4_stack_k, 0);
+    const int extra = std::max(q.shape.stack_bound - (int)q.shape.scene.b4_stack_k, 0);
     if ((rc = c->q_spill.ensure(std::max<size_t>((size_t)extra * (size_t)n_lanes * sizeof(uint32_t), 16)))) return rc;
   }
   rtow::TraceParams P;
   std::memset(&P, 0, sizeof P);
-  P.sc = shape.scene;
+  P.sc = q.shape.scene;
   P.n_lanes = (uint32_t)n_lanes;
   P.spill = (uint32_t *)c->q_spill.p;
   // every walk runs to completion (cap 0xffffffff); the leaf-phase quorum is the render's
@@ -1733,10 +1745,7 @@ static int impl_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel_
   HIPCHK(hipMemsetAsync(c->q_counters.p, 0, 2 * sizeof(unsigned long long), st));
   if (stats) HIPCHK(hipEventRecord(c->q_ev[1], st));
   auto *counters = (unsigned long long *)c->q_counters.p;
-  const int lrc = strict ? rtow::launch_query_strict(P, d_rays, d_hits, (uint32_t)n_rays, map, counters, kernel, (int)grid,
-                                                     block, shape.lds_bytes, st)
-                         : rtow::launch_query_fast(P, d_rays, d_hits, (uint32_t)n_rays, map, counters, kernel, (int)grid,
-                                                   block, shape.lds_bytes, st);
+  const int lrc = launch(P, counters, (int)grid);
   if (lrc != 0) return fail(RTOW_EHIP, "query kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
   if (stats) {
     HIPCHK(hipEventRecord(c->q_ev[2], st));
@@ -1749,9 +1758,81 @@ static int impl_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel_
     HIPCHK(hipEventElapsedTime(&ms, c->q_ev[0], c->q_ev[3]));
     stats->total_ms = ms;
     stats->segments = (uint64_t)n_rays;
-    stats->prim_tests = kernel == RTOW_KERNEL_BRUTE ? (uint64_t)n_rays * (uint64_t)c->n_prims : c->h_qcounters[0];
+    stats->prim_tests = c->h_qcounters[0];
     stats->node_tests = kernel == RTOW_KERNEL_BRUTE ? 0u : c->h_qcounters[1];
   }
+  return RTOW_OK;
+}
+
+static int impl_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_rays, int64_t n_rays,
+                                 void *d_hits, void *hip_stream, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
+  if (n_rays > 0 && (!d_rays || !d_hits)) return fail(RTOW_EINVAL, "NULL ray or hit buffer");
+  if (((uintptr_t)d_rays & 15u) != 0u || ((uintptr_t)d_hits & 7u) != 0u)
+    return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned, hit buffer 8-byte aligned");
+  QueryRun q;
+  int rc;
+  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
+  if (n_rays == 0) return RTOW_OK;
+
+  const int kernel = q.kernel;
+  const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
+  const int32_t *map = nullptr;
+  if ((rc = query_map(c, which, &map))) return rc;
+  const int block = q.shape.block;
+  const unsigned lds = q.shape.lds_bytes;
+  const int occ = q.strict ? rtow::query_occupancy_strict(kernel, block, lds, nullptr)
+                           : rtow::query_occupancy_fast(kernel, block, lds, nullptr);
+  rc = query_launch(c, q, n_rays, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
+    return q.strict ? rtow::launch_query_strict(P, d_rays, d_hits, (uint32_t)n_rays, map, counters, kernel, grid, block, lds,
+                                                hip_stream)
+                    : rtow::launch_query_fast(P, d_rays, d_hits, (uint32_t)n_rays, map, counters, kernel, grid, block, lds,
+                                              hip_stream);
+  });
+  if (rc == RTOW_OK && stats && kernel == RTOW_KERNEL_BRUTE)
+    stats->prim_tests = (uint64_t)n_rays * (uint64_t)c->n_prims;  // (the closest-hit STREAM walk tests every primitive)
+  return rc;
+}
+
+// Any-hit queries: the closest-hit query's contract without its hit records (so no query_map: nothing to translate).
+static int impl_occluded_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_rays, int64_t n_rays,
+                                void *d_occluded, void *hip_stream, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
+  if (n_rays > 0 && (!d_rays || !d_occluded)) return fail(RTOW_EINVAL, "NULL ray or result buffer");
+  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
+  QueryRun q;
+  int rc;
+  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
+  if (n_rays == 0) return RTOW_OK;
+
+  const int kernel = q.kernel;
+  const int block = q.shape.block;
+  const unsigned lds = q.shape.lds_bytes;
+  const int occ = q.strict ? rtow::occlude_occupancy_strict(kernel, block, lds, nullptr)
+                           : rtow::occlude_occupancy_fast(kernel, block, lds, nullptr);
+  return query_launch(c, q, n_rays, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
+    return q.strict ? rtow::launch_occlude_strict(P, d_rays, d_occluded, (uint32_t)n_rays, counters, kernel, grid, block, lds,
+                                                  hip_stream)
+                    : rtow::launch_occlude_fast(P, d_rays, d_occluded, (uint32_t)n_rays, counters, kernel, grid, block, lds,
+                                                hip_stream);
+  });
+}
+
+static int impl_occluded(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
+                         uint8_t *occluded, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
+  if (n_rays > 0 && (!rays || !occluded)) return fail(RTOW_EINVAL, "NULL ray or result array");
+  if (n_rays == 0) return impl_occluded_device(c, precision, kernel, nullptr, 0, nullptr, nullptr, stats);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = c->q_rays.ensure((size_t)n_rays * sizeof(rtow_ray_t))) || (rc = c->q_occ.ensure((size_t)n_rays))) return rc;
+  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n_rays * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
+  if ((rc = impl_occluded_device(c, precision, kernel, c->q_rays.p, n_rays, c->q_occ.p, nullptr, stats))) return rc;
+  HIPCHK(hipMemcpy(occluded, c->q_occ.p, (size_t)n_rays, hipMemcpyDeviceToHost));
   return RTOW_OK;
 }
 
@@ -2013,6 +2094,15 @@ int rtow_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel, const 
 int rtow_intersect(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, rtow_hit_t *hits,
                    rtow_stats_t *stats) {
   return guarded("rtow_intersect", [&] { return impl_intersect(c, precision, kernel, rays, n_rays, hits, stats); });
+}
+int rtow_occluded_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays,
+                         void *d_occluded, void *hip_stream, rtow_stats_t *stats) {
+  return guarded("rtow_occluded_device",
+                 [&] { return impl_occluded_device(c, precision, kernel, d_rays, n_rays, d_occluded, hip_stream, stats); });
+}
+int rtow_occluded(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, uint8_t *occluded,
+                  rtow_stats_t *stats) {
+  return guarded("rtow_occluded", [&] { return impl_occluded(c, precision, kernel, rays, n_rays, occluded, stats); });
 }
 int rtow_debug_schedule(rtow_ctx *c, const rtow_config_t *cfg, uint32_t *out, int32_t capacity_pairs) {
   return guarded("rtow_debug_schedule", [&] { return impl_debug_schedule(c, cfg, out, capacity_pairs); });

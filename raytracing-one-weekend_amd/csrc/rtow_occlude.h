@@ -1,0 +1,598 @@
+// rtow_occlude.h — the any-hit (occlusion) ray query kernel (rtow_occluded / rtow_occluded_device, include/rtow.h),
+// included by rtow_occlude_strict.hip and rtow_occlude_fast.hip, which differ only in -ffp-contract and in RTOW_SUFFIX.
+//
+// What it computes: for every caller ray, 1 if some primitive's hit test accepts a t in [0.001, tmax], else 0 — the
+// shadow / visibility question.  The walks below are any-hit versions of the render's walks (rtow_trace_bvh.h,
+// rtow_trace_grid.h, rtow_trace_bvh4.h, rtow_trace_hit.h): the closest-so-far value starts at the ray's tmax instead of
+// +inf, so box and cell culling prune at tmax from the first node, and a lane stops at the end of the first leaf phase
+// in which it accepts a hit.  The pieces they are built from (Image, the ray forms, leaf_test, the hit tests, the
+// 4-wide step, leaf and stack) are the render's, included read-only; the benchmarked walks themselves are not touched.
+//
+// Why seeding is exact: a primitive's hit test with upper bound tmax accepts exactly when its unbounded test returns a
+// t <= tmax (sphere_resolve picks its root by tmin alone: root1 <= root2, so a near root beyond tmax rules out the far
+// one; a triangle has one t), and the f32 box / cell intervals are conservative as they are for the closest-hit walks.
+// So the answer equals `closest hit over [0.001, inf) <= tmax` — bit-determined in the strict build, the same under
+// every strategy.  (The fast build's grid walk compares in distance units, tmax * |d|, and its triangle test compares
+// t * det: the answer can differ from the fast closest hit's `t <= tmax` only when t is within rounding of tmax.)
+//
+// Execution model: that of the closest-hit query (rtow_query.h): persistent waves of 64 consecutive rays, the scene
+// image staged in LDS per workgroup exactly as the render stages it, lanes past n_rays (and rays whose tmax is below
+// 0.001 or NaN) entering the walks with active = false.  One byte per ray: a wave writes 64 contiguous bytes.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rtow_device.h"
+
+#ifndef RTOW_SUFFIX
+#error "define RTOW_SUFFIX"
+#endif
+#define RTOW_OCAT2(a, b) a##b
+#define RTOW_OCAT(a, b) RTOW_OCAT2(a, b)
+
+namespace rtow {
+namespace {
+#include "rtow_trace_math.h"
+#include "rtow_trace_hit.h"
+#include "rtow_trace_stamps.h"
+#include "rtow_trace_bvh.h"
+#include "rtow_trace_grid.h"
+#include "rtow_trace_bvh4.h"
+#ifndef RTOW_FAST_MATH
+#include "rtow_trace_reftree.h"
+#endif
+
+constexpr uint32_t kORayBytes = 64u;  // rtow_ray_t, include/rtow.h
+
+struct OccludeParams {
+  TraceParams P;               // the scene (P.sc) and the walks' launch fields: spill, n_lanes, leaf_votes
+  const unsigned char *rays;   // [n][64 B], 16-byte aligned
+  unsigned char *occluded;     // [n] bytes, 0 or 1
+  uint32_t n;
+  unsigned long long *counters;  // [0] primitive tests, [1] node tests
+};
+
+// The closest-so-far value a walk starts from: the ray's tmax (+inf: no bound).
+__device__ __forceinline__ Closest seeded(double tmax) {
+  Closest best;
+  best.t = (real)tmax;
+  best.prim = -1;
+  return best;
+}
+
+// ---- BVH: the threaded walk of closest_hit_bvh (rtow_trace_bvh.h), seeded, with early exit ----
+template <bool LDS>
+__device__ __forceinline__ bool any_hit_bvh(const Image<LDS> &im, const DevScene &sc, V3 o, V3 d, real time, double tmax,
+                                            bool active, uint32_t &nnode, uint32_t &nprim) {
+  Closest best = seeded(tmax);
+  const RayForms ray = make_ray_forms(o, d, time);
+  const float ix = safe_inv((float)d.x), iy = safe_inv((float)d.y), iz = safe_inv((float)d.z);
+  const float oix = (float)o.x * ix, oiy = (float)o.y * iy, oiz = (float)o.z * iz;
+  const float tmin32 = 0.0009f;  // < RTOW_TMIN
+  const float slack = 1.00002f;  // relative slack on the far side of the interval
+  const float tmax32 = round_up_f32(best.t);  // the bound: fixed, the walk ends at the first hit
+  const uint32_t END = (uint32_t)sc.n_nodes;
+  const ImgOffsets off = {sc.off_ids, sc.off_sph, sc.off_mov, sc.off_tri, 0u, 0u, sc.off_sph32, sc.off_mov32};
+  int last_id = -1;
+  uint32_t node = active ? 0u : END;
+  uint32_t q0 = 0u, q1 = 0u, q2 = 0u, q3 = 0u;  // queued leaves (0 = empty), oldest first
+  for (;;) {
+    if (node < END) {
+      const float4 r0 = im.f4(node * 32u), r1 = im.f4(node * 32u + 16u);
+      ++nnode;
+      const float ax = fmaf(r0.x, ix, -oix), bx = fmaf(r0.w, ix, -oix);
+      const float ay = fmaf(r0.y, iy, -oiy), by = fmaf(r1.x, iy, -oiy);
+      const float az = fmaf(r0.z, iz, -oiz), bz = fmaf(r1.y, iz, -oiz);
+      const float tnear = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tmin32));
+      const float tfar = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tmax32));
+      const bool hit = tnear <= tfar * slack;
+      const uint32_t skip = __float_as_uint(r1.z), leaf = __float_as_uint(r1.w);
+      if (hit && leaf != 0u) {
+        if (q0 == 0u)
+          q0 = leaf;
+        else if (q1 == 0u)
+          q1 = leaf;
+        else if (q2 == 0u)
+          q2 = leaf;
+        else
+          q3 = leaf;
+      }
+      node = (hit && leaf == 0u) ? node + 1u : skip;
+    }
+    const bool any_walking = __any(node < END);
+    if (__any(q3 != 0u) || !any_walking) {
+      if (q0 != 0u) leaf_test<LDS, false>(im, sc, off, q0 >> 3, q0 & 7u, ray, best, nprim, last_id);
+      q0 = q1;
+      q1 = q2;
+      q2 = q3;
+      q3 = 0u;
+      if (best.prim >= 0) {  // occluded: this lane is finished (the wave keeps voting)
+        node = END;
+        q0 = q1 = q2 = 0u;
+      }
+      if (!__any(node < END) && !__any(q0 != 0u)) break;
+    }
+  }
+  return best.prim >= 0;
+}
+
+// ---- GRID: the 3D-DDA of closest_hit_grid (rtow_trace_grid.h) without its suspend / resume, seeded, early exit ----
+// The DDA's step direction is taken from the sign of the reciprocal it steps with (1 / -0.0 is negative), not from
+// `d >= 0` as the render's walk does: the two disagree for a -0.0 component, which made that walk step the wrong way
+// (rtow_query.h hands it +0.0 instead; here the walk is consistent by construction and takes the caller's direction).
+template <bool LDS>
+__device__ __forceinline__ bool any_hit_grid(const Image<LDS> &im, const DevScene &sc, V3 o, V3 d, real time,
+                                             double tmax, bool active, uint32_t &nnode, uint32_t &nprim,
+                                             uint32_t leaf_votes) {
+#ifdef RTOW_UNIT_RAYS
+  // the fast build walks the unit direction (rtow_trace_bvh.h, RTOW_UNIT_RAYS): its ray parameter is a distance, and so
+  // is the bound it starts from
+  const double a_ref = dot(d, d);
+  const double inv_len = fast_rsqrt(a_ref), len = a_ref * inv_len;
+  d = d * inv_len;
+  const RayForms ray = make_unit_ray_forms(o, d, time, len);
+  const float tmin32w = 0.0009f * (float)len;
+  Closest best = seeded(tmax * len);
+#else
+  const RayForms ray = make_ray_forms(o, d, time);
+  const float tmin32w = 0.0009f;
+  Closest best = seeded(tmax);
+#endif
+  ImgOffsets off = {sc.g_off_ids, sc.g_off_sph, sc.g_off_mov, sc.g_off_tri, 0u, 0u, sc.g_off_sph32, sc.g_off_mov32};
+  int last_id = -1;
+  const RTOW_CONST float *hf = (const RTOW_CONST float *)sc.gblob;
+  const RTOW_CONST int32_t *hi = (const RTOW_CONST int32_t *)sc.gblob;
+  const float gx = hf[0], gy = hf[1], gz = hf[2];
+  const float cx = hf[3], cy = hf[4], cz = hf[5];
+  const float icx = hf[6], icy = hf[7], icz = hf[8];
+  const int nx = hi[9], ny = hi[10], nz = hi[11];
+  const uint32_t n_large = (uint32_t)hi[12], off_large = (uint32_t)hi[13];
+  off.fat = (uint32_t)hi[14];
+  off.fat_stride = (uint32_t)hi[15];
+
+  // the large primitives (the ground sphere), for every ray, as closest_hit_grid tests them (static spheres four, then
+  // two at a time); a hit among them ends the lane before the DDA
+  if (active && n_large != 0u) {
+    const uint32_t lf = (off_large - off.ids) >> 2;
+    uint32_t k = 0;
+    for (; k + 3 < n_large; k += 4) {
+      int id[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) id[j] = (int)im.u32(off.ids + 4u * (lf + k + j));
+      if (id[0] < sc.n_sph && id[1] < sc.n_sph && id[2] < sc.n_sph && id[3] < sc.n_sph) {
+        double dd[4], hh[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t r = off.sph + 32u * (uint32_t)id[j];
+          const double2 p0 = im.d2(r), p1 = im.d2(r + 16u);
+          dd[j] = sphere_disc<double>(ray.o64, ray.d64, ray.a64, p0.x, p0.y, p1.x, p1.y, hh[j]);
+        }
+        nprim += 4u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sphere_resolve<double>(dd[j], hh[j], ray.a64, ray.inv_a64, id[j], ray.tmin, best);
+        last_id = id[3];
+      } else {
+        leaf_test<LDS, false>(im, sc, off, lf + k, 4u, ray, best, nprim, last_id);
+      }
+    }
+    for (; k + 1 < n_large; k += 2) {
+      const int ia = (int)im.u32(off.ids + 4u * (lf + k)), ib = (int)im.u32(off.ids + 4u * (lf + k + 1));
+      if (ia < sc.n_sph && ib < sc.n_sph) {
+        const uint32_t ra = off.sph + 32u * (uint32_t)ia, rb = off.sph + 32u * (uint32_t)ib;
+        const double2 a0 = im.d2(ra), a1 = im.d2(ra + 16u), b0 = im.d2(rb), b1 = im.d2(rb + 16u);
+        double ha, hb;
+        const double da = sphere_disc<double>(ray.o64, ray.d64, ray.a64, a0.x, a0.y, a1.x, a1.y, ha);
+        const double db = sphere_disc<double>(ray.o64, ray.d64, ray.a64, b0.x, b0.y, b1.x, b1.y, hb);
+        nprim += 2u;
+        sphere_resolve<double>(da, ha, ray.a64, ray.inv_a64, ia, ray.tmin, best);
+        sphere_resolve<double>(db, hb, ray.a64, ray.inv_a64, ib, ray.tmin, best);
+        last_id = ib;
+      } else {
+        leaf_test<LDS, false>(im, sc, off, lf + k, 2u, ray, best, nprim, last_id);
+      }
+    }
+    if (k < n_large) leaf_test<LDS, false>(im, sc, off, lf + k, n_large - k, ray, best, nprim, last_id);
+  }
+  const float tmax32 = round_up_f32(best.t);
+  stage_prio<kPrioSetup>();
+
+  const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;
+  const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
+  const float ix = safe_inv(dx), iy = safe_inv(dy), iz = safe_inv(dz);
+  const float oix = ox * ix, oiy = oy * iy, oiz = oz * iz;
+  const float hx = fmaf((float)nx, cx, gx), hy = fmaf((float)ny, cy, gy), hz = fmaf((float)nz, cz, gz);
+  const float ax = fmaf(gx, ix, -oix), bx = fmaf(hx, ix, -oix);
+  const float ay = fmaf(gy, iy, -oiy), by = fmaf(hy, iy, -oiy);
+  const float az = fmaf(gz, iz, -oiz), bz = fmaf(hz, iz, -oiz);
+  const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tmin32w));
+  const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tmax32));
+  bool walking = active && best.prim < 0 && t0 <= t1 * 1.00002f;
+
+  const float px = fmaf(t0, dx, ox), py = fmaf(t0, dy, oy), pz = fmaf(t0, dz, oz);
+  int c0 = (int)floorf((px - gx) * icx), c1 = (int)floorf((py - gy) * icy), c2 = (int)floorf((pz - gz) * icz);
+  c0 = min(max(c0, 0), nx - 1);
+  c1 = min(max(c1, 0), ny - 1);
+  c2 = min(max(c2, 0), nz - 1);
+  const bool fx = !(ix < 0.0f), fy = !(iy < 0.0f), fz = !(iz < 0.0f);  // (see above: the sign of the reciprocal)
+  float tmx = fmaf(fmaf((float)(c0 + (fx ? 1 : 0)), cx, gx), ix, -oix);
+  float tmy = fmaf(fmaf((float)(c1 + (fy ? 1 : 0)), cy, gy), iy, -oiy);
+  float tmz = fmaf(fmaf((float)(c2 + (fz ? 1 : 0)), cz, gz), iz, -oiz);
+  const float tdx = fabsf(cx * ix), tdy = fabsf(cy * iy), tdz = fabsf(cz * iz);
+  int remx = fx ? nx - 1 - c0 : c0, remy = fy ? ny - 1 - c1 : c1, remz = fz ? nz - 1 - c2 : c2;
+  const int incx = fx ? 1 : -1, incy = fy ? nx : -nx, incz = fz ? nx * ny : -(nx * ny);
+  int idx = (c2 * ny + c1) * nx + c0;
+
+  stage_prio<kPrioStage>();
+  uint32_t q0 = 0u, q1 = 0u;
+  for (;;) {
+    if (walking && q1 == 0u) {  // (a lane with two cells queued waits for the next leaf phase)
+      const uint32_t cw = im.u32(sc.g_off_cells + 4u * (uint32_t)idx);
+      ++nnode;
+      if (cw != 0u) {
+        if (q0 == 0u)
+          q0 = cw;
+        else
+          q1 = cw;
+      }
+      const float tnext = fminf(fminf(tmx, tmy), tmz);
+      const bool sx = tmx == tnext;
+      const bool sy = !sx && tmy == tnext;
+      const int rem = sx ? remx : (sy ? remy : remz);
+      walking = rem > 0 && !(tnext > tmax32);
+      idx += sx ? incx : (sy ? incy : incz);
+      tmx += sx ? tdx : 0.0f;
+      tmy += sy ? tdy : 0.0f;
+      tmz += (!sx && !sy) ? tdz : 0.0f;
+      remx -= sx ? 1 : 0;
+      remy -= sy ? 1 : 0;
+      remz -= (!sx && !sy) ? 1 : 0;
+    }
+    const bool any_walking = __any(walking);
+    const unsigned long long m_pending = __ballot(q0 != 0u);
+    if ((m_pending != 0ull && ((uint32_t)__popcll(m_pending) >= leaf_votes || __ballot(walking && q1 == 0u) == 0ull)) ||
+        !any_walking) {
+      stage_prio<kPrioLeaf>();
+      if (q0 != 0u) leaf_test<LDS, true>(im, sc, off, q0 >> 8, q0 & 255u, ray, best, nprim, last_id);
+      q0 = q1;
+      q1 = 0u;
+      if (best.prim >= 0) {  // occluded: the lane's DDA stops here
+        walking = false;
+        q0 = 0u;
+      }
+      stage_prio<kPrioStage>();
+      if (!__any(walking) && !__any(q0 != 0u)) break;
+    }
+  }
+  return best.prim >= 0;
+}
+
+// ---- BVH4: the trip loop of closest_hit_bvh4 (rtow_trace_bvh4.h) without its suspend / resume, seeded, early exit ----
+template <bool FULL>
+__device__ __forceinline__ bool any_hit_bvh4(const Bvh4Reader<FULL> &im, const DevScene &sc, const TraceParams &P, V3 o,
+                                             V3 d, double tmax, bool active, uint32_t lane_g, uint32_t &nnode,
+                                             uint32_t &nprim) {
+  Closest best = seeded(tmax);
+  const V3d o64 = to_f64(o), d64 = to_f64(d);
+  const Bvh4Ray ray = bvh4_ray<FULL>(sc, o, d);
+  const Bvh4Stack st = bvh4_stack(sc);
+  const float tmax32 = round_up_f32(best.t);  // the bound: fixed, the walk ends at the first hit
+  uint32_t sa = st.lds;
+  uint32_t cur = active ? 0u : kRefNone;  // node 0 = root
+  uint32_t q0 = kRefNone, q1 = kRefNone;  // queued leaves, oldest first
+  if constexpr (FULL) stage_prio<kPrioLeaf>();
+  for (;;) {
+    bvh4_step<FULL>(im, P, ray, tmax32, st, lane_g, cur, sa, q0, q1, nnode);
+    const bool any_walking = __any(cur != kRefNone);
+    const unsigned long long m_pending = __ballot(q0 != kRefNone);
+    if ((m_pending != 0ull && ((uint32_t)__popcll(m_pending) >= P.leaf_votes || __ballot(bvh4_busy(cur, q1)) == 0ull)) ||
+        !any_walking) {
+      if (q0 != kRefNone) bvh4_leaf<FULL>(im, sc, q0, o64, d64, best, nprim);
+      q0 = q1;
+      q1 = kRefNone;
+      if (best.prim >= 0) {  // occluded: drop the node in hand, the queued leaf and the stack
+        cur = kRefNone;
+        q0 = kRefNone;
+        sa = st.lds;
+      }
+      if (!__any(cur != kRefNone) && !__any(q0 != kRefNone)) break;
+    }
+  }
+  if constexpr (FULL) stage_prio<kPrioStage>();
+  return best.prim >= 0;
+}
+
+// ---- STREAM: closest_hit_stream (rtow_trace_hit.h), seeded; the wave leaves when every active lane has a hit ----
+// `open`: the lane has a ray and no hit yet.  The votes are wave-level (one per block of four spheres, per pair of
+// scalar-loaded triangles, per tile): the tiled triangle loop stages its tiles with all 64 lanes, so a lane that is
+// done stays in the loop until the whole wave is.
+__device__ __forceinline__ bool any_hit_stream(const DevScene &sc, V3d o, V3d d, double time, double tmax, bool active,
+                                               uint32_t &nprim) {
+  Closest best = seeded(tmax);
+  const double tmin = RTOW_TMIN;
+  const double a = dot(d, d);
+  const double inv_a = fast_rcp(a);  // used by the fast build only
+  bool open = active;
+  {
+    cdptr g = (cdptr)sc.sph;
+    const int n = sc.n_sph;
+    for (int i = 0; i < n; i += 4) {
+      if (!__any(open)) break;
+      const int e = i + 4 < n ? i + 4 : n;
+      if (open) {
+        for (int k = i; k < e; ++k)
+          sphere_test<double>(o, d, a, inv_a, g[4 * k + 0], g[4 * k + 1], g[4 * k + 2], g[4 * k + 3], k, tmin, best);
+        nprim += (uint32_t)(e - i);
+      }
+      open = open && best.prim < 0;
+    }
+  }
+  {
+    cdptr g = (cdptr)sc.mov;
+    const int n = sc.n_mov;
+    const int base = sc.n_sph;
+    for (int i = 0; i < n; i += 2) {
+      if (!__any(open)) break;
+      const int e = i + 2 < n ? i + 2 : n;
+      if (open) {
+        for (int k = i; k < e; ++k) {
+          const double cx = g[8 * k + 0] + time * g[8 * k + 3];
+          const double cy = g[8 * k + 1] + time * g[8 * k + 4];
+          const double cz = g[8 * k + 2] + time * g[8 * k + 5];
+          sphere_test<double>(o, d, a, inv_a, cx, cy, cz, g[8 * k + 6], base + k, tmin, best);
+        }
+        nprim += (uint32_t)(e - i);
+      }
+      open = open && best.prim < 0;
+    }
+  }
+  if (sc.stream_tile_lds != 0u) {
+    // the tiled loop of closest_hit_stream: the same staging (two 3 KB tiles per wave, coalesced fetch, broadcast reads)
+    const int n = sc.n_tri;
+    const int base = sc.n_sph + sc.n_mov;
+    if (__any(open)) {
+      const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+      const uint32_t slice = (threadIdx.x >> 6) * (2u * kStreamTileBytes);
+      const unsigned char *src = (const unsigned char *)sc.tri;
+      const uint32_t total = (uint32_t)n * 96u;
+      const uint32_t ntiles = ((uint32_t)n + kStreamTile - 1u) / kStreamTile;
+      vu4 r0, r1, r2;
+      auto fetch = [&](uint32_t tile) {
+        const uint32_t p = tile * kStreamTileBytes + 16u * lane;
+        const vu4 z = {0u, 0u, 0u, 0u};
+        r0 = p < total ? glb_read<vu4>(src, p) : z;
+        r1 = p + 1024u < total ? glb_read<vu4>(src, p + 1024u) : z;
+        r2 = p + 2048u < total ? glb_read<vu4>(src, p + 2048u) : z;
+      };
+      auto park = [&](uint32_t buf) {
+        const uint32_t q = slice + buf * kStreamTileBytes + 16u * lane;
+        lds_write<vu4>(q, r0);
+        lds_write<vu4>(q + 1024u, r1);
+        lds_write<vu4>(q + 2048u, r2);
+      };
+      fetch(0u);
+      park(0u);
+      for (uint32_t tile = 0; tile < ntiles; ++tile) {
+        if (tile + 1u < ntiles) fetch(tile + 1u);
+        const uint32_t tb = slice + (tile & 1u) * kStreamTileBytes;
+        const int first = (int)(tile * kStreamTile);
+        const int cnt = n - first < (int)kStreamTile ? n - first : (int)kStreamTile;
+        if (open) {
+          for (int k = 0; k < cnt; ++k) {
+            const uint32_t r = tb + 96u * (uint32_t)k;
+            const vd2 p0 = lds_read<vd2>(r), p1 = lds_read<vd2>(r + 16u), p2 = lds_read<vd2>(r + 32u),
+                      p3 = lds_read<vd2>(r + 48u), p4 = lds_read<vd2>(r + 64u), p5 = lds_read<vd2>(r + 80u);
+            triangle_test<double>(o, d, V3d{p0.x, p0.y, p1.x}, V3d{p1.y, p2.x, p2.y}, V3d{p3.x, p3.y, p4.x},
+                                  V3d{p4.y, p5.x, p5.y}, base + first + k, tmin, best);
+          }
+          nprim += (uint32_t)cnt;
+        }
+        open = open && best.prim < 0;
+        if (!__any(open)) break;  // (wave-uniform: the tile fetched for the next round is not parked)
+        if (tile + 1u < ntiles) park((tile + 1u) & 1u);
+      }
+    }
+  } else {
+    cdptr g = (cdptr)sc.tri16;
+    const int n = sc.n_tri;
+    const int base = sc.n_sph + sc.n_mov;
+    for (int i = 0; i < n; i += 2) {
+      if (!__any(open)) break;
+      const int e = i + 2 < n ? i + 2 : n;
+      if (open) {
+        for (int k = i; k < e; ++k)
+          triangle_test<double>(o, d, V3d{g[16 * k + 0], g[16 * k + 1], g[16 * k + 2]},
+                                V3d{g[16 * k + 3], g[16 * k + 4], g[16 * k + 5]},
+                                V3d{g[16 * k + 6], g[16 * k + 7], g[16 * k + 8]},
+                                V3d{g[16 * k + 9], g[16 * k + 10], g[16 * k + 11]}, base + k, tmin, best);
+        nprim += (uint32_t)(e - i);
+      }
+      open = open && best.prim < 0;
+    }
+  }
+  return best.prim >= 0;
+}
+
+__device__ __forceinline__ unsigned o_lane_id() {
+  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+}
+
+// KERNEL: 1 = STREAM, 2 = BVH, 3 = GRID, 4 = BVH4, 5 = REFTREE (strict build only); LDS: as in rtow_query.h
+template <int KERNEL, bool LDS>
+__global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
+    RTOW_OCAT(rtow_occlude_, RTOW_SUFFIX)(const OccludeParams Q) {
+  const TraceParams &P = Q.P;
+  const DevScene &sc = P.sc;
+  const unsigned lane = o_lane_id();
+  [[maybe_unused]] const uint32_t lane_g = blockIdx.x * blockDim.x + threadIdx.x;
+
+  // ---- scene image in LDS: what the trace kernel stages for the same strategy (rtow_trace_body.h) ----
+  Image<LDS> im;
+  im.g = KERNEL == 3 ? sc.gblob : sc.blob;
+  [[maybe_unused]] Bvh4Reader<LDS> im4;
+  if constexpr (KERNEL == 4) {
+    im4.g = sc.blob4;
+    im4.lds_limit = sc.b4_lds_limit;
+    im4.aux_src = sc.b4_aux_src;
+    im4.aux_lds = sc.b4_aux_lds;
+    const uint4 *src = reinterpret_cast<const uint4 *>(sc.blob4);
+    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
+    const uint32_t n16 = sc.b4_lds_limit / 16u;
+    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    if (sc.b4_aux_src < sc.blob4_bytes) {
+      const uint4 *asrc = reinterpret_cast<const uint4 *>(sc.blob4 + sc.b4_aux_src);
+      uint4 *adst = reinterpret_cast<uint4 *>(rtow_lds + sc.b4_aux_lds);
+      const uint32_t a16 = (sc.blob4_bytes - sc.b4_aux_src) / 16u;
+      for (uint32_t i = threadIdx.x; i < a16; i += blockDim.x) adst[i] = asrc[i];
+    }
+    __syncthreads();
+  } else if constexpr ((KERNEL == 2 || KERNEL == 3) && LDS) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(im.g);
+    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
+    const uint32_t n16 = (KERNEL == 3 ? sc.gblob_bytes : sc.blob_bytes) / 16u;
+    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    __syncthreads();
+  }
+
+  uint32_t nnode = 0u, nprim = 0u;
+  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  // wave-uniform loop: every lane of the wave runs every step (the walks vote across the wave)
+  for (uint32_t base = wave * 64u; base < Q.n; base += n_waves * 64u) {
+    const uint32_t i = base + lane;
+    const bool in = i < Q.n;
+    V3 ro = {0, 0, 0}, rd = {0, 0, 1};
+    real rtime = 0;
+    double tmax = 0.0;
+    if (in) {
+      const vd2 *r = reinterpret_cast<const vd2 *>(Q.rays + (size_t)i * kORayBytes);
+      const vd2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];  // {ox, oy} {oz, time} {dx, dy} {dz, tmax}
+      ro = {r0.x, r0.y, r1.x};
+      rtime = r1.y;
+      rd = {r2.x, r2.y, r3.x};
+      tmax = r3.y;
+    }
+    // a ray whose interval [0.001, tmax] is empty (tmax NaN included) hits nothing: it skips the walk
+    const bool active = in && tmax >= RTOW_TMIN;
+
+    bool hit = false;
+    if constexpr (KERNEL == 4) {
+      hit = any_hit_bvh4<LDS>(im4, sc, P, ro, rd, tmax, active, lane_g, nnode, nprim);
+    } else if constexpr (KERNEL == 3) {
+      hit = any_hit_grid<LDS>(im, sc, ro, rd, rtime, tmax, active, nnode, nprim, P.leaf_votes);
+    } else if constexpr (KERNEL == 2) {
+      hit = any_hit_bvh<LDS>(im, sc, ro, rd, rtime, tmax, active, nnode, nprim);
+    } else if constexpr (KERNEL == 5) {
+#ifndef RTOW_FAST_MATH
+      // the reference's tree is an exactness mode: its closest hit, compared with tmax
+      if (active) {
+        const Closest best = closest_hit_reftree(sc, to_f64(ro), to_f64(rd), (double)rtime, nnode, nprim);
+        hit = best.prim >= 0 && best.t <= tmax;
+      }
+#endif
+    } else {
+      hit = any_hit_stream(sc, to_f64(ro), to_f64(rd), (double)rtime, tmax, active, nprim);
+    }
+    if (in) Q.occluded[i] = hit ? 1u : 0u;
+  }
+
+  // statistics: one atomic per wave and counter
+  unsigned long long c0 = nprim, c1 = nnode;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    c0 += __shfl_down(c0, off);
+    c1 += __shfl_down(c1, off);
+  }
+  if (lane == 0) {
+    atomicAdd(&Q.counters[0], c0);
+    atomicAdd(&Q.counters[1], c1);
+  }
+}
+
+}  // namespace
+
+template <class Kern>
+static int o_no_static_lds(Kern k) {  // the walks address the dynamic LDS block from 0 (rtow_trace_math.h lds_read)
+  hipFuncAttributes fa;
+  const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k));
+  if (e != hipSuccess) return (int)e;
+  return fa.sharedSizeBytes == 0 ? 0 : (int)hipErrorInvalidValue;
+}
+
+template <int K, bool L>
+static const void *occlude_fn() {
+  return reinterpret_cast<const void *>(RTOW_OCAT(rtow_occlude_, RTOW_SUFFIX)<K, L>);
+}
+
+template <int K, bool L>
+static int launch_o(const OccludeParams &q, int grid, int block, unsigned lds_bytes, hipStream_t st) {
+  auto k = RTOW_OCAT(rtow_occlude_, RTOW_SUFFIX)<K, L>;
+  static const int lds_ok = o_no_static_lds(k);
+  if (lds_ok != 0) return lds_ok;
+  if (lds_bytes > 48 * 1024) {
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds_bytes, st, q);
+  return (int)hipGetLastError();
+}
+
+// kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE (strict build); `lds_bytes` selects the variant as in rtow_query.h
+int RTOW_OCAT(launch_occlude_, RTOW_SUFFIX)(const TraceParams &p, const void *rays, void *occluded, uint32_t n,
+                                            unsigned long long *counters, int kernel, int grid, int block,
+                                            unsigned lds_bytes, void *stream) {
+  OccludeParams q;
+  q.P = p;
+  q.rays = (const unsigned char *)rays;
+  q.occluded = (unsigned char *)occluded;
+  q.n = n;
+  q.counters = counters;
+  hipStream_t st = (hipStream_t)stream;
+  const bool lds = lds_bytes > 0;
+  switch (kernel) {
+    case 1: return launch_o<1, false>(q, grid, block, lds_bytes, st);  // (LDS: the tiled triangle loop's per-wave tiles)
+    case 2: return lds ? launch_o<2, true>(q, grid, block, lds_bytes, st) : launch_o<2, false>(q, grid, block, 0, st);
+    case 3: return lds ? launch_o<3, true>(q, grid, block, lds_bytes, st) : launch_o<3, false>(q, grid, block, 0, st);
+    case 4:
+      return p.sc.b4_half == 0u ? launch_o<4, true>(q, grid, block, lds_bytes, st)
+                                : launch_o<4, false>(q, grid, block, lds_bytes, st);
+#ifndef RTOW_FAST_MATH
+    case 5: return launch_o<5, false>(q, grid, block, 0, st);
+#endif
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
+// Workgroups per CU that stay resident: the rule of query_occupancy_* (rtow_query.h).
+int RTOW_OCAT(occlude_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+  const bool lds = lds_bytes > 0;
+  const void *fn;
+  switch (kernel) {
+    case 1: fn = occlude_fn<1, false>(); break;
+    case 2: fn = lds ? occlude_fn<2, true>() : occlude_fn<2, false>(); break;
+    case 3: fn = lds ? occlude_fn<3, true>() : occlude_fn<3, false>(); break;
+    case 4: fn = occlude_fn<4, true>(); break;  // (both variants have the same launch bounds)
+#ifndef RTOW_FAST_MATH
+    case 5: fn = occlude_fn<5, false>(); break;
+#endif
+    default: return -1;
+  }
+  if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
+  if (fa.sharedSizeBytes != 0) return -1;
+  const int regs = fa.numRegs > 0 ? fa.numRegs : 128;
+  if (vgprs) *vgprs = regs;
+  const int alloc = ((regs + 7) / 8) * 8;
+  int waves_per_simd = 512 / alloc;
+  if (waves_per_simd > 8) waves_per_simd = 8;
+  if (waves_per_simd < 1) waves_per_simd = 1;
+  int nb = (waves_per_simd * 4) / (block / 64);
+  if (lds_bytes > 0) {
+    const int by_lds = (int)((160u * 1024u) / lds_bytes);
+    if (by_lds < nb) nb = by_lds;
+  }
+  return nb < 1 ? 1 : nb;
+}
+
+}  // namespace rtow

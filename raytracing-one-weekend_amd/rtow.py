@@ -19,7 +19,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_ROOT = PKG_DIR.parent
 LIB_PATH = Path(os.environ.get("RTOW_LIB", PKG_DIR / "librtow.so"))  # RTOW_LIB: A/B against another build
 
-RTOW_ABI_VERSION = 8
+RTOW_ABI_VERSION = 9
 RTOW_OK, RTOW_EINVAL, RTOW_ENODEV, RTOW_EHIP, RTOW_ENOSCENE, RTOW_EEMPTY, RTOW_ENOMEM = 0, -1, -2, -3, -4, -5, -6
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2
 PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_TRIANGLE = 0, 1, 2
@@ -141,7 +141,7 @@ EXPORTS = [
     "rtow_multi_create", "rtow_multi_set_builder", "rtow_multi_upload", "rtow_multi_build_info",
     "rtow_multi_render", "rtow_multi_destroy", "rtow_host_reftree_info",
     "rtow_render_device_rgb8", "rtow_multi_render_rgb8", "rtow_multi_frame_breakdown",
-    "rtow_intersect_device", "rtow_intersect",
+    "rtow_intersect_device", "rtow_intersect", "rtow_occluded_device", "rtow_occluded",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -223,6 +223,11 @@ def lib():
                                             C.c_void_p, C.POINTER(Stats)]
         L.rtow_intersect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                      C.POINTER(Stats)]
+    if hasattr(L, "rtow_occluded"):
+        L.rtow_occluded_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.POINTER(Stats)]
+        L.rtow_occluded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.POINTER(Stats)]
     L.rtow_profile_collect.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     if hasattr(L, "rtow_debug_schedule"):  # (absent from older builds loaded through RTOW_LIB for A/B runs)
         L.rtow_debug_schedule.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(C.c_uint32), C.c_int32]
@@ -433,6 +438,28 @@ class Context:
         check(lib().rtow_intersect_device(self._h, precision, kernel, C.c_void_p(d_rays), n, C.c_void_p(d_hits),
                                           C.c_void_p(stream), C.byref(st) if st is not None else None),
               "rtow_intersect_device")
+        return st
+
+    def occluded(self, rays, precision=F64_FAST, kernel=KERNEL_AUTO, want_stats=False):
+        """Any-hit test of every ray (a RAY_DTYPE array, host memory) over [0.001, tmax]: a numpy bool array, and Stats
+        with `want_stats` (rtow_occluded)."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        out = np.empty(len(r), dtype=np.uint8)
+        st = Stats() if want_stats else None
+        check(lib().rtow_occluded(self._h, precision, kernel, r.ctypes.data_as(C.c_void_p), len(r),
+                                  out.ctypes.data_as(C.c_void_p), C.byref(st) if st is not None else None),
+              "rtow_occluded")
+        occ = out.view(np.bool_)
+        return (occ, st) if want_stats else occ
+
+    def occluded_device(self, d_rays: int, n: int, d_occluded: int, precision=F64_FAST, kernel=KERNEL_AUTO,
+                        stream: int = 0, want_stats=False):
+        """The same on device buffers (raw pointers: n x 64-byte rays, n bytes of results — a torch.bool tensor),
+        enqueued on `stream` (rtow_occluded_device); returns Stats with `want_stats` (then synchronised), else None."""
+        st = Stats() if want_stats else None
+        check(lib().rtow_occluded_device(self._h, precision, kernel, C.c_void_p(d_rays), n, C.c_void_p(d_occluded),
+                                         C.c_void_p(stream), C.byref(st) if st is not None else None),
+              "rtow_occluded_device")
         return st
 
     def profile_collect(self):
