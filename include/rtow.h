@@ -397,6 +397,34 @@ int rtow_occluded_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const
 int rtow_occluded(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
                   uint8_t *occluded, rtow_stats_t *stats);
 
+/* ---- in-place refit of the resident scene (moving geometry) ---------------------------------------------------------
+ * Replace the geometry, materials and camera of the scene resident in ctx, keeping its trees' topology: the node
+ * structure, leaf membership and leaf order of the binary and 4-wide BVHs stay as built; records, boxes and planes are
+ * recomputed on the GPU (csrc/rtow_refit.hip) by the host builder's rules, the grid is rebuilt (present afterwards
+ * exactly when a fresh upload of `scene` would build it).  Only the images the resident scene holds are refreshed (after
+ * the lean upload of rtow_render*, those its kernel reads).  An unchanged refit right after a host-builder upload leaves
+ * every image byte-identical.
+ *   may change   every sphere, moving sphere and triangle; material indices and records; the camera (t0 / t1 included)
+ *   must keep    n_spheres, n_moving, n_triangles, n_materials, n_prims, and prim_kind / prim_index (identical, or
+ *                absent in both); anything else is RTOW_EINVAL with the resident scene untouched
+ * Ordering: as rtow_scene_upload (waits for earlier device work, queues on the null stream, later renders and queries on
+ * any stream see the new scene).  Hit `prim` ids keep naming primitives in insertion order.  Culling quality degrades
+ * as the geometry moves away from the uploaded shape (rtow_refit_info_t::bvh_area_ratio); re-upload when it has.
+ * Errors: RTOW_EINVAL (NULL ctx or scene, an invalid scene, a shape mismatch), RTOW_ENOSCENE without a resident scene. */
+int rtow_scene_refit(rtow_ctx *ctx, const rtow_scene_t *scene);
+
+typedef struct rtow_refit_info_t {
+  int32_t refits;          /* refits since the last rtow_scene_upload / rtow_render upload */
+  int32_t grid_resident;   /* the grid image exists after the last refit (it is rebuilt) */
+  double refit_ms;         /* host wall time of the last rtow_scene_refit call */
+  double device_ms;        /* device time of the last refit's kernels and copies (HIP events) */
+  double bvh_area_ratio;   /* sum of the binary BVH's inner-node half-areas / root half-area for the current geometry, over
+                              the same sum for the geometry of the upload.  1.0 = as built, and before any refit; grows
+                              as the tree degrades.  0 when no binary BVH is resident. */
+} rtow_refit_info_t;
+/* Facts about the refits since the last upload; synchronises.  RTOW_ENOSCENE without a scene. */
+int rtow_refit_info(rtow_ctx *ctx, rtow_refit_info_t *out);
+
 /* Convenience: upload + render + copy this rank's rows to host memory.
  * Lean upload: rtow_render / rtow_render_rgb8 know their config and build only the structures ITS kernel reads
  * (the cover scene through the grid kernel needs no BVH, no 4-wide image, no binary32 images).  The scene they

@@ -182,19 +182,23 @@ struct Image32 {
   std::vector<unsigned char> blob;  // prefix left zeroed when `prefix` is NULL (filled on the device)
   uint32_t off_sph = 0, off_mov = 0, off_tri = 0, off_sph32 = 0, off_mov32 = 0, off_pmat = 0, off_mats = 0;
 };
-void make_image32(const unsigned char *prefix, uint32_t prefix_bytes, const std::vector<double> &sph,
-                  const std::vector<double> &mov, const std::vector<double> &tri, const std::vector<int32_t> &pmat,
-                  const std::vector<unsigned char> &mats_bytes, Image32 &out) {
+// the section offsets of that image; returns its size
+size_t layout_image32(uint32_t prefix_bytes, size_t ns, size_t nm, size_t nt, size_t n_pmat, size_t mats_bytes, Image32 &out) {
   auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-  const size_t ns = sph.size() / 4, nm = mov.size() / 8, nt = tri.size() / 12;
   out.off_sph = prefix_bytes;
   out.off_mov = (uint32_t)(out.off_sph + ns * 32);
   out.off_tri = (uint32_t)(out.off_mov + nm * 64);
   out.off_sph32 = (uint32_t)up16(out.off_tri + nt * 48);
   out.off_mov32 = (uint32_t)(out.off_sph32 + ns * 16);
   out.off_pmat = (uint32_t)up16(out.off_mov32 + nm * 32);
-  out.off_mats = (uint32_t)up16(out.off_pmat + pmat.size() * 4);
-  out.blob.assign(up16(out.off_mats + mats_bytes.size()), 0);
+  out.off_mats = (uint32_t)up16(out.off_pmat + n_pmat * 4);
+  return up16(out.off_mats + mats_bytes);
+}
+void make_image32(const unsigned char *prefix, uint32_t prefix_bytes, const std::vector<double> &sph,
+                  const std::vector<double> &mov, const std::vector<double> &tri, const std::vector<int32_t> &pmat,
+                  const std::vector<unsigned char> &mats_bytes, Image32 &out) {
+  const size_t ns = sph.size() / 4, nm = mov.size() / 8, nt = tri.size() / 12;
+  out.blob.assign(layout_image32(prefix_bytes, ns, nm, nt, pmat.size(), mats_bytes.size(), out), 0);
   unsigned char *b = out.blob.data();
   if (prefix) std::memcpy(b, prefix, prefix_bytes);
   if (ns) std::memcpy(b + out.off_sph, sph.data(), ns * 32);
@@ -257,6 +261,24 @@ int launch_occlude_fast(const TraceParams &p, const void *rays, void *occluded, 
                         int kernel, int grid, int block, unsigned lds_bytes, void *stream);
 int occlude_occupancy_strict(int kernel, int block, unsigned lds_bytes, int *vgprs);
 int occlude_occupancy_fast(int kernel, int block, unsigned lds_bytes, int *vgprs);
+// csrc/rtow_refit.hip (rtow_scene_refit): 0, or 1 when a launch failed
+int refit_records(const double *g_sph, const double *g_mov, const double *g_tri, int ns, int nm, int nt, double *sph,
+                  double *sph_r, double *mov, double *tri, double *tri16, void *stream);
+int refit_prim_boxes(const double *sph, const double *sph_r, const double *mov, const double *tri, int ns, int nm, int nt,
+                     double time0, double time1, double *pbox, void *stream);
+int refit_tri_section(int nt, const double *tri, const int32_t *pmat_tri, const int32_t *map, unsigned char *dst,
+                      uint32_t off_tri, uint32_t off_pmat, int f32, void *stream);
+int refit_spheres32(int ns, int nm, const double *sph, const double *mov, unsigned char *dst, uint32_t off_sph32,
+                    uint32_t off_mov32, void *stream);
+int refit_bvh2_links(const unsigned char *blob, int n_nodes, int32_t *parent, void *stream);
+int refit_bvh2(unsigned char *blob, int n_nodes, uint32_t off_ids, int n_ids, const int32_t *map, int cls_base,
+               const double *pbox, const int32_t *parent, uint32_t *flags, double *nbox, double *partials, int emit,
+               const double cam_origin[3], double *area_out, void *stream);
+int refit_bvh4_links(const unsigned char *blob4, int n4, uint32_t node_bytes, uint32_t child_off, int32_t *parent,
+                     int32_t *need, void *stream);
+int refit_bvh4(unsigned char *blob4, int n4, uint32_t node_bytes, uint32_t child_off, int half, int n_rec, const int32_t *map,
+               int cls_base, const double *pbox, const int32_t *parent, const int32_t *need, uint32_t *flags, double *nbox,
+               double *sbox, const double cam_origin[3], double *frame, void *stream);
 }  // namespace rtow
 
 // Experiment knobs (RTOW_* environment variables), read ONCE at rtow_ctx_create: nothing on the
@@ -425,6 +447,19 @@ struct rtow_ctx {
   bool q_map_ok[3] = {false, false, false};
   hipEvent_t q_ev[4] = {};
   unsigned long long *h_qcounters = nullptr;
+  // in-place refits (rtow_scene_refit, csrc/rtow_refit.hip).  What the first refit after an upload derives from the
+  // images as built (before anything is overwritten) is kept until the next upload: the record slot -> triangle maps of
+  // the leaf-ordered images, the parent links of both trees, the area sum of the binary BVH as uploaded.
+  struct Refit {
+    bool ready = false;                // the per-upload state below is derived
+    std::vector<int32_t> slot2tri[2];  // [0] BVH image when ds.leaf_direct, [1] the 4-wide image (class-order triangle index)
+    DevBuf map2, map4, par2, par4, need4, flags, nbox2, nbox4, sbox4, pbox, partials;
+    DevBuf area;                       // [0] area sum of the upload's geometry, [1] of the last refit's; [2..7] 4-wide frame
+    DevBuf g_sph, g_mov, g_tri;        // raw geometry, staged
+    int refits = 0;
+    double refit_ms = 0.0;
+    hipEvent_t ev[2] = {};
+  } rf;
 };
 
 // BVH4: stack entries per lane (4 B x 1024 lanes each) an image staged whole must leave room for (RTOW_BVH4_STACK_K)
@@ -488,8 +523,12 @@ void rtow_ctx_destroy(rtow_ctx *c) {
                     &c->blob32, &c->gblob32, &c->cam32_dev, &c->blob4,
                     &c->partials, &c->stack, &c->counters, &c->spill, &c->out, &c->out8, &c->rtree, &c->counters_init,
                     &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_occ, &c->q_map[0], &c->q_map[1],
-                    &c->q_map[2]})
+                    &c->q_map[2], &c->rf.map2, &c->rf.map4, &c->rf.par2, &c->rf.par4, &c->rf.need4, &c->rf.flags,
+                    &c->rf.nbox2, &c->rf.nbox4, &c->rf.sbox4, &c->rf.pbox, &c->rf.partials, &c->rf.area, &c->rf.g_sph,
+                    &c->rf.g_mov, &c->rf.g_tri})
     b->release();
+  for (hipEvent_t e : c->rf.ev)
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->q_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->h_qcounters) (void)hipHostFree(c->h_qcounters);
@@ -535,6 +574,94 @@ static int validate_scene(const rtow_scene_t *s) {
   return RTOW_OK;
 }
 
+static void camera_record(const rtow_camera_t &k, rtow::DevCamera &dc) {
+  for (int i = 0; i < 3; ++i) {
+    dc.origin[i] = k.origin[i];
+    dc.u[i] = k.u[i];
+    dc.v[i] = k.v[i];
+    dc.horizontal[i] = k.horizontal[i];
+    dc.vertical[i] = k.vertical[i];
+    dc.llc[i] = k.lower_left_corner[i];
+  }
+  dc.lens_radius = k.lens_radius;
+  dc.t0 = k.t0;
+  dc.t1 = k.t1;
+}
+
+// Material index per primitive (class-major) and the device material records (scene_upload, impl_scene_refit)
+static void scene_materials(const rtow_scene_t *s, std::vector<int32_t> &pmat, std::vector<rtow::DevMaterial> &mats) {
+  const int ns = s->n_spheres, nm = s->n_moving, nt = s->n_triangles;
+  pmat.resize((size_t)ns + nm + nt);
+  for (int i = 0; i < ns; ++i) pmat[i] = s->sphere_mat[i];
+  for (int i = 0; i < nm; ++i) pmat[(size_t)ns + i] = s->moving_mat[i];
+  for (int i = 0; i < nt; ++i) pmat[(size_t)ns + nm + i] = s->triangle_mat[i];
+  mats.resize(s->n_materials);
+  for (int i = 0; i < s->n_materials; ++i) {
+    const rtow_material_t &m = s->materials[i];
+    rtow::DevMaterial &d = mats[i];
+    std::memset(&d, 0, sizeof d);
+    const bool diel = m.kind == RTOW_MAT_DIELECTRIC;  // attenuation {1,1,1}, common-model.cpp:61
+    for (int k = 0; k < 3; ++k) d.att[k] = diel ? 1.0 : m.albedo[k];
+    d.fuzz = m.kind == RTOW_MAT_LAMBERTIAN ? 0.0 : m.fuzz;
+    d.ir = m.ir;
+    d.kind = m.kind;
+  }
+}
+
+// The uniform grid built in HBM (csrc/rtow_build_grid.hip) from the record arrays resident in c->sph / mov / tri; the host
+// does the scalar steps between the phases with the code the host builder uses, so the image is byte-identical.  gimg.ok
+// stays false when the scene does not suit the grid.  sph (host records) decides the fat-list format; mov, tri and pmat
+// are read for their sizes only.  (scene_upload, impl_scene_refit)
+static int grid_device_build(rtow_ctx *c, const rtow_camera_t &cam, int ns, int nm, int nt, const std::vector<double> &sph,
+                             const std::vector<double> &mov, const std::vector<double> &tri, const std::vector<int32_t> &pmat,
+                             const std::vector<unsigned char> &mats_bytes, rtow::GridImage &gimg) {
+  const double cpp = c->knobs.grid_cpp;
+  const double large_ratio = c->knobs.grid_large;
+  int rc;
+  rtow::GridBuildBounds gb;
+  int grc = rtow::grid_build_phase1((const double *)c->sph.p, (const double *)c->sph_r.p, (const double *)c->mov.p,
+                                    (const double *)c->tri.p, ns, nm, nt, cam.t0, cam.t1, large_ratio,
+                                    nullptr, &c->grid_scratch, &gb);
+  if (grc) return fail(RTOW_EHIP, "device grid build failed (phase 1, stage %d): %s", grc, hipGetErrorString(hipGetLastError()));
+  if (gb.n_small > 0 && gb.n_large <= 64) {
+    rtow::GridHeader hd;
+    rtow::grid_header(gb.gmn, gb.gmx, gb.scale_prims, cam.origin, (size_t)gb.n_small, cpp, hd);
+    unsigned long long total_ids = 0, max_list = 0;
+    grc = rtow::grid_build_phase2(c->grid_scratch, hd.gminf, hd.cellf, hd.n, hd.pad, nullptr, &total_ids, &max_list);
+    if (grc) return fail(RTOW_EHIP, "device grid build failed (phase 2, stage %d): %s", grc, hipGetErrorString(hipGetLastError()));
+    if (max_list <= 255 && total_ids + (unsigned long long)gb.n_large < (1u << 24)) {
+      const size_t ncell = (size_t)hd.n[0] * hd.n[1] * hd.n[2];
+      for (int k = 0; k < 3; ++k) gimg.n[k] = hd.n[k];
+      double scale_small = 0.0;  // (the host builder's rule: rtow_grid.h build_grid_image)
+      for (int k = 0; k < 3; ++k)
+        scale_small = std::max({scale_small, std::fabs(gb.gmn[k]), std::fabs(gb.gmx[k]), std::fabs(cam.origin[k])});
+      const uint32_t fat = rtow::grid_wants_fat_lists(nm, nt, ncell, (size_t)total_ids + (size_t)gb.n_large,
+                                                      (size_t)gb.n_large, sph, mov, tri, pmat, mats_bytes, (size_t)total_ids,
+                                                      scale_small);
+      rtow::layout_grid_image(ncell, (size_t)total_ids + (size_t)gb.n_large, (size_t)gb.n_large, sph, mov, tri, pmat,
+                              mats_bytes, gimg, true, fat ? (size_t)total_ids : 0, fat ? fat : 48u);
+      if ((rc = c->gblob.ensure(gimg.total_bytes))) return rc;
+      unsigned char *gp = (unsigned char *)c->gblob.p;
+      unsigned char header[64];
+      const uint32_t off_large = (uint32_t)(gimg.off_ids + total_ids * 4);
+      rtow::write_grid_header(header, hd, gimg.n_large, off_large, gimg.off_fat, gimg.fat_stride);
+      HIPCHK(hipMemsetAsync(gp, 0, gimg.total_bytes, nullptr));
+      if ((rc = h2d_block(gp, header, 64))) return rc;  // (`header` is on the stack: never the source of an async copy)
+      if (ns) HIPCHK(hipMemcpyAsync(gp + gimg.off_sph, c->sph.p, sph.size() * 8, hipMemcpyDeviceToDevice, nullptr));
+      if (nm) HIPCHK(hipMemcpyAsync(gp + gimg.off_mov, c->mov.p, mov.size() * 8, hipMemcpyDeviceToDevice, nullptr));
+      if (nt) HIPCHK(hipMemcpyAsync(gp + gimg.off_tri, c->tri.p, tri.size() * 8, hipMemcpyDeviceToDevice, nullptr));
+      HIPCHK(hipMemcpyAsync(gp + gimg.off_pmat, c->prim_mat.p, pmat.size() * 4, hipMemcpyDeviceToDevice, nullptr));
+      HIPCHK(hipMemcpyAsync(gp + gimg.off_mats, c->mats.p, mats_bytes.size(), hipMemcpyDeviceToDevice, nullptr));
+      grc = rtow::grid_build_phase3(c->grid_scratch, hd.gminf, hd.cellf, hd.n, hd.pad, total_ids, gp, gimg.off_cells,
+                                    gimg.off_ids, nullptr, (const double *)c->sph.p, gimg.off_fat,
+                                    (const double *)c->mov.p, ns, gimg.fat_stride);
+      if (grc) return fail(RTOW_EHIP, "device grid build failed (phase 3, stage %d): %s", grc, hipGetErrorString(hipGetLastError()));
+      gimg.ok = true;
+    }
+  }
+  return RTOW_OK;
+}
+
 static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need);
 static int impl_scene_upload(rtow_ctx *c, const rtow_scene_t *s) {
   // AUTO knows no config here: the host builder (include/rtow.h), whatever an earlier rtow_render resolved AUTO to
@@ -564,6 +691,9 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
   c->have_scene = false;
   c->have_rtree = false;
   c->q_map_ok[0] = c->q_map_ok[1] = c->q_map_ok[2] = false;  // (the ray queries' id tables belong to the old scene)
+  c->rf.ready = false;
+  c->rf.refits = 0;
+  c->rf.refit_ms = 0.0;
   c->build_info.ref_tree_nodes = 0;
   c->build_info.ref_tree_stupid_volume = 0.0;
   const double t_up0 = now_ms();
@@ -631,21 +761,9 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
     d[10] = e1[2] * e2[0] - e2[2] * e1[0];
     d[11] = e1[0] * e2[1] - e2[0] * e1[1];
   }
-  std::vector<int32_t> pmat((size_t)ns + nm + nt);
-  for (int i = 0; i < ns; ++i) pmat[i] = s->sphere_mat[i];
-  for (int i = 0; i < nm; ++i) pmat[(size_t)ns + i] = s->moving_mat[i];
-  for (int i = 0; i < nt; ++i) pmat[(size_t)ns + nm + i] = s->triangle_mat[i];
-  std::vector<rtow::DevMaterial> mats(s->n_materials);
-  for (int i = 0; i < s->n_materials; ++i) {
-    const rtow_material_t &m = s->materials[i];
-    rtow::DevMaterial &d = mats[i];
-    std::memset(&d, 0, sizeof d);
-    const bool diel = m.kind == RTOW_MAT_DIELECTRIC;  // attenuation {1,1,1}, common-model.cpp:61
-    for (int k = 0; k < 3; ++k) d.att[k] = diel ? 1.0 : m.albedo[k];
-    d.fuzz = m.kind == RTOW_MAT_LAMBERTIAN ? 0.0 : m.fuzz;
-    d.ir = m.ir;
-    d.kind = m.kind;
-  }
+  std::vector<int32_t> pmat;
+  std::vector<rtow::DevMaterial> mats;
+  scene_materials(s, pmat, mats);
 
   // BVH over the same records, packed with them into one scene image
   // host SAH stops splitting by cost (mostly 1-2 primitives per leaf, cap 4); the radix tree has
@@ -851,50 +969,9 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
   if (!(need & kNeedGrid)) {
     // (not asked for)
   } else if (nt <= grid_max_tris && c->builder == RTOW_BUILDER_DEVICE_LBVH) {
-    // the same grid, built in HBM (csrc/rtow_build_grid.hip); the host does the scalar steps between
-    // the phases with the code the host builder uses, so the image is byte-identical
+    // the same grid, built in HBM (csrc/rtow_build_grid.hip)
     grid_on_device = true;
-    rtow::GridBuildBounds gb;
-    int grc = rtow::grid_build_phase1((const double *)c->sph.p, (const double *)c->sph_r.p, (const double *)c->mov.p,
-                                      (const double *)c->tri.p, ns, nm, nt, s->camera.t0, s->camera.t1, large_ratio,
-                                      nullptr, &c->grid_scratch, &gb);
-    if (grc) return fail(RTOW_EHIP, "device grid build failed (phase 1, stage %d): %s", grc, hipGetErrorString(hipGetLastError()));
-    if (gb.n_small > 0 && gb.n_large <= 64) {
-      rtow::GridHeader hd;
-      rtow::grid_header(gb.gmn, gb.gmx, gb.scale_prims, s->camera.origin, (size_t)gb.n_small, cpp, hd);
-      unsigned long long total_ids = 0, max_list = 0;
-      grc = rtow::grid_build_phase2(c->grid_scratch, hd.gminf, hd.cellf, hd.n, hd.pad, nullptr, &total_ids, &max_list);
-      if (grc) return fail(RTOW_EHIP, "device grid build failed (phase 2, stage %d): %s", grc, hipGetErrorString(hipGetLastError()));
-      if (max_list <= 255 && total_ids + (unsigned long long)gb.n_large < (1u << 24)) {
-        const size_t ncell = (size_t)hd.n[0] * hd.n[1] * hd.n[2];
-        for (int k = 0; k < 3; ++k) gimg.n[k] = hd.n[k];
-        double scale_small = 0.0;  // (the host builder's rule: rtow_grid.h build_grid_image)
-        for (int k = 0; k < 3; ++k)
-          scale_small = std::max({scale_small, std::fabs(gb.gmn[k]), std::fabs(gb.gmx[k]), std::fabs(s->camera.origin[k])});
-        const uint32_t fat = rtow::grid_wants_fat_lists(nm, nt, ncell, (size_t)total_ids + (size_t)gb.n_large,
-                                                        (size_t)gb.n_large, sph, mov, tri, pmat, mats_bytes, (size_t)total_ids,
-                                                        scale_small);
-        rtow::layout_grid_image(ncell, (size_t)total_ids + (size_t)gb.n_large, (size_t)gb.n_large, sph, mov, tri, pmat,
-                                mats_bytes, gimg, true, fat ? (size_t)total_ids : 0, fat ? fat : 48u);
-        if ((rc = c->gblob.ensure(gimg.total_bytes))) return rc;
-        unsigned char *gp = (unsigned char *)c->gblob.p;
-        unsigned char header[64];
-        const uint32_t off_large = (uint32_t)(gimg.off_ids + total_ids * 4);
-        rtow::write_grid_header(header, hd, gimg.n_large, off_large, gimg.off_fat, gimg.fat_stride);
-        HIPCHK(hipMemsetAsync(gp, 0, gimg.total_bytes, nullptr));
-        if ((rc = h2d_block(gp, header, 64))) return rc;  // (`header` is on the stack: never the source of an async copy)
-        if (ns) HIPCHK(hipMemcpyAsync(gp + gimg.off_sph, c->sph.p, sph.size() * 8, hipMemcpyDeviceToDevice, nullptr));
-        if (nm) HIPCHK(hipMemcpyAsync(gp + gimg.off_mov, c->mov.p, mov.size() * 8, hipMemcpyDeviceToDevice, nullptr));
-        if (nt) HIPCHK(hipMemcpyAsync(gp + gimg.off_tri, c->tri.p, tri.size() * 8, hipMemcpyDeviceToDevice, nullptr));
-        HIPCHK(hipMemcpyAsync(gp + gimg.off_pmat, c->prim_mat.p, pmat.size() * 4, hipMemcpyDeviceToDevice, nullptr));
-        HIPCHK(hipMemcpyAsync(gp + gimg.off_mats, c->mats.p, mats_bytes.size(), hipMemcpyDeviceToDevice, nullptr));
-        grc = rtow::grid_build_phase3(c->grid_scratch, hd.gminf, hd.cellf, hd.n, hd.pad, total_ids, gp, gimg.off_cells,
-                                      gimg.off_ids, nullptr, (const double *)c->sph.p, gimg.off_fat,
-                                      (const double *)c->mov.p, ns, gimg.fat_stride);
-        if (grc) return fail(RTOW_EHIP, "device grid build failed (phase 3, stage %d): %s", grc, hipGetErrorString(hipGetLastError()));
-        gimg.ok = true;
-      }
-    }
+    if ((rc = grid_device_build(c, s->camera, ns, nm, nt, sph, mov, tri, pmat, mats_bytes, gimg))) return rc;
   } else if (nt <= grid_max_tris) {
     rtow::build_grid_image(sph, sph_r, mov, tri, s->camera.origin, gimg, cpp, large_ratio, s->camera.t0,
                            s->camera.t1, pmat, mats_bytes);
@@ -942,19 +1019,8 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
   ds.g_off_mats = gimg.off_mats;
   c->n_prims = ns + nm + nt;
 
-  const rtow_camera_t &k = s->camera;
   rtow::DevCamera &dc = c->cam;
-  for (int i = 0; i < 3; ++i) {
-    dc.origin[i] = k.origin[i];
-    dc.u[i] = k.u[i];
-    dc.v[i] = k.v[i];
-    dc.horizontal[i] = k.horizontal[i];
-    dc.vertical[i] = k.vertical[i];
-    dc.llc[i] = k.lower_left_corner[i];
-  }
-  dc.lens_radius = k.lens_radius;
-  dc.t0 = k.t0;
-  dc.t1 = k.t1;
+  camera_record(s->camera, dc);
   {
     std::vector<rtow::DevCamera> one(1, dc);
     if ((rc = upload(c->cam_dev, one))) return rc;
@@ -1623,12 +1689,40 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
 // ---- ray queries (rtow_intersect / rtow_intersect_device) -------------------------------------------------------------
 constexpr int64_t kMaxQueryRays = (1ll << 31) - 64;  // include/rtow.h
 
+// Record slot of a leaf-ordered image -> class-order triangle index (which: 1 the host-built mesh BVH image, 2 the 4-wide
+// image).  The leaf-ordered images hold exact copies of the class-ordered triangle records, so a slot's triangle is found by
+// matching its 96 bytes (identical records — duplicate triangles — are paired in order: any one of them gives the same hit).
+static int match_slots(rtow_ctx *c, int which, std::vector<int32_t> &slot2tri) {
+  const int nt = c->ds.n_tri;
+  const unsigned char *img = which == 1 ? c->ds.blob + c->ds.off_tri : c->ds.blob4 + c->ds.b4_off_tri;
+  const size_t bytes = (size_t)nt * 96u;
+  std::vector<unsigned char> rec_cls(bytes), rec_img(bytes);
+  HIPCHK(hipMemcpy(rec_cls.data(), c->tri.p, bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rec_img.data(), img, bytes, hipMemcpyDeviceToHost));
+  std::vector<int32_t> oc((size_t)nt), oi((size_t)nt);
+  for (int i = 0; i < nt; ++i) oc[i] = oi[i] = i;
+  auto by_record = [](const std::vector<unsigned char> &r) {
+    return [&r](int32_t a, int32_t b) {
+      const int m = std::memcmp(&r[(size_t)a * 96u], &r[(size_t)b * 96u], 96);
+      return m != 0 ? m < 0 : a < b;
+    };
+  };
+  std::sort(oc.begin(), oc.end(), by_record(rec_cls));
+  std::sort(oi.begin(), oi.end(), by_record(rec_img));
+  slot2tri.assign((size_t)nt, -1);
+  for (int k = 0; k < nt; ++k) {
+    if (std::memcmp(&rec_cls[(size_t)oc[k] * 96u], &rec_img[(size_t)oi[k] * 96u], 96) != 0)
+      return fail(RTOW_EINVAL, "internal error: the %s image's triangle records are not those of the scene",
+                  which == 1 ? "BVH" : "4-wide");
+    slot2tri[(size_t)oi[k]] = oc[k];
+  }
+  return RTOW_OK;
+}
+
 // Walk-order primitive id -> insertion index (the uploaded scene's prim_kind / prim_index order; class-major order when
 // the scene came without one).  which: 0 class-major ids (STREAM, GRID, REFTREE walks and a device-built BVH image),
-// 1 the record slots of a host-built mesh BVH image (ds.leaf_direct), 2 the record slots of the 4-wide image.  The
-// leaf-ordered images hold exact copies of the class-ordered triangle records, so a slot's triangle is found by matching
-// its 96 bytes (identical records — duplicate triangles — are paired in order: any one of them gives the same hit).
-// Built on the host at the first query that needs the table after an upload; scene_upload drops them.
+// 1 the record slots of a host-built mesh BVH image (ds.leaf_direct), 2 the record slots of the 4-wide image (match_slots).
+// Built on the host at the first query that needs the table after an upload or a refit; both drop them.
 static int query_map(rtow_ctx *c, int which, const int32_t **out) {
   if (c->q_map_ok[which]) {
     *out = (const int32_t *)c->q_map[which].p;
@@ -1648,28 +1742,13 @@ static int query_map(rtow_ctx *c, int which, const int32_t **out) {
   if (which == 0) {
     table.swap(cls2ins);
   } else {
-    const unsigned char *img = which == 1 ? c->ds.blob + c->ds.off_tri : c->ds.blob4 + c->ds.b4_off_tri;
-    const size_t bytes = (size_t)nt * 96u;
-    std::vector<unsigned char> rec_cls(bytes), rec_img(bytes);
-    HIPCHK(hipMemcpy(rec_cls.data(), c->tri.p, bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rec_img.data(), img, bytes, hipMemcpyDeviceToHost));
-    std::vector<int32_t> oc((size_t)nt), oi((size_t)nt);
-    for (int i = 0; i < nt; ++i) oc[i] = oi[i] = i;
-    auto by_record = [](const std::vector<unsigned char> &r) {
-      return [&r](int32_t a, int32_t b) {
-        const int m = std::memcmp(&r[(size_t)a * 96u], &r[(size_t)b * 96u], 96);
-        return m != 0 ? m < 0 : a < b;
-      };
-    };
-    std::sort(oc.begin(), oc.end(), by_record(rec_cls));
-    std::sort(oi.begin(), oi.end(), by_record(rec_img));
+    // after a refit the records have moved: the maps its first call derived from the images as uploaded
+    std::vector<int32_t> matched;
+    if (!c->rf.ready)
+      if (int rc = match_slots(c, which, matched)) return rc;
+    const std::vector<int32_t> &slot2tri = c->rf.ready ? c->rf.slot2tri[which - 1] : matched;
     table.assign((size_t)nt, -1);
-    for (int k = 0; k < nt; ++k) {
-      if (std::memcmp(&rec_cls[(size_t)oc[k] * 96u], &rec_img[(size_t)oi[k] * 96u], 96) != 0)
-        return fail(RTOW_EINVAL, "internal error: the %s image's triangle records are not those of the scene",
-                    which == 1 ? "BVH" : "4-wide");
-      table[(size_t)oi[k]] = cls2ins[(size_t)ns + nm + oc[k]];
-    }
+    for (int k = 0; k < nt; ++k) table[(size_t)k] = cls2ins[(size_t)ns + nm + slot2tri[(size_t)k]];
   }
   DevBuf &b = c->q_map[which];
   if (int rc = b.ensure(std::max<size_t>(table.size() * sizeof(int32_t), 4))) return rc;
@@ -2065,6 +2144,288 @@ static int impl_render_rgb8(rtow_ctx *c, const rtow_scene_t *scene, const rtow_c
   return check_dropped(c, true);  // never RTOW_OK with samples dropped, with or without `stats`
 }
 
+// ---- in-place refit (rtow_scene_refit) -------------------------------------------------------------------------------
+// The same shape as the resident scene: counts and insertion order (checked before anything is written).
+static int refit_check_shape(const rtow_ctx *c, const rtow_scene_t *s) {
+  if (s->n_spheres != c->ds.n_sph || s->n_moving != c->ds.n_mov || s->n_triangles != c->ds.n_tri || s->n_prims != c->n_prims ||
+      s->n_materials != c->ds.n_mats)
+    return fail(RTOW_EINVAL, "rtow_scene_refit: the scene's counts (%d spheres, %d moving, %d triangles, %d materials) are not "
+                "the resident scene's (%d, %d, %d, %d): call rtow_scene_upload", s->n_spheres, s->n_moving, s->n_triangles,
+                s->n_materials, c->ds.n_sph, c->ds.n_mov, c->ds.n_tri, c->ds.n_mats);
+  const rtow_ctx::HostSceneCopy &h = c->host_scene;
+  const bool order = s->prim_kind && s->prim_index;
+  if (order != h.have_order ||
+      (order && (std::memcmp(s->prim_kind, h.pk.data(), (size_t)s->n_prims * 4) != 0 ||
+                 std::memcmp(s->prim_index, h.pi.data(), (size_t)s->n_prims * 4) != 0)))
+    return fail(RTOW_EINVAL, "rtow_scene_refit: prim_kind / prim_index differ from the resident scene's insertion order");
+  return RTOW_OK;
+}
+
+// What the first refit after an upload derives from the images as built, before they are overwritten: the slot maps of
+// the leaf-ordered images, the parent links of both trees, and the area sum of the binary BVH for the uploaded geometry.
+static int refit_prepare(rtow_ctx *c) {
+  rtow_ctx::Refit &r = c->rf;
+  const rtow::DevScene &ds = c->ds;
+  const int ns = ds.n_sph, nm = ds.n_mov, nt = ds.n_tri, np = c->n_prims;
+  int rc;
+  const bool bvh2 = (c->built & kNeedBvh) != 0;
+  r.slot2tri[0].clear();
+  r.slot2tri[1].clear();
+  if (bvh2 && ds.leaf_direct) {
+    if ((rc = match_slots(c, 1, r.slot2tri[0])) || (rc = r.map2.ensure((size_t)nt * 4))) return rc;
+    HIPCHK(hipMemcpy(r.map2.p, r.slot2tri[0].data(), (size_t)nt * 4, hipMemcpyHostToDevice));
+  }
+  if (c->have_bvh4) {
+    if ((rc = match_slots(c, 2, r.slot2tri[1])) || (rc = r.map4.ensure((size_t)nt * 4))) return rc;
+    HIPCHK(hipMemcpy(r.map4.p, r.slot2tri[1].data(), (size_t)nt * 4, hipMemcpyHostToDevice));
+  }
+  if ((rc = r.area.ensure(8 * sizeof(double))) || (rc = r.pbox.ensure((size_t)np * 48))) return rc;
+  if (bvh2) {
+    const int n = ds.n_nodes;
+    if ((rc = r.par2.ensure((size_t)n * 4)) || (rc = r.flags.ensure((size_t)n * 4)) || (rc = r.nbox2.ensure((size_t)n * 48)) ||
+        (rc = r.partials.ensure(((size_t)n + 255) / 256 * 8)))
+      return rc;
+    if (rtow::refit_bvh2_links(ds.blob, n, (int32_t *)r.par2.p, nullptr))
+      return fail(RTOW_EHIP, "refit link pass failed: %s", hipGetErrorString(hipGetLastError()));
+    // the upload's geometry: its records and shutter are still resident
+    if (rtow::refit_prim_boxes(ds.sph, ds.sph_r, ds.mov, ds.tri, ns, nm, nt, c->cam.t0, c->cam.t1, (double *)r.pbox.p, nullptr) ||
+        rtow::refit_bvh2(const_cast<unsigned char *>(ds.blob), n, ds.off_ids, np,
+                         ds.leaf_direct ? (const int32_t *)r.map2.p : nullptr, ns + nm,
+                         (const double *)r.pbox.p, (const int32_t *)r.par2.p, (uint32_t *)r.flags.p, (double *)r.nbox2.p,
+                         (double *)r.partials.p, /*emit=*/0, c->cam.origin, (double *)r.area.p, nullptr))
+      return fail(RTOW_EHIP, "refit area pass failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  if (c->have_bvh4) {
+    const int n4 = c->build_info.bvh4_nodes;
+    const uint32_t nb = ds.b4_half ? rtow::kBvh4HalfNodeBytes : rtow::kBvh4NodeBytes, co = ds.b4_half ? 48u : 96u;
+    if ((rc = r.par4.ensure((size_t)n4 * 4)) || (rc = r.need4.ensure((size_t)n4 * 4)) ||
+        (rc = r.flags.ensure((size_t)std::max(n4, ds.n_nodes) * 4)) || (rc = r.nbox4.ensure((size_t)n4 * 48)) ||
+        (rc = r.sbox4.ensure((size_t)n4 * 192)))
+      return rc;
+    if (rtow::refit_bvh4_links(ds.blob4, n4, nb, co, (int32_t *)r.par4.p, (int32_t *)r.need4.p, nullptr))
+      return fail(RTOW_EHIP, "refit 4-wide link pass failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  r.ready = true;
+  return RTOW_OK;
+}
+
+static int impl_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  int rc = validate_scene(s);
+  if (rc) return rc;
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  if ((rc = refit_check_shape(c, s))) return rc;
+  const double t_call = now_ms();
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());  // (earlier work may still read the images)
+  rtow_ctx::Refit &r = c->rf;
+  if (!r.ev[0])
+    for (hipEvent_t &e : r.ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(r.ev[0], nullptr));
+  c->have_scene = false;  // (until every image is consistent again: a failure below leaves no scene)
+  c->arena.used = 0;
+  struct ArenaScope {
+    explicit ArenaScope(PinnedArena *a) { g_arena = a; }
+    ~ArenaScope() { g_arena = nullptr; }
+  } arena_scope(&c->arena);
+  if (!r.ready && (rc = refit_prepare(c))) return rc;
+  rtow::DevScene &ds = c->ds;
+  const int ns = ds.n_sph, nm = ds.n_mov, nt = ds.n_tri, np = c->n_prims;
+  const bool bvh2 = (c->built & kNeedBvh) != 0, f32 = (c->built & kNeedF32) != 0;
+
+  // raw geometry, material indices and records through the pinned arena; the derived records on the device
+  std::vector<int32_t> pmat;
+  std::vector<rtow::DevMaterial> mats;
+  scene_materials(s, pmat, mats);
+  const size_t mats_n = mats.size() * sizeof(rtow::DevMaterial);
+  if ((rc = r.g_sph.ensure((size_t)ns * 32 + 8)) || (rc = r.g_mov.ensure((size_t)nm * 64 + 8)) ||
+      (rc = r.g_tri.ensure((size_t)nt * 72 + 8)))
+    return rc;
+  if ((ns && (rc = h2d_block(r.g_sph.p, s->sphere_geom, (size_t)ns * 32))) ||
+      (nm && (rc = h2d_block(r.g_mov.p, s->moving_geom, (size_t)nm * 64))) ||
+      (nt && (rc = h2d_block(r.g_tri.p, s->triangle_geom, (size_t)nt * 72))) ||
+      (rc = h2d_block(c->prim_mat.p, pmat.data(), (size_t)np * 4)) || (rc = h2d_block(c->mats.p, mats.data(), mats_n)))
+    return rc;
+  auto *sph = (double *)c->sph.p, *sph_r = (double *)c->sph_r.p, *mov = (double *)c->mov.p, *tri = (double *)c->tri.p;
+  const auto *prim_mat = (const int32_t *)c->prim_mat.p;
+  if (rtow::refit_records((const double *)r.g_sph.p, (const double *)r.g_mov.p, (const double *)r.g_tri.p, ns, nm, nt, sph,
+                          sph_r, mov, tri, c->have_tri16 ? (double *)c->tri16.p : nullptr, nullptr))
+    return fail(RTOW_EHIP, "refit record pass failed: %s", hipGetErrorString(hipGetLastError()));
+  if ((bvh2 || c->have_bvh4) &&
+      rtow::refit_prim_boxes(sph, sph_r, mov, tri, ns, nm, nt, s->camera.t0, s->camera.t1, (double *)r.pbox.p, nullptr))
+    return fail(RTOW_EHIP, "refit box pass failed: %s", hipGetErrorString(hipGetLastError()));
+  auto d2d = [](void *dst, const void *src, size_t n) {
+    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, nullptr) : hipSuccess;
+  };
+  const int32_t *map2 = ds.leaf_direct ? (const int32_t *)r.map2.p : nullptr;
+  const rtow_camera_t &cam = s->camera;
+
+  // binary BVH: records, boxes, planes (and the f32 build's copy of it)
+  if (bvh2) {
+    unsigned char *b = (unsigned char *)c->blob.p;
+    if (map2) {
+      if (rtow::refit_tri_section(nt, tri, prim_mat + ns + nm, map2, b, ds.off_tri, ds.off_pmat, 0, nullptr))
+        return fail(RTOW_EHIP, "refit record scatter failed: %s", hipGetErrorString(hipGetLastError()));
+    } else {
+      HIPCHK(d2d(b + ds.off_sph, sph, (size_t)ns * 32));
+      HIPCHK(d2d(b + ds.off_mov, mov, (size_t)nm * 64));
+      HIPCHK(d2d(b + ds.off_tri, tri, (size_t)nt * 96));
+      HIPCHK(d2d(b + ds.off_pmat, prim_mat, (size_t)np * 4));
+    }
+    HIPCHK(d2d(b + ds.off_mats, c->mats.p, mats_n));
+    if (rtow::refit_bvh2(b, ds.n_nodes, ds.off_ids, np, map2, ns + nm, (const double *)r.pbox.p, (const int32_t *)r.par2.p,
+                         (uint32_t *)r.flags.p, (double *)r.nbox2.p, (double *)r.partials.p, /*emit=*/1, cam.origin,
+                         (double *)r.area.p + 1, nullptr))
+      return fail(RTOW_EHIP, "refit BVH pass failed: %s", hipGetErrorString(hipGetLastError()));
+    if (f32) {  // the same layout as uploaded: nodes and ids, then the records
+      const rtow::DevScene &d32 = c->ds32;
+      unsigned char *b32 = (unsigned char *)c->blob32.p;
+      HIPCHK(d2d(b32, b, ds.off_sph));
+      HIPCHK(d2d(b32 + d32.off_sph, sph, (size_t)ns * 32));
+      HIPCHK(d2d(b32 + d32.off_mov, mov, (size_t)nm * 64));
+      if (!map2) HIPCHK(d2d(b32 + d32.off_pmat, prim_mat, (size_t)np * 4));
+      if (rtow::refit_tri_section(nt, tri, prim_mat + ns + nm, map2, b32, d32.off_tri, map2 ? d32.off_pmat : ~0u, 1, nullptr) ||
+          rtow::refit_spheres32(ns, nm, sph, mov, b32, d32.off_sph32, d32.off_mov32, nullptr))
+        return fail(RTOW_EHIP, "refit f32 record scatter failed: %s", hipGetErrorString(hipGetLastError()));
+      HIPCHK(d2d(b32 + d32.off_mats, c->mats.p, mats_n));
+    }
+  }
+
+  // 4-wide BVH: records in leaf order, boxes, planes in a frame from the new root box
+  if (c->have_bvh4) {
+    unsigned char *b4 = (unsigned char *)c->blob4.p;
+    const int n4 = c->build_info.bvh4_nodes;
+    const uint32_t nb = ds.b4_half ? rtow::kBvh4HalfNodeBytes : rtow::kBvh4NodeBytes, co = ds.b4_half ? 48u : 96u;
+    double *frame_dev = (double *)r.area.p + 2;
+    if (rtow::refit_tri_section(nt, tri, prim_mat + ns + nm, (const int32_t *)r.map4.p, b4, ds.b4_off_tri, ds.b4_off_pmat, 0,
+                                nullptr) ||
+        rtow::refit_bvh4(b4, n4, nb, co, (int)ds.b4_half, nt, (const int32_t *)r.map4.p, ns + nm, (const double *)r.pbox.p,
+                         (const int32_t *)r.par4.p, (const int32_t *)r.need4.p, (uint32_t *)r.flags.p, (double *)r.nbox4.p,
+                         (double *)r.sbox4.p, cam.origin, frame_dev, nullptr))
+      return fail(RTOW_EHIP, "refit 4-wide pass failed: %s", hipGetErrorString(hipGetLastError()));
+    HIPCHK(d2d(b4 + ds.b4_off_mats, c->mats.p, mats_n));
+    if (ds.b4_half) {  // the frame is a launch parameter: 48 bytes back
+      double frame[6];
+      HIPCHK(hipMemcpy(frame, frame_dev, sizeof frame, hipMemcpyDeviceToHost));
+      for (int k = 0; k < 3; ++k) {
+        ds.b4_c[k] = frame[k];
+        ds.b4_is[k] = (float)(1.0 / frame[3 + k]);
+      }
+    }
+  }
+
+  // the grid cannot be refit: rebuilt on the device, present exactly when a fresh upload would build it
+  rtow::GridImage gimg;
+  if ((c->built & kNeedGrid) && nt <= c->knobs.grid_max_tris) {
+    std::vector<double> sph_h((size_t)ns * 4), mov_n((size_t)nm * 8), tri_n((size_t)nt * 12);
+    for (int i = 0; i < ns; ++i) {  // (the fat-list format reads the spheres' r*r)
+      const double *g = s->sphere_geom + 4 * (size_t)i;
+      for (int k = 0; k < 3; ++k) sph_h[4 * (size_t)i + k] = g[k];
+      sph_h[4 * (size_t)i + 3] = std::copysign(g[3] * g[3], g[3]);
+    }
+    std::vector<unsigned char> mats_bytes(mats_n);
+    std::memcpy(mats_bytes.data(), mats.data(), mats_n);
+    if ((rc = grid_device_build(c, cam, ns, nm, nt, sph_h, mov_n, tri_n, pmat, mats_bytes, gimg))) return rc;
+  }
+  if (c->built & kNeedGrid) {
+    c->have_grid = gimg.ok;
+    c->grid_fat_stride = (gimg.ok && gimg.off_fat) ? gimg.fat_stride : 0u;
+    c->gblob_bytes = gimg.ok ? (uint32_t)gimg.total_bytes : 0u;
+    ds.gblob = (const unsigned char *)c->gblob.p;
+    ds.gblob_bytes = c->gblob_bytes;
+    ds.g_off_cells = gimg.off_cells;
+    ds.g_off_ids = gimg.off_ids;
+    ds.g_off_sph = gimg.off_sph;
+    ds.g_off_mov = gimg.off_mov;
+    ds.g_off_tri = gimg.off_tri;
+    ds.g_off_pmat = gimg.off_pmat;
+    ds.g_off_mats = gimg.off_mats;
+  }
+  rtow::DevScene &d32 = c->ds32;
+  if (f32) {
+    d32.gblob = nullptr;
+    d32.gblob_bytes = 0;
+    if (gimg.ok) {
+      Image32 g32;
+      const size_t total = layout_image32(gimg.off_sph, ns, nm, nt, np, mats_n, g32);
+      if ((rc = c->gblob32.ensure(total))) return rc;
+      unsigned char *g = (unsigned char *)c->gblob32.p;
+      HIPCHK(hipMemsetAsync(g, 0, total, nullptr));
+      HIPCHK(d2d(g, c->gblob.p, gimg.off_sph));  // header, cells and ids
+      HIPCHK(d2d(g + g32.off_sph, sph, (size_t)ns * 32));
+      HIPCHK(d2d(g + g32.off_mov, mov, (size_t)nm * 64));
+      HIPCHK(d2d(g + g32.off_pmat, prim_mat, (size_t)np * 4));
+      HIPCHK(d2d(g + g32.off_mats, c->mats.p, mats_n));
+      if (rtow::refit_tri_section(nt, tri, nullptr, nullptr, g, g32.off_tri, ~0u, 1, nullptr) ||
+          rtow::refit_spheres32(ns, nm, sph, mov, g, g32.off_sph32, g32.off_mov32, nullptr))
+        return fail(RTOW_EHIP, "refit f32 grid records failed: %s", hipGetErrorString(hipGetLastError()));
+      d32.gblob = g;
+      d32.gblob_bytes = (uint32_t)total;
+      d32.g_off_sph = g32.off_sph;
+      d32.g_off_mov = g32.off_mov;
+      d32.g_off_tri = g32.off_tri;
+      d32.g_off_sph32 = g32.off_sph32;
+      d32.g_off_mov32 = g32.off_mov32;
+      d32.g_off_pmat = g32.off_pmat;
+      d32.g_off_mats = g32.off_mats;
+    }
+    d32.g_off_cells = ds.g_off_cells;
+    d32.g_off_ids = ds.g_off_ids;
+  }
+  for (int k = 0; k < 3; ++k) {  // (ds32 is ds with the f32 images' fields)
+    d32.b4_c[k] = ds.b4_c[k];
+    d32.b4_is[k] = ds.b4_is[k];
+  }
+  for (auto &o : c->occ) o[0] = o[1] = o[2] = o[3] = o[4] = 0;  // (image sizes decide the launch shapes)
+
+  // camera, host copy of the scene (the reference tree is rebuilt from it at its next use)
+  camera_record(cam, c->cam);
+  if ((rc = h2d_block(c->cam_dev.p, &c->cam, sizeof c->cam))) return rc;
+  if (f32) {
+    const double *cd = reinterpret_cast<const double *>(&c->cam);
+    float cam32[21];
+    for (int i = 0; i < 21; ++i) cam32[i] = (float)cd[i];
+    if ((rc = h2d_block(c->cam32_dev.p, cam32, sizeof cam32))) return rc;
+  }
+  rtow_ctx::HostSceneCopy &h = c->host_scene;
+  h.sg.assign(s->sphere_geom, s->sphere_geom + 4 * (size_t)ns);
+  h.mg.assign(s->moving_geom, s->moving_geom + 8 * (size_t)nm);
+  h.tg.assign(s->triangle_geom, s->triangle_geom + 9 * (size_t)nt);
+  c->have_rtree = false;
+  c->q_map_ok[1] = c->q_map_ok[2] = false;  // (rebuilt from the refit's slot maps; table 0 does not move)
+
+  HIPCHK(hipEventRecord(r.ev[1], nullptr));
+  HIPCHK(hipEventRecord(c->upload_ev, nullptr));  // ordering contract of rtow_scene_upload
+  c->have_scene = true;
+  r.refits++;
+  r.refit_ms = now_ms() - t_call;
+  return RTOW_OK;
+}
+
+int rtow_refit_info(rtow_ctx *c, rtow_refit_info_t *out) {
+  if (!c || !out) return fail(RTOW_EINVAL, "NULL argument");
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  std::memset(out, 0, sizeof *out);
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());
+  const rtow_ctx::Refit &r = c->rf;
+  out->refits = r.refits;
+  out->grid_resident = c->have_grid ? 1 : 0;
+  out->refit_ms = r.refit_ms;
+  out->bvh_area_ratio = (c->built & kNeedBvh) ? 1.0 : 0.0;
+  if (r.refits > 0) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, r.ev[0], r.ev[1]));
+    out->device_ms = ms;
+    if (c->built & kNeedBvh) {
+      double a[2];
+      HIPCHK(hipMemcpy(a, r.area.p, sizeof a, hipMemcpyDeviceToHost));
+      out->bvh_area_ratio = a[0] > 0.0 ? a[1] / a[0] : 1.0;  // (a tree without inner nodes cannot degrade)
+    }
+  }
+  return RTOW_OK;
+}
+
 // ---- the guarded entry points (see guarded() above) ----
 int rtow_ctx_create(int device_id, rtow_ctx **out) {
   return guarded("rtow_ctx_create", [&] { return impl_ctx_create(device_id, out); });
@@ -2103,6 +2464,9 @@ int rtow_occluded_device(rtow_ctx *c, int32_t precision, int32_t kernel, const v
 int rtow_occluded(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, uint8_t *occluded,
                   rtow_stats_t *stats) {
   return guarded("rtow_occluded", [&] { return impl_occluded(c, precision, kernel, rays, n_rays, occluded, stats); });
+}
+int rtow_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
+  return guarded("rtow_scene_refit", [&] { return impl_scene_refit(c, s); });
 }
 int rtow_debug_schedule(rtow_ctx *c, const rtow_config_t *cfg, uint32_t *out, int32_t capacity_pairs) {
   return guarded("rtow_debug_schedule", [&] { return impl_debug_schedule(c, cfg, out, capacity_pairs); });

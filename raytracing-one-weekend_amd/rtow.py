@@ -91,6 +91,14 @@ class BuildInfo(C.Structure):
     ]
 
 
+class RefitInfo(C.Structure):
+    """rtow_refit_info_t: the refits since the last upload."""
+    _fields_ = [
+        ("refits", C.c_int32), ("grid_resident", C.c_int32),
+        ("refit_ms", C.c_double), ("device_ms", C.c_double), ("bvh_area_ratio", C.c_double),
+    ]
+
+
 class HostConfig(C.Structure):
     _fields_ = [
         ("number_of_balls_sqrt", C.c_int32), ("aspect_ratio", C.c_double),
@@ -142,6 +150,7 @@ EXPORTS = [
     "rtow_multi_render", "rtow_multi_destroy", "rtow_host_reftree_info",
     "rtow_render_device_rgb8", "rtow_multi_render_rgb8", "rtow_multi_frame_breakdown",
     "rtow_intersect_device", "rtow_intersect", "rtow_occluded_device", "rtow_occluded",
+    "rtow_scene_refit", "rtow_refit_info",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -228,6 +237,9 @@ def lib():
                                            C.c_void_p, C.POINTER(Stats)]
         L.rtow_occluded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.POINTER(Stats)]
+    if hasattr(L, "rtow_scene_refit"):
+        L.rtow_scene_refit.argtypes = [C.c_void_p, C.POINTER(Scene)]
+        L.rtow_refit_info.argtypes = [C.c_void_p, C.POINTER(RefitInfo)]
     L.rtow_profile_collect.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     if hasattr(L, "rtow_debug_schedule"):  # (absent from older builds loaded through RTOW_LIB for A/B runs)
         L.rtow_debug_schedule.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(C.c_uint32), C.c_int32]
@@ -351,6 +363,19 @@ class Context:
     def upload(self, scene):
         s = scene.c if isinstance(scene, HostScene) else scene
         check(lib().rtow_scene_upload(self._h, C.byref(s)), "rtow_scene_upload")
+
+    def refit(self, scene):
+        """Replace the resident scene's geometry, materials and camera in place, keeping its trees' topology
+        (rtow_scene_refit): same counts and insertion order as the uploaded scene."""
+        s = scene.c if isinstance(scene, HostScene) else scene
+        check(lib().rtow_scene_refit(self._h, C.byref(s)), "rtow_scene_refit")
+
+    def refit_info(self) -> RefitInfo:
+        """Refits since the last upload, the last one's host and device times, and the binary BVH's area ratio
+        (rtow_refit_info; synchronises)."""
+        ri = RefitInfo()
+        check(lib().rtow_refit_info(self._h, C.byref(ri)), "rtow_refit_info")
+        return ri
 
     def set_builder(self, builder: int):
         """BUILDER_AUTO (default of a new context), BUILDER_HOST_SAH or BUILDER_DEVICE_LBVH; applies from the next upload."""
