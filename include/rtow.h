@@ -347,8 +347,16 @@ typedef struct rtow_hit_t {   /* 72 B */
  *
  *   precision  RTOW_F64_STRICT: t, point, normal and front_face are bit-identical to the reference's hit tests (the
  *                               oracle's), under every kernel;
- *              RTOW_F64_FAST:   the fast build's walks and tests; parity by tolerance (relative 1e-9 on t, with a
- *                               different primitive only at such near-ties);
+ *              RTOW_F64_FAST:   the fast build's walks and tests.  Against the reference's hit tests over the real
+ *                               numbers (tests/exact_hits.py): on a ray all of whose decisions (edge tests, the
+ *                               det >= 1e-6 cut, the discriminant, t against 0.001 and tmax, front_face, the gap to the
+ *                               second-nearest hit) are clear of their rounding band |q| > 34 u S_q (u = 2^-53, S_q the
+ *                               sum of q's absolute terms), hit / miss, the primitive (one of an exact tie) and
+ *                               front_face are exact, t is within 34 u (S_num + |t| S_den) / |den| of the exact root,
+ *                               point and normal follow; on any other ray the answer is one the band allows (a
+ *                               primitive whose own tests are within it, or a miss where every hit is).  An exactly
+ *                               tangent ray (discriminant 0) misses.  GRID walks the unit direction, so its triangle
+ *                               cut is det >= 1e-6 |d| (the same cut for |d| = 1);
  *              RTOW_F32:        refused (RTOW_EINVAL).
  *   kernel     RTOW_KERNEL_AUTO resolves as a render of the resident scene does; BRUTE, BVH, GRID and BVH4 have the
  *              render's fallbacks and residency rules (after the lean upload of rtow_render a strategy whose structures
@@ -381,8 +389,10 @@ int rtow_intersect(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_
  *
  *   precision  RTOW_F64_STRICT: occluded[i] == (rtow_intersect(...).t <= tmax) for every ray, under every kernel (and
  *                               the same under BRUTE, BVH, GRID and BVH4 for time in [0, 1]);
- *              RTOW_F64_FAST:   the fast build's walks; may differ from the fast closest hit's t <= tmax only where
- *                               |t - tmax| <= 1e-9 * max(1, tmax);
+ *              RTOW_F64_FAST:   the fast build's walks; the exact any-hit answer on every ray whose decisions are clear
+ *                               of the band of rtow_intersect_device (t against tmax included), an answer the band
+ *                               allows on the others; an exactly tangent ray is not occluded by that sphere; GRID's
+ *                               triangle cut is det >= 1e-6 |d|;
  *              RTOW_F32:        refused (RTOW_EINVAL).
  *   kernel     as rtow_intersect_device: the same resolution, fallbacks, residency rules (RTOW_ENOSCENE after a lean
  *              upload) and kernel_used; RTOW_KERNEL_REFTREE is strict only (it runs the reference tree's closest hit and

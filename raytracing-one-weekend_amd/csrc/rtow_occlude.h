@@ -172,7 +172,7 @@ __device__ __forceinline__ bool any_hit_grid(const Image<LDS> &im, const DevScen
         for (int j = 0; j < 4; ++j) sphere_resolve<double>(dd[j], hh[j], ray.a64, ray.inv_a64, id[j], ray.tmin, best);
         last_id = id[3];
       } else {
-        leaf_test<LDS, false>(im, sc, off, lf + k, 4u, ray, best, nprim, last_id);
+        leaf_test<LDS, false, 0, true>(im, sc, off, lf + k, 4u, ray, best, nprim, last_id);
       }
     }
     for (; k + 1 < n_large; k += 2) {
@@ -188,10 +188,10 @@ __device__ __forceinline__ bool any_hit_grid(const Image<LDS> &im, const DevScen
         sphere_resolve<double>(db, hb, ray.a64, ray.inv_a64, ib, ray.tmin, best);
         last_id = ib;
       } else {
-        leaf_test<LDS, false>(im, sc, off, lf + k, 2u, ray, best, nprim, last_id);
+        leaf_test<LDS, false, 0, true>(im, sc, off, lf + k, 2u, ray, best, nprim, last_id);
       }
     }
-    if (k < n_large) leaf_test<LDS, false>(im, sc, off, lf + k, n_large - k, ray, best, nprim, last_id);
+    if (k < n_large) leaf_test<LDS, false, 0, true>(im, sc, off, lf + k, n_large - k, ray, best, nprim, last_id);
   }
   const float tmax32 = round_up_f32(best.t);
   stage_prio<kPrioSetup>();

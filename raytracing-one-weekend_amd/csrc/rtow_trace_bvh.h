@@ -139,7 +139,10 @@ __device__ __forceinline__ RayForms make_unit_ray_forms(V3d o, V3d du, double ti
 // grid-cell members, tested in binary32 by the f32 build (no effect in the binary64 builds).
 // SPEC (rtow_device.h, kSpec*): what the host knows about the scene — the classes that cannot occur and the list
 // format that is there are told to the compiler, which drops their code (and the registers it would hold).
-template <bool LDS, bool SMALL, int SPEC = 0>
+// GRID: the ids are a grid image's list (the large-primitive list of rtow_grid.h), read from it whatever
+// sc.leaf_direct says — that flag describes the BVH image's leaves only (a host-built mesh BVH with a triangle in the
+// grid's large list read triangle records far past the image's end).
+template <bool LDS, bool SMALL, int SPEC = 0, bool GRID = false>
 __device__ __forceinline__ void leaf_test(const Image<LDS> &im, const DevScene &sc, ImgOffsets off,
                                           uint32_t first, uint32_t count, const RayForms &ray, Closest &best,
                                           uint32_t &nprim, int &last_id) {
@@ -210,7 +213,7 @@ __device__ __forceinline__ void leaf_test(const Image<LDS> &im, const DevScene &
   }
 #endif
   for (uint32_t k = 0; k < count; ++k) {
-    const int id = (!SMALL && sc.leaf_direct) ? (int)(first + k) : (int)im.u32(off.ids + 4u * (first + k));
+    const int id = (!SMALL && !GRID && sc.leaf_direct) ? (int)(first + k) : (int)im.u32(off.ids + 4u * (first + k));
     if constexpr (SPEC == 1) __builtin_assume(id < sc.n_sph);
     if constexpr (SPEC == 2) __builtin_assume(id < sc.n_sph + sc.n_mov);
     // one-entry mailbox: a primitive spanning adjacent grid cells is listed in each of them

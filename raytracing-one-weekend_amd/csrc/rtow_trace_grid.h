@@ -82,7 +82,7 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
         for (int j = 0; j < 4; ++j) sphere_resolve<double>(dd[j], hh[j], ray.a64, ray.inv_a64, id[j], ray.tmin, best);
         last_id = id[3];
       } else {
-        leaf_test<LDS, false, SPEC>(im, sc, off, lf + k, 4u, ray, best, nprim, last_id);
+        leaf_test<LDS, false, SPEC, true>(im, sc, off, lf + k, 4u, ray, best, nprim, last_id);
       }
     }
     for (; k + 1 < n_large; k += 2) {
@@ -98,10 +98,10 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
         sphere_resolve<double>(db, hb, ray.a64, ray.inv_a64, ib, ray.tmin, best);
         last_id = ib;
       } else {
-        leaf_test<LDS, false, SPEC>(im, sc, off, lf + k, 2u, ray, best, nprim, last_id);
+        leaf_test<LDS, false, SPEC, true>(im, sc, off, lf + k, 2u, ray, best, nprim, last_id);
       }
     }
-    if (k < n_large) leaf_test<LDS, false, SPEC>(im, sc, off, lf + k, n_large - k, ray, best, nprim, last_id);
+    if (k < n_large) leaf_test<LDS, false, SPEC, true>(im, sc, off, lf + k, n_large - k, ray, best, nprim, last_id);
   }
   float tmax32 = round_up_f32(best.t);
   // the walk's set-up — clip against the grid, first cell, the DDA's increments: some eighty binary32 instructions and

@@ -1,0 +1,634 @@
+"""An exact reference for the ray queries (rtow_intersect / rtow_occluded): which answers are certain, and how far a
+kernel's answer may be from them.
+
+A helper module for the tests (numpy and the standard library, no GPU).  The semantics are the reference's hit tests
+(oracle/rtow_oracle.cpp sphere_hit_helper / triangle_hit, src/common-model.cpp) over the REAL numbers: every binary64
+input is the dyadic rational it denotes, including tmin (the double nearest 0.001), tmax and the double 1e-6 of the
+triangle cut.
+  * triangle A, B, C: n = (B - A) x (C - A), det = -d.n, ao = o - A, ud = e2.(ao x d), vd = -e1.(ao x d), td = ao.n;
+    a hit iff det >= 1e-6, ud >= 0, vd >= 0, ud + vd <= det, tmin det <= td <= tmax det; t = td / det; front_face 1.
+  * sphere (c, r), the moving sphere's c = c0 + time (c1 - c0): oc = o - c, a = d.d, h = oc.d, c' = oc.oc - r^2,
+    disc = h^2 - a c'; the near root (-h - sqrt disc) / a if it lies in [tmin, tmax], else the far root; front_face =
+    (d.(p - c) < 0) xor (r < 0), i.e. (near root and disc > 0) xor (r < 0).  The kernels evaluate d.(p - c) at their
+    computed p: -+sqrt(disc) + a (t_computed - t), so front_face is decided when sqrt(disc) > a E_t + tau S_ff.  The roots are compared with tmin and tmax
+    exactly, by sign and squaring; where a value is needed it is computed to 130 bits with math.isqrt.
+
+Decided and undecided.  Every decision q of a test is DECIDED when |q| > tau * S_q, where S_q is q's expression
+evaluated on the absolute values of its operands, in the form the kernels evaluate.  A floating-point evaluation of an
+expression of depth k (k roundings on its longest path, inputs included) is within gamma_k * S_q of q, gamma_k ~ k u,
+u = 2^-53; so on a decided decision every kernel takes the exact branch.  A ray is decided when every decision that can
+change its answer is, and the gap between its nearest and its second-nearest hit exceeds both their t bounds.
+
+  * strict (-ffp-contract=off, the reference's expressions): the records round e1 = B - A, e2 = C - A (1), n = e1 x e2
+    (+2: 3); det = -d.n (+3: 6); ao (1), ao x d (3), ud, vd = dot (6); u + v <= 1 on ud * (1/det) (+3: 9); t = td * (1/det)
+    (8).  Sphere: the moving centre c0 + time * dc (2), oc (3), h (6), c' (+1 for the record's r^2: 7), disc (9).
+    k = 9; tau_strict = 2 * 9 u = 18 u (a factor 2 for gamma_k = k u / (1 - k u) and for S taken from the exact operands).
+  * fast (-ffp-contract=fast, rtow_trace_hit.h under RTOW_FAST_MATH): the same forms with fewer roundings, plus the
+    GRID walk on the unit direction (rtow_trace_grid.h): |d|^2 (3), rsqrt and one Newton step (2), d * inv_len (1) perturb
+    every operand that carries d by 6 u, which the quadratic terms of disc see twice (+12 on 9: k = 21, rounded down
+    to 17 for the contractions: every fma saves one rounding in each of the eight two-term sums above).  The fat 48-byte
+    cell-list entries test h = o.d - C.d and c' = |o|^2 - 2 C.o + (|C|^2 - r^2) in WORLD coordinates, so fast S_q takes
+    |o_i| + |c_i| where strict takes |o_i - c_i|.  tau_fast = 2 * 17 u = 34 u.
+  * every other test in the fast build (1/a by rcp + Newton, t = td * rcp(det), the t * det forms of the triangle test)
+    is within those counts.
+  * tmin / tmax against a root t: decided when |t - tmin| (|t - tmax|) exceeds t's bound E_t (below).
+
+The t bound (condition-aware, for the form that computes t):
+  * triangle t = td / det:   E_t = tau (S_td + |t| S_det) / |det|;
+  * sphere t = (-h -+ sqrt disc) / a:   E_t = (tau S_h + min(sqrt(tau S_disc), tau S_disc / sqrt disc) + tau sqrt disc
+    + tau |t| a) / a — the square root's sensitivity min(sqrt e, e / sqrt x) to an error e in x is what makes a nearly
+    tangent ray's root uncertain;
+  * plus u |t| for the rounding of the exact t to binary64 (and the filter's own bound, below, where the filter decided).
+The hit point: |p_i - (o_i + t d_i)| <= |d_i| E_t + 4 u (|o_i| + |t d_i|).  A sphere's normal (p - c) * rsqrt(|p - c|^2):
+within 2 sqrt(3) (max_i |p_i err| + 4 u |c|) / |r| + 8 u of the exact unit normal (dot 3, rsqrt with one Newton step 2,
+product 1: 6 u, rounded up).  A triangle's normal is the record's e1 x e2, bit for bit.
+
+The fast build's GRID walk applies the triangle cut to the UNIT direction: det / |d| >= 1e-6 (rtow_trace_grid.h walks
+d / |d|; the triangle test is the render's).  For |d| = 1 the two agree; the reference is told which one a walk uses
+(`unit_cut`).
+
+Speed.  A vectorised binary64 filter runs over every (ray, primitive) pair first, with the forward error bound
+GF * S_q, GF = 32 u (the filter's own expressions are at most 10 roundings deep): a pair all of whose decisions are
+beyond (tau + GF) S_q is decided there.  The few others go to the exact path (fractions.Fraction).  Large meshes take a
+box prefilter (exact vertex bounds, padded by 1e-6 of the scene's scale: far more than any band) before the filter.
+"""
+from __future__ import annotations
+
+import math
+from fractions import Fraction as Fr
+
+import numpy as np
+
+U = 2.0 ** -53
+TMIN = 0.001
+CUT = 1e-6
+STRICT, FAST = "strict", "fast"
+TAU = {STRICT: 18 * U, FAST: 34 * U}
+GF = 32 * U
+SPHERE, MOVING, TRIANGLE = 0, 1, 2
+MISS, HIT, UND = 0, 1, 2
+_SQRT_BITS = 130
+_FTMIN, _FCUT = Fr(TMIN), Fr(CUT)
+
+
+class CheckError(AssertionError):
+    pass
+
+
+class Cand:
+    """One (ray, primitive) pair that may hit.  status HIT: decided (t, E, front are the exact answer's); UND: the
+    outcomes a kernel may produce, outs = [(t, E, front)] (t NaN: any t).  hit: the exact answer."""
+    __slots__ = ("prim", "status", "hit", "t", "E", "front", "outs", "tex", "key")
+
+    def __init__(self, prim, status, hit, t, E, front, outs, tex=None, key=None):
+        self.prim, self.status, self.hit, self.t, self.E, self.front, self.outs = prim, status, hit, t, E, front, outs
+        self.tex, self.key = tex, key
+
+    def __repr__(self):
+        return f"Cand(prim={self.prim}, status={self.status}, hit={self.hit}, t={self.t}, E={self.E}, outs={self.outs})"
+
+
+# ---- the scene ----------------------------------------------------------------------------------------------------
+class Scene:
+    """Geometry per class and the insertion order: sph [n,4], mov [n,8], tri [n,9], kind / index / material per
+    inserted primitive (test_gpu_query.SceneView has these fields)."""
+
+    def __init__(self, sph, mov, tri, kind, index, prim_mat):
+        self.sph = np.asarray(sph, np.float64).reshape(-1, 4)
+        self.mov = np.asarray(mov, np.float64).reshape(-1, 8)
+        self.tri = np.asarray(tri, np.float64).reshape(-1, 9)
+        self.kind = np.asarray(kind, np.int32)
+        self.index = np.asarray(index, np.int32)
+        self.prim_mat = np.asarray(prim_mat, np.int32)
+        self.ins = {}
+        for p, (k, i) in enumerate(zip(self.kind, self.index)):
+            self.ins[(int(k), int(i))] = p
+        g = self.tri
+        e1, e2 = g[:, 3:6] - g[:, :3], g[:, 6:9] - g[:, :3]
+        self.tri_n = np.stack([e1[:, 1] * e2[:, 2] - e2[:, 1] * e1[:, 2], e1[:, 2] * e2[:, 0] - e2[:, 2] * e1[:, 0],
+                               e1[:, 0] * e2[:, 1] - e2[:, 0] * e1[:, 1]], axis=1)  # the record's n (rtow_capi.cpp)
+
+    @classmethod
+    def of(cls, v):
+        return cls(v.sph, v.mov, v.tri, v.kind, v.index, v.prim_mat)
+
+    @classmethod
+    def class_major(cls, sph, mov, tri, pmat):
+        """Insertion order = class-major order (rtow.Scene built by test_gpu_refit.scene_of); pmat class-major."""
+        ns, nm, nt = len(np.reshape(sph, (-1, 4))), len(np.reshape(mov, (-1, 8))), len(np.reshape(tri, (-1, 9)))
+        kind = np.array([SPHERE] * ns + [MOVING] * nm + [TRIANGLE] * nt, np.int32)
+        index = np.concatenate([np.arange(ns), np.arange(nm), np.arange(nt)]).astype(np.int32)
+        return cls(sph, mov, tri, kind, index, pmat)
+
+    def scale(self):
+        pts = [self.sph[:, :3], self.mov[:, :3], self.mov[:, 3:6]] + [self.tri[:, 3 * k:3 * k + 3] for k in range(3)]
+        pts = np.concatenate([p for p in pts if len(p)] or [np.zeros((1, 3))])
+        return max(1.0, float(np.max(np.abs(pts))))
+
+
+# ---- exact helpers ------------------------------------------------------------------------------------------------
+def _f3(v):
+    return [Fr(float(x)) for x in v]
+
+
+def _dot(a, b):
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+
+
+def _cross(x, y):
+    return [x[1] * y[2] - y[1] * x[2], x[2] * y[0] - y[2] * x[0], x[0] * y[1] - y[0] * x[1]]
+
+
+def _sqrt(x: Fr) -> Fr:
+    """sqrt(x) to _SQRT_BITS bits (x >= 0)."""
+    if x == 0:
+        return Fr(0)
+    p, q = x.numerator, x.denominator
+    sh = max(0, 2 * _SQRT_BITS - (p.bit_length() - q.bit_length()))
+    sh += sh & 1
+    return Fr(math.isqrt((p << sh) // q), 1 << (sh // 2))
+
+
+def _gt(x: Fr, band: float) -> bool:
+    """|x| > band, exactly (band a float)."""
+    return abs(x) > Fr(band) if math.isfinite(band) else False
+
+
+# ---- the exact path, one pair ---------------------------------------------------------------------------------------
+def exact_triangle(o, d, tmax, A, B, C, tau, unit_cut=False):
+    """(hit, decided-or-not outcome, t Fraction, E, outs): see Cand."""
+    o, d, A, B, C = _f3(o), _f3(d), _f3(A), _f3(B), _f3(C)
+    e1 = [B[k] - A[k] for k in range(3)]
+    e2 = [C[k] - A[k] for k in range(3)]
+    n = _cross(e1, e2)
+    det = -_dot(d, n)
+    ao = [o[k] - A[k] for k in range(3)]
+    dao = _cross(ao, d)
+    ud, vd, td = _dot(e2, dao), -_dot(e1, dao), _dot(ao, n)
+    fa = lambda v: [abs(float(x)) for x in v]  # noqa: E731
+    E1a, E2a, AOa, Da = fa(e1), fa(e2), fa(ao), fa(d)
+    Na = [E1a[1] * E2a[2] + E2a[1] * E1a[2], E1a[2] * E2a[0] + E2a[2] * E1a[0], E1a[0] * E2a[1] + E2a[0] * E1a[1]]
+    DAOa = [AOa[1] * Da[2] + Da[1] * AOa[2], AOa[2] * Da[0] + Da[2] * AOa[0], AOa[0] * Da[1] + Da[0] * AOa[1]]
+    S_det, S_ud, S_vd, S_td = (sum(x * y for x, y in zip(p, q)) for p, q in ((Da, Na), (E2a, DAOa), (E1a, DAOa), (AOa, Na)))
+    dd = _dot(d, d)
+    if unit_cut:  # det >= 1e-6 |d|
+        ok_cut = det >= 0 and det * det >= _FCUT * _FCUT * dd
+        hi, lo = det - Fr(tau * S_det), det + Fr(tau * S_det)  # decided: det -+ band both on one side of 1e-6 |d|
+        above = hi > 0 and hi * hi > _FCUT * _FCUT * dd
+        below = lo < 0 or lo * lo < _FCUT * _FCUT * dd
+        dec_cut = above or below
+    else:
+        ok_cut = det >= _FCUT
+        dec_cut = _gt(det - _FCUT, tau * S_det)
+    if not ok_cut and dec_cut:
+        return None
+    if det <= 0:  # (the cut is undecided and the forms below mean nothing: any outcome)
+        return Cand(-1, UND, False, None, math.inf, 1, [(math.nan, math.inf, 1)])
+    t = td / det
+    at = abs(float(t))
+    S_t = S_td + at * S_det
+    E = tau * S_t / float(det) + U * at
+    decs = [(ud >= 0, _gt(ud, tau * S_ud)), (vd >= 0, _gt(vd, tau * S_vd)),
+            (det - ud - vd >= 0, _gt(det - ud - vd, tau * (S_det + S_ud + S_vd))),
+            (t >= _FTMIN, _gt(t - _FTMIN, E))]
+    if math.isfinite(tmax):
+        decs.append((t <= Fr(tmax), _gt(Fr(tmax) - t, E)))
+    decs.append((ok_cut, dec_cut))
+    hit = all(ok for ok, _ in decs)
+    if any(not ok and dec for ok, dec in decs):
+        return None
+    if all(dec for _, dec in decs):
+        return Cand(-1, HIT, True, float(t), E, 1, [(float(t), E, 1)], tex=t)
+    return Cand(-1, UND, hit, float(t) if hit else None, E, 1, [(float(t), E, 1)], tex=t)
+
+
+def exact_sphere(o, d, tmax, c, r, omag, tau):
+    """c: the exact centre (Fractions); omag[i]: the |o_i - c_i| (strict) or |o_i| + |c_i| (fast) of S, per axis."""
+    o, d = _f3(o), _f3(d)
+    r = Fr(float(r))
+    oc = [o[k] - c[k] for k in range(3)]
+    a = _dot(d, d)
+    h = _dot(oc, d)
+    cc = _dot(oc, oc) - r * r
+    disc = h * h - a * cc
+    Da = [abs(float(x)) for x in d]
+    fa = float(a)
+    S_h = sum(m * x for m, x in zip(omag, Da))
+    S_c = sum(m * m for m in omag) + float(r) ** 2
+    S_d = S_h * S_h + fa * S_c
+    dec_disc = _gt(disc, tau * S_d)
+    inward = r < 0
+    if disc < 0:
+        if dec_disc:
+            return None
+        t0 = float(-h / a)
+        E0 = (tau * S_h + math.sqrt(tau * S_d) + tau * abs(t0) * fa) / fa + U * abs(t0)
+        return Cand(-1, UND, False, None, E0, int(inward), [(t0, E0, 0), (t0, E0, 1)])
+    sq = _sqrt(disc)
+    fsq = float(sq)
+    t1, t2 = (-h - sq) / a, (-h + sq) / a
+
+    def E(t):
+        at = abs(float(t))
+        s = math.sqrt(tau * S_d) if fsq == 0 else min(math.sqrt(tau * S_d), tau * S_d / fsq)
+        return (tau * S_h + s + tau * fsq + tau * at * fa) / fa + U * at
+
+    E1, E2 = E(t1), E(t2)
+    tmx = Fr(tmax) if math.isfinite(tmax) else None
+    X = -h - _FTMIN * a  # t1 >= tmin  <=>  X >= sqrt(disc)
+    n1 = X >= 0 and X * X >= disc
+    if tmx is None:
+        x1 = x2 = True
+    else:
+        Y = -h - tmx * a  # t1 <= tmax  <=>  Y <= sqrt(disc)
+        x1 = Y <= 0 or Y * Y <= disc
+        W = tmx * a + h  # t2 <= tmax  <=>  sqrt(disc) <= W
+        x2 = W >= 0 and disc <= W * W
+    Z = _FTMIN * a + h  # t2 >= tmin  <=>  sqrt(disc) >= Z
+    n2 = Z <= 0 or disc >= Z * Z
+    dn1, dn2 = _gt(t1 - _FTMIN, E1), _gt(t2 - _FTMIN, E2)
+    dx1 = tmx is None or _gt(tmx - t1, E1)
+    dx2 = tmx is None or _gt(tmx - t2, E2)
+    S_ff = lambda t: sum(Da[k] * (omag[k] + abs(float(t)) * Da[k]) for k in range(3))  # noqa: E731
+    f_near = int((disc > 0) != inward)
+    f_far = int(inward)
+    if n1:
+        hit, t, Et, front = x1, t1, E1, f_near
+        dec = dn1 and dx1
+    else:
+        hit, t, Et, front = n2 and x2, t2, E2, f_far
+        dec = dn1 and dn2 and dx2
+    dec_front = fsq > fa * max(E1, E2) + tau * S_ff(t)  # (d.(p - c) = -+sqrt(disc) + a (t_computed - t))
+    outs = []
+    if (n1 or not dn1) and (x1 or not dx1):
+        outs.append((float(t1), E1, f_near))
+        if not dec_front:
+            outs.append((float(t1), E1, 1 - f_near))
+    if (not n1 or not dn1) and (n2 or not dn2) and (x2 or not dx2):
+        outs.append((float(t2), E2, f_far))
+        if not dec_front:
+            outs.append((float(t2), E2, 1 - f_far))
+    if not dec_disc:  # and the miss
+        dec = False
+    if dec and hit and dec_front:
+        return Cand(-1, HIT, True, float(t), Et, front, [(float(t), Et, front)], tex=t)
+    if dec and not hit:
+        return None
+    if not outs:
+        return None
+    return Cand(-1, UND, hit, float(t) if hit else None, Et, front, outs, tex=t if hit else None)
+
+
+# ---- the binary64 filter over pairs ----------------------------------------------------------------------------------
+def _tri_filter(o, d, tmax, A, e1, e2, tau, unit_cut):
+    """Pairs [m]: status (0 miss, 1 hit, 2 exact path), t, E."""
+    n = np.stack([e1[:, 1] * e2[:, 2] - e2[:, 1] * e1[:, 2], e1[:, 2] * e2[:, 0] - e2[:, 2] * e1[:, 0],
+                  e1[:, 0] * e2[:, 1] - e2[:, 0] * e1[:, 1]], axis=1)
+    Na = np.stack([np.abs(e1[:, 1] * e2[:, 2]) + np.abs(e2[:, 1] * e1[:, 2]),
+                   np.abs(e1[:, 2] * e2[:, 0]) + np.abs(e2[:, 2] * e1[:, 0]),
+                   np.abs(e1[:, 0] * e2[:, 1]) + np.abs(e2[:, 0] * e1[:, 1])], axis=1)
+    det = -np.einsum("ij,ij->i", d, n)
+    ao = o - A
+    dao = np.stack([ao[:, 1] * d[:, 2] - d[:, 1] * ao[:, 2], ao[:, 2] * d[:, 0] - d[:, 2] * ao[:, 0],
+                    ao[:, 0] * d[:, 1] - d[:, 0] * ao[:, 1]], axis=1)
+    AOa, Da = np.abs(ao), np.abs(d)
+    DAOa = np.stack([AOa[:, 1] * Da[:, 2] + Da[:, 1] * AOa[:, 2], AOa[:, 2] * Da[:, 0] + Da[:, 2] * AOa[:, 0],
+                     AOa[:, 0] * Da[:, 1] + Da[:, 0] * AOa[:, 1]], axis=1)
+    ud = np.einsum("ij,ij->i", e2, dao)
+    vd = -np.einsum("ij,ij->i", e1, dao)
+    td = np.einsum("ij,ij->i", ao, n)
+    S_det = np.einsum("ij,ij->i", Da, Na)
+    S_ud = np.einsum("ij,ij->i", np.abs(e2), DAOa)
+    S_vd = np.einsum("ij,ij->i", np.abs(e1), DAOa)
+    S_td = np.einsum("ij,ij->i", AOa, Na)
+    k = tau + GF
+    cut = CUT * np.sqrt(np.einsum("ij,ij->i", d, d)) if unit_cut else CUT
+    S_cut = S_det + (CUT * np.sqrt(np.einsum("ij,ij->i", Da, Da)) * 4 * U if unit_cut else 0.0)
+    q_cut = det - cut
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        t = td / det
+        at = np.abs(t)
+        E = k * (S_td + at * S_det) / det + 2 * U * at
+        decs = [(q_cut, k * S_cut), (ud, k * S_ud), (vd, k * S_vd), (det - ud - vd, k * (S_det + S_ud + S_vd)),
+                (t - TMIN, E), (tmax - t, np.where(np.isfinite(tmax), E, 0.0))]
+        fail = np.zeros(len(o), bool)
+        sure = np.ones(len(o), bool)
+        for q, b in decs:
+            fail |= q < -b
+            sure &= q > b
+    st = np.where(fail, MISS, np.where(sure & (det > 0), HIT, UND)).astype(np.int8)
+    return st, t, E
+
+
+def _sph_filter(o, d, tmax, c, r, omag, tau):
+    oc = o - c
+    a = np.einsum("ij,ij->i", d, d)
+    h = np.einsum("ij,ij->i", oc, d)
+    cc = np.einsum("ij,ij->i", oc, oc) - r * r
+    disc = h * h - a * cc
+    Da = np.abs(d)
+    S_h = np.einsum("ij,ij->i", omag, Da)
+    S_d = S_h * S_h + a * (np.einsum("ij,ij->i", omag, omag) + r * r)
+    k = tau + GF
+    st = np.full(len(o), UND, np.int8)
+    st[disc < -k * S_d] = MISS
+    pos = disc > k * S_d
+    t = np.full(len(o), np.nan)
+    E = np.full(len(o), np.inf)
+    front = np.zeros(len(o), np.int32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        sq = np.sqrt(np.where(pos, disc, 0.0))
+        t1, t2 = (-h - sq) / a, (-h + sq) / a
+
+        def Eof(tt):
+            s = np.minimum(np.sqrt(k * S_d), k * S_d / sq)
+            return (k * S_h + s + k * sq + k * np.abs(tt) * a) / a + 2 * U * np.abs(tt)
+
+        E1, E2 = Eof(t1), Eof(t2)
+        fin = np.isfinite(tmax)
+        near = pos & (t1 - TMIN > E1)
+        far = pos & (TMIN - t1 > E1)
+        near_in = near & ((tmax - t1 > E1) | ~fin)
+        near_out = near & fin & (t1 - tmax > E1)
+        far_in = far & (t2 - TMIN > E2) & ((tmax - t2 > E2) | ~fin)
+        far_out = far & ((TMIN - t2 > E2) | (fin & (t2 - tmax > E2)))
+        tt = np.where(near_in, t1, t2)
+        S_ff = np.einsum("ij,ij->i", Da, omag + np.abs(tt)[:, None] * Da)
+        ff_ok = sq > k * S_ff + a * np.where(near_in, E1, E2)  # (d.(p - c) at the computed t)
+    inward = r < 0
+    st[near_out | far_out] = MISS
+    hit = (near_in | far_in) & ff_ok
+    st[hit] = HIT
+    t[hit] = tt[hit]
+    E[hit] = np.where(near_in, E1, E2)[hit]
+    front[hit] = np.where(near_in, ~inward, inward)[hit]
+    return st, t, E, front
+
+
+# ---- the reference over a ray set -------------------------------------------------------------------------------------
+class Reference:
+    """Per ray of `rays` (RAY_DTYPE) against `scene` (Scene) under `build` (STRICT / FAST): the exact closest hit and
+    any-hit, decided or not, and the candidates (Cand) that explain an undecided ray's answers."""
+
+    def __init__(self, scene, rays, build, unit_cut=False, chunk=1 << 20):
+        self.scene, self.rays, self.build, self.unit_cut = scene, rays, build, unit_cut
+        self.tau = TAU[build]
+        n = len(rays)
+        self.cands = [[] for _ in range(n)]
+        self._o = np.ascontiguousarray(rays["origin"], np.float64)
+        self._d = np.ascontiguousarray(rays["direction"], np.float64)
+        self._time = np.ascontiguousarray(rays["time"], np.float64)
+        self._tmax = np.ascontiguousarray(rays["tmax"], np.float64)
+        self.n_exact = 0
+        self._spheres(chunk)
+        self._triangles(chunk)
+        self._resolve()
+
+    # -- spheres (static and moving) --
+    def _centres(self, ri, cls, ci):
+        if cls == SPHERE:
+            return self.scene.sph[ci, :3], np.zeros((len(ci), 3))
+        g = self.scene.mov[ci]
+        tm = self._time[ri][:, None]
+        dc = g[:, 3:6] - g[:, :3]
+        return g[:, :3] + tm * dc, np.abs(g[:, :3]) + np.abs(tm * dc)
+
+    def _omag(self, o, c, extra):
+        return (np.abs(o) + np.abs(c) if self.build == FAST else np.abs(o - c)) + extra
+
+    def _spheres(self, chunk):
+        for cls, g in ((SPHERE, self.scene.sph), (MOVING, self.scene.mov)):
+            if len(g) == 0:
+                continue
+            r = g[:, 3] if cls == SPHERE else g[:, 6]
+            per = max(1, chunk // len(g))
+            for r0 in range(0, len(self.rays), per):
+                ri = np.repeat(np.arange(r0, min(r0 + per, len(self.rays))), len(g))
+                ci = np.tile(np.arange(len(g)), len(ri) // len(g))
+                c, extra = self._centres(ri, cls, ci)
+                o = self._o[ri]
+                st, t, E, fr = _sph_filter(o, self._d[ri], self._tmax[ri], c, r[ci], self._omag(o, c, extra), self.tau)
+                for j in np.nonzero(st == HIT)[0]:
+                    self._add(ri[j], cls, ci[j], Cand(-1, HIT, True, float(t[j]), float(E[j]), int(fr[j]),
+                                                      [(float(t[j]), float(E[j]), int(fr[j]))]))
+                for j in np.nonzero(st == UND)[0]:
+                    self._exact(ri[j], cls, ci[j])
+
+    def _exact_sphere_pair(self, i, cls, ci):
+        o, d = self._o[i], self._d[i]
+        if cls == SPHERE:
+            g = self.scene.sph[ci]
+            c, r, extra = _f3(g[:3]), g[3], np.zeros(3)
+        else:
+            g = self.scene.mov[ci]
+            c0, c1 = _f3(g[:3]), _f3(g[3:6])
+            tm = Fr(float(self._time[i]))
+            c, r = [c0[k] + tm * (c1[k] - c0[k]) for k in range(3)], g[6]
+            extra = np.abs(g[:3]) + np.abs(self._time[i] * (g[3:6] - g[:3]))
+        cf = np.array([float(x) for x in c])
+        om = self._omag(o[None], cf[None], extra[None])[0]
+        return exact_sphere(o, d, float(self._tmax[i]), c, r, [float(x) for x in om], self.tau)
+
+    def _exact_pair(self, i, cls, ci):
+        self.n_exact += 1
+        if cls == TRIANGLE:
+            g = self.scene.tri[ci]
+            return exact_triangle(self._o[i], self._d[i], float(self._tmax[i]), g[0:3], g[3:6], g[6:9], self.tau,
+                                  self.unit_cut)
+        return self._exact_sphere_pair(i, cls, ci)
+
+    def _exact(self, i, cls, ci):
+        c = self._exact_pair(i, cls, ci)
+        if c is not None:
+            self._add(i, cls, ci, c)
+
+    def _add(self, i, cls, ci, cand):
+        cand.prim = self.scene.ins[(cls, int(ci))]
+        cand.key = (cls, int(ci))
+        self.cands[int(i)].append(cand)
+
+    # -- triangles --
+    def _tri_pairs(self, chunk):
+        tri = self.scene.tri
+        nt, n = len(tri), len(self.rays)
+        if nt * n <= 4 * chunk:
+            per = max(1, chunk // nt)
+            for r0 in range(0, n, per):
+                ri = np.repeat(np.arange(r0, min(r0 + per, n)), nt)
+                yield ri, np.tile(np.arange(nt), len(ri) // nt)
+            return
+        # box prefilter: exact vertex bounds padded by 1e-6 of the scene's scale, slab test over [0, tmax]
+        v = tri.reshape(-1, 3, 3)
+        pad = 1e-6 * self.scene.scale()
+        lo, hi = v.min(1) - pad, v.max(1) + pad
+        per = max(1, chunk // nt)
+        for r0 in range(0, n, per):
+            ids = np.arange(r0, min(r0 + per, n))
+            o, d, tm = self._o[ids][:, None, :], self._d[ids][:, None, :], self._tmax[ids][:, None]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                inv = 1.0 / d
+                a, b = (lo[None] - o) * inv, (hi[None] - o) * inv
+                tn = np.fmax(np.fmax.reduce(np.fmin(a, b), axis=2), 0.0)
+                tf = np.fmin(np.fmin.reduce(np.fmax(a, b), axis=2), tm * (1 + 1e-9))
+            rr, cc = np.nonzero(~(tn > tf * (1 + 1e-9) + 1e-300))
+            yield ids[rr], cc
+
+    def _triangles(self, chunk):
+        if len(self.scene.tri) == 0:
+            return
+        g = self.scene.tri
+        for ri, ci in self._tri_pairs(chunk):
+            if len(ri) == 0:
+                continue
+            A = g[ci, 0:3]
+            st, t, E = _tri_filter(self._o[ri], self._d[ri], self._tmax[ri], A, g[ci, 3:6] - A, g[ci, 6:9] - A,
+                                   self.tau, self.unit_cut)
+            for j in np.nonzero(st == HIT)[0]:
+                self._add(ri[j], TRIANGLE, ci[j], Cand(-1, HIT, True, float(t[j]), float(E[j]), 1,
+                                                       [(float(t[j]), float(E[j]), 1)]))
+            for j in np.nonzero(st == UND)[0]:
+                self._exact(ri[j], TRIANGLE, ci[j])
+
+    # -- per ray --
+    def _tex(self, i, c):
+        if c.tex is None:
+            e = self._exact_pair(i, *c.key)
+            c.tex = e.tex
+        return c.tex
+
+    def _resolve(self):
+        n = len(self.rays)
+        self.decided = np.zeros(n, bool)
+        self.occ = np.zeros(n, bool)
+        self.occ_decided = np.zeros(n, bool)
+        self.ties = [()] * n
+        self.t = np.full(n, np.inf)
+        self.E = np.zeros(n)
+        self.front = np.zeros(n, np.int32)
+        for i, cs in enumerate(self.cands):
+            H = [c for c in cs if c.status == HIT]
+            Uc = [c for c in cs if c.status == UND]
+            self.occ[i] = any(c.hit for c in cs)
+            self.occ_decided[i] = bool(H) or not Uc
+            hits = sorted((c for c in cs if c.hit), key=lambda c: c.t)
+            if hits:  # the exact closest hit and its ties
+                b = hits[0]
+                close = [c for c in hits if c.t - c.E <= b.t + b.E]
+                if len(close) > 1:
+                    m = min(self._tex(i, c) for c in close)
+                    tied = [c for c in close if abs(self._tex(i, c) - m) <= abs(m) * Fr(1, 1 << 120)]
+                else:
+                    tied = [b]
+                self.ties[i] = tuple(sorted(c.prim for c in tied))
+                self.t[i], self.E[i], self.front[i] = tied[0].t, max(c.E for c in tied), tied[0].front
+            if not H:
+                self.decided[i] = not Uc
+                continue
+            best = min(H, key=lambda c: c.t)
+            ok = all(c.status == HIT for c in tied) and len({c.front for c in tied}) == 1
+            for c in cs:
+                if c.prim in self.ties[i]:
+                    continue
+                for (t, E, _) in c.outs:
+                    if not (t - E > best.t + best.E):  # (NaN: any t)
+                        ok = False
+            self.decided[i] = ok
+
+
+# ---- the checker ----------------------------------------------------------------------------------------------------
+def _sphere_of(scene, prim, time):
+    k, i = int(scene.kind[prim]), int(scene.index[prim])
+    if k == SPHERE:
+        g = scene.sph[i]
+        return _f3(g[:3]), g[3], float(np.max(np.abs(g[:3])))
+    g = scene.mov[i]
+    c0, c1, tm = _f3(g[:3]), _f3(g[3:6]), Fr(float(time))
+    return [c0[k] + tm * (c1[k] - c0[k]) for k in range(3)], g[6], float(np.max(np.abs(g[:3]) + np.abs(time * (g[3:6] - g[:3]))))
+
+
+def check(ref, hits, occ=None, what=""):
+    """Every field of `hits` (HIT_DTYPE) and `occ` (bool, optional) against the reference.  Returns the counts; raises
+    CheckError with the first failures."""
+    sc, rays = ref.scene, ref.rays
+    bad = []
+    worst = 0.0
+    diff = 0
+
+    def fail(i, msg):
+        if len(bad) < 8:
+            bad.append((int(i), msg))
+
+    for i in range(len(rays)):
+        h = hits[i]
+        o, d = rays["origin"][i].astype(np.float64), rays["direction"][i].astype(np.float64)
+        gp = int(h["prim"])
+        if occ is not None and ref.occ_decided[i] and bool(occ[i]) != bool(ref.occ[i]):
+            fail(i, f"occluded {bool(occ[i])}, exact {bool(ref.occ[i])}")
+        if occ is not None and not ref.occ_decided[i]:
+            if occ[i] and not ref.cands[i]:
+                fail(i, "occluded with no candidate")
+            if not occ[i] and any(c.status == HIT for c in ref.cands[i]):
+                fail(i, "not occluded with a decided hit")
+        if gp < 0:
+            if not (math.isinf(h["t"]) and h["kind"] == -1 and h["material"] == -1 and h["front_face"] == 0):
+                fail(i, f"miss record {h}")
+            if ref.decided[i] and ref.ties[i]:
+                fail(i, f"miss, exact hit {ref.ties[i]} at {ref.t[i]!r}")
+            elif not ref.decided[i] and any(c.status == HIT for c in ref.cands[i]):
+                fail(i, "miss with a decided hit")
+            continue
+        if gp >= len(sc.kind) or h["kind"] != sc.kind[gp] or h["material"] != sc.prim_mat[gp]:
+            fail(i, f"prim {gp}: kind {h['kind']} material {h['material']}")
+            continue
+        t = float(h["t"])
+        if ref.decided[i]:
+            if gp not in ref.ties[i]:
+                fail(i, f"prim {gp} t {t!r}, exact {ref.ties[i]} at {ref.t[i]!r}")
+                continue
+            te, E = ref.t[i], ref.E[i]
+            if t != te:
+                diff += 1
+            err = abs(t - te) / E if E > 0 else (0.0 if t == te else math.inf)
+            worst = max(worst, err)
+            if not err <= 1.0:
+                fail(i, f"t {t!r}, exact {te!r} +- {E:.3g}")
+            if int(h["front_face"]) != int(ref.front[i]):
+                fail(i, f"front_face {h['front_face']}, exact {ref.front[i]}")
+            pe = o + te * d
+            pb = np.abs(d) * E + 4 * U * (np.abs(o) + np.abs(te * d)) + 1e-300
+            if not np.all(np.abs(h["point"] - pe) <= pb):
+                fail(i, f"point {h['point']}, exact {pe} +- {pb}")
+            if sc.kind[gp] == TRIANGLE:
+                if not np.array_equal(np.asarray(h["normal"]).view(np.uint64), sc.tri_n[sc.index[gp]].view(np.uint64)):
+                    fail(i, f"triangle normal {h['normal']}, record {sc.tri_n[sc.index[gp]]}")
+            else:
+                c, r, cm = _sphere_of(sc, gp, float(rays["time"][i]))
+                ng = [(Fr(float(o[k])) + Fr(te) * Fr(float(d[k])) - c[k]) / abs(Fr(float(r))) for k in range(3)]
+                ng = np.array([float(x) for x in ng])
+                ne = ng if h["front_face"] else -ng
+                nb = 2 * math.sqrt(3) * (float(np.max(pb)) + 4 * U * cm) / abs(r) + 8 * U
+                if not np.all(np.abs(h["normal"] - ne) <= nb):
+                    fail(i, f"sphere normal {h['normal']}, exact {ne} +- {nb:.3g}")
+        else:
+            mine = [c for c in ref.cands[i] if c.prim == gp]
+            if not mine:
+                fail(i, f"undecided: prim {gp} cannot hit")
+                continue
+            ok = False
+            for c in mine:
+                for (te, E, fr) in c.outs:
+                    if math.isnan(te) or (abs(t - te) <= E and int(h["front_face"]) == fr):
+                        ok = True
+            if not ok:
+                fail(i, f"undecided: prim {gp} t {t!r} front {h['front_face']}, outcomes {mine[0].outs}")
+            for c in ref.cands[i]:
+                if c.status == HIT and c.prim != gp and c.t + c.E < t - max(c.E for c in mine):
+                    fail(i, f"undecided: prim {gp} t {t!r} behind decided prim {c.prim} at {c.t!r}")
+                    break
+    n = len(rays)
+    stats = {"rays": n, "decided": int(ref.decided.sum()), "undecided": int(n - ref.decided.sum()),
+             "occ_undecided": int(n - ref.occ_decided.sum()), "t_differs": diff, "worst_t_err": worst,
+             "exact_pairs": ref.n_exact}
+    if bad:
+        raise CheckError(f"{what}: {len(bad)}+ failures: {bad}")
+    return stats
