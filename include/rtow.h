@@ -407,6 +407,62 @@ int rtow_occluded_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const
 int rtow_occluded(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
                   uint8_t *occluded, rtow_stats_t *stats);
 
+/* ---- closest-point (distance) queries -------------------------------------------------------------------------------
+ * "What is the nearest surface to this point?" — for every query point p, the primitive of the resident scene nearest
+ * to p, the distance and the nearest point on it, when that distance is <= max_dist.  The geometry is the records the
+ * device holds (not the caller's B and C): sphere c and copysign(r^2, r); moving sphere c0 + time * (c1 - c0) with the
+ * record's r^2; triangle {a + s e1 + t e2 : s, t >= 0, s + t <= 1} with e1 = B - A, e2 = C - A rounded.  The radius is
+ * R = sqrt(|r^2|) (correctly rounded), so a negative radius (hollow glass) is the same surface; the distance to a sphere is
+ * | |p - c| - R |, and p at the centre reports c + (R, 0, 0).  A degenerate triangle answers as its edges do; no result
+ * is ever NaN for a finite p.  Formulas: csrc/rtow_pointq.h.
+ *
+ *   precision  RTOW_F64_STRICT: dist and point are bit-identical to those formulas evaluated in IEEE binary64 in their
+ *                               written order (tests/point_ref.py mirrors them), under every kernel and with either
+ *                               builder; prim is one of the primitives whose distance equals the minimum exactly (tie
+ *                               rule), and point is that primitive's;
+ *              RTOW_F64_FAST:   the same formulas contracted (FMA) with the fast build's square root and reciprocal.
+ *                               Against the exact distance D of the reported primitive (tests/point_ref.py):
+ *                               D - 64 u S <= dist <= D + 64 u S + min(64 u S k^2, h) (u = 2^-53; S = |p - a|_1 +
+ *                               |e1|_1 + |e2|_1 for a triangle, |p - c|_1 + R (+ |c0|_1 + |time (c1 - c0)|_1 when
+ *                               moving) for a sphere; k = |e1| |e2| / |e1 x e2|, h the triangle's smallest height; the
+ *                               k term is absent for spheres), and that primitive's D is within the same bands of the
+ *                               exact minimum.  The strict build meets the same bound with 32 u;
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ *   kernel     BRUTE tests every primitive; BVH walks the binary tree; BVH4 the 4-wide tree, nearest child first; GRID
+ *              has no point walk and is answered by BVH (kernel_used says BVH); AUTO takes BVH4 if the 4-wide image is
+ *              resident, else BVH if the binary image is, else BRUTE (so it never fails on a resident scene).  An explicit
+ *              BVH4 on a scene without a 4-wide image falls back to BVH, and an explicit BVH whose image was not built by
+ *              the lean upload of rtow_render gives RTOW_ENOSCENE, as in the ray queries.  RTOW_KERNEL_REFTREE: RTOW_EINVAL.
+ *   max_dist   inclusive, and the walk's starting search radius (a short radius prunes from the first node); NaN or
+ *              negative: a miss without a walk; +inf: unbounded.
+ *   time       results are independent of the kernel for time in [0, 1] only (the moving spheres' boxes cover it).
+ * A miss reports dist = +inf, point 0, prim = kind = material = -1.  prim is the insertion index, as rtow_hit_t::prim.
+ * d_queries / d_hits are DEVICE pointers, both 16-byte aligned; nothing beyond n is written.  Enqueued on hip_stream with
+ * the ordering rule of rtow_intersect_device; with stats it synchronises and fills segments = n, prim_tests, node_tests,
+ * kernel_ms, total_ms, kernel_used.  Errors: those of rtow_intersect_device.  n == 0 launches nothing.  One call in
+ * flight per context; the render path (profile ring, dropped-sample word) is not involved. */
+typedef struct rtow_point_query_t { /* 48 B, 16-byte aligned in device memory */
+  double point[3];
+  double time;      /* moving-sphere centre c0 + time*(c1-c0), as in the ray tests */
+  double max_dist;  /* report the nearest primitive only if its distance <= max_dist */
+  double pad_;
+} rtow_point_query_t;
+
+typedef struct rtow_point_hit_t {   /* 48 B */
+  double dist;      /* +inf when nothing is within max_dist */
+  double point[3];  /* nearest point on that primitive's surface; 0 on a miss */
+  int32_t prim;     /* insertion order, exactly as rtow_hit_t::prim; -1 on a miss */
+  int32_t kind;     /* RTOW_PRIM_*; -1 on a miss */
+  int32_t material; /* -1 on a miss */
+  int32_t pad_;
+} rtow_point_hit_t;
+
+int rtow_closest_point_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const void *d_queries, int64_t n,
+                              void *d_hits, void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
+int rtow_closest_point(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
+                       rtow_point_hit_t *hits, rtow_stats_t *stats);
+
 /* ---- in-place refit of the resident scene (moving geometry) ---------------------------------------------------------
  * Replace the geometry, materials and camera of the scene resident in ctx, keeping its trees' topology: the node
  * structure, leaf membership and leaf order of the binary and 4-wide BVHs stay as built; records, boxes and planes are

@@ -261,6 +261,12 @@ int launch_occlude_fast(const TraceParams &p, const void *rays, void *occluded, 
                         int kernel, int grid, int block, unsigned lds_bytes, void *stream);
 int occlude_occupancy_strict(int kernel, int block, unsigned lds_bytes, int *vgprs);
 int occlude_occupancy_fast(int kernel, int block, unsigned lds_bytes, int *vgprs);
+int launch_pointq_strict(const TraceParams &p, const void *queries, void *hits, uint32_t n, const int32_t *map,
+                         unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
+int launch_pointq_fast(const TraceParams &p, const void *queries, void *hits, uint32_t n, const int32_t *map,
+                       unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
+int pointq_occupancy_strict(int kernel, int block, unsigned lds_bytes, int *vgprs);
+int pointq_occupancy_fast(int kernel, int block, unsigned lds_bytes, int *vgprs);
 // csrc/rtow_refit.hip (rtow_scene_refit): 0, or 1 when a launch failed
 int refit_records(const double *g_sph, const double *g_mov, const double *g_tri, int ns, int nm, int nt, double *sph,
                   double *sph_r, double *mov, double *tri, double *tri16, void *stream);
@@ -1321,23 +1327,32 @@ static int impl_render_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb
   return RTOW_OK;
 }
 
-// The strategy a request resolves to, with the render's fallbacks and residency rules (shared by the render and the
-// ray queries); the first RTOW_KERNEL_REFTREE request builds the reference's tree.
-static int resolve_kernel(rtow_ctx *c, int precision, int requested, int *out) {
-  int kernel = requested;
-  // a handful of primitives is cheaper to stream than to walk
+// The strategy RTOW_KERNEL_AUTO stands for in a render of the resident scene (and in the ray queries).
+static int auto_kernel(const rtow_ctx *c, int precision) {
   // AUTO: a handful of primitives is cheaper to stream than to walk; sphere scenes walk the
   // grid (measured 1.3x the BVH on the cover scene); triangle meshes walk the BVH (a triangle
   // spans many cells and its test is 3.5x a sphere's, so duplicates are expensive: 0.4x)
+  const bool bvh4_ok = c->have_bvh4 && precision != RTOW_F32;  // triangle mesh, host builder, binary64 build
+  return c->n_prims <= 16 ? RTOW_KERNEL_BRUTE
+         : (c->have_grid && c->ds.n_tri == 0) ? RTOW_KERNEL_GRID
+         : bvh4_ok ? RTOW_KERNEL_BVH4 : RTOW_KERNEL_BVH;
+}
+
+static int resident_kernel(rtow_ctx *c, int precision, int kernel, bool stream_records, int *out);
+// The strategy a request resolves to, with the render's fallbacks and residency rules (shared by the render and the
+// ray queries); the first RTOW_KERNEL_REFTREE request builds the reference's tree.
+static int resolve_kernel(rtow_ctx *c, int precision, int requested, int *out) {
+  return resident_kernel(c, precision, requested == RTOW_KERNEL_AUTO ? auto_kernel(c, precision) : requested, true, out);
+}
+
+// The fallbacks and residency rules of a chosen strategy.  stream_records: BRUTE reads the STREAM kernel's triangle
+// records (the render and the ray queries; the point query reads the class records every upload keeps).
+static int resident_kernel(rtow_ctx *c, int precision, int kernel, bool stream_records, int *out) {
   const bool strict = precision == RTOW_F64_STRICT;
   const bool f32 = precision == RTOW_F32;
   const bool bvh4_ok = c->have_bvh4 && !f32;  // triangle mesh, host builder, binary64 build
-  if (kernel == RTOW_KERNEL_AUTO)
-    kernel = c->n_prims <= 16 ? RTOW_KERNEL_BRUTE
-             : (c->have_grid && c->ds.n_tri == 0) ? RTOW_KERNEL_GRID
-             : bvh4_ok ? RTOW_KERNEL_BVH4 : RTOW_KERNEL_BVH;
   if (kernel == RTOW_KERNEL_GRID && !c->have_grid) kernel = RTOW_KERNEL_BVH;  // scene not suited to a grid
-  if (kernel == RTOW_KERNEL_BRUTE && c->ds.n_tri > 0 && !c->have_tri16)
+  if (kernel == RTOW_KERNEL_BRUTE && stream_records && c->ds.n_tri > 0 && !c->have_tri16)
     return fail(RTOW_ENOSCENE, "the resident scene was uploaded for another kernel (the STREAM kernel's triangle records are "
                                "missing): call rtow_scene_upload");
   if (kernel == RTOW_KERNEL_BVH4 && !bvh4_ok) kernel = RTOW_KERNEL_BVH;
@@ -1767,14 +1782,27 @@ struct QueryRun {
   bool strict = false;
   LaunchShape shape;
 };
-static int query_begin(rtow_ctx *c, int32_t precision, int32_t kernel_req, rtow_stats_t *stats, QueryRun &q) {
+// The point query's strategy: AUTO takes the best resident tree (BVH4, else BVH, else BRUTE: it never fails on a resident
+// scene); GRID has no point walk and is answered by the binary BVH; then the render's fallbacks and residency rules.
+static int resolve_point_kernel(rtow_ctx *c, int precision, int requested, int *out) {
+  int kernel = requested;
+  if (kernel == RTOW_KERNEL_REFTREE) return fail(RTOW_EINVAL, "point queries: RTOW_KERNEL_REFTREE has no point walk");
+  if (kernel == RTOW_KERNEL_AUTO)
+    kernel = c->have_bvh4 ? RTOW_KERNEL_BVH4 : (c->built & kNeedBvh) ? RTOW_KERNEL_BVH : RTOW_KERNEL_BRUTE;
+  if (kernel == RTOW_KERNEL_GRID) kernel = RTOW_KERNEL_BVH;
+  return resident_kernel(c, precision, kernel, false, out);
+}
+
+static int query_begin(rtow_ctx *c, int32_t precision, int32_t kernel_req, rtow_stats_t *stats, QueryRun &q,
+                       bool point = false) {
   if (precision == RTOW_F32) return fail(RTOW_EINVAL, "ray queries: RTOW_F32 is not supported (binary64 builds only)");
   if (precision != RTOW_F64_STRICT && precision != RTOW_F64_FAST) return fail(RTOW_EINVAL, "unknown precision %d", precision);
   if (kernel_req < RTOW_KERNEL_AUTO || kernel_req > RTOW_KERNEL_REFTREE) return fail(RTOW_EINVAL, "unknown kernel %d", kernel_req);
   if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
   HIPCHK(hipSetDevice(c->device));
   int rc;
-  if ((rc = resolve_kernel(c, precision, kernel_req, &q.kernel))) return rc;
+  if ((rc = point ? resolve_point_kernel(c, precision, kernel_req, &q.kernel) : resolve_kernel(c, precision, kernel_req, &q.kernel)))
+    return rc;
   if ((rc = launch_shape(c, q.kernel, false, q.shape))) return rc;
   q.strict = precision == RTOW_F64_STRICT;
   if (stats) {
@@ -1912,6 +1940,53 @@ static int impl_occluded(rtow_ctx *c, int32_t precision, int32_t kernel, const r
   HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n_rays * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
   if ((rc = impl_occluded_device(c, precision, kernel, c->q_rays.p, n_rays, c->q_occ.p, nullptr, stats))) return rc;
   HIPCHK(hipMemcpy(occluded, c->q_occ.p, (size_t)n_rays, hipMemcpyDeviceToHost));
+  return RTOW_OK;
+}
+
+// Closest-point queries: the closest-hit query's contract (arguments, ordering, stats, query_map) with the point walks.
+static int impl_closest_point_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_queries, int64_t n,
+                                     void *d_hits, void *hip_stream, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n %lld outside [0, 2^31 - 64]", (long long)n);
+  if (n > 0 && (!d_queries || !d_hits)) return fail(RTOW_EINVAL, "NULL query or hit buffer");
+  if (((uintptr_t)d_queries & 15u) != 0u || ((uintptr_t)d_hits & 15u) != 0u)
+    return fail(RTOW_EINVAL, "query and hit buffers must be 16-byte aligned");
+  QueryRun q;
+  int rc;
+  if ((rc = query_begin(c, precision, kernel_req, stats, q, true))) return rc;
+  if (n == 0) return RTOW_OK;
+
+  const int kernel = q.kernel;
+  const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
+  const int32_t *map = nullptr;
+  if ((rc = query_map(c, which, &map))) return rc;
+  const int block = q.shape.block;
+  const unsigned lds = kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;  // (BRUTE: no triangle tiles)
+  const int occ = q.strict ? rtow::pointq_occupancy_strict(kernel, block, lds, nullptr)
+                           : rtow::pointq_occupancy_fast(kernel, block, lds, nullptr);
+  return query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
+    return q.strict ? rtow::launch_pointq_strict(P, d_queries, d_hits, (uint32_t)n, map, counters, kernel, grid, block, lds,
+                                                 hip_stream)
+                    : rtow::launch_pointq_fast(P, d_queries, d_hits, (uint32_t)n, map, counters, kernel, grid, block, lds,
+                                               hip_stream);
+  });
+}
+
+static int impl_closest_point(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
+                              rtow_point_hit_t *hits, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n %lld outside [0, 2^31 - 64]", (long long)n);
+  if (n > 0 && (!queries || !hits)) return fail(RTOW_EINVAL, "NULL query or hit array");
+  if (n == 0) return impl_closest_point_device(c, precision, kernel, nullptr, 0, nullptr, nullptr, stats);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_point_query_t))) ||
+      (rc = c->q_hits.ensure((size_t)n * sizeof(rtow_point_hit_t))))
+    return rc;
+  HIPCHK(hipMemcpy(c->q_rays.p, queries, (size_t)n * sizeof(rtow_point_query_t), hipMemcpyHostToDevice));
+  if ((rc = impl_closest_point_device(c, precision, kernel, c->q_rays.p, n, c->q_hits.p, nullptr, stats))) return rc;
+  HIPCHK(hipMemcpy(hits, c->q_hits.p, (size_t)n * sizeof(rtow_point_hit_t), hipMemcpyDeviceToHost));
   return RTOW_OK;
 }
 
@@ -2464,6 +2539,15 @@ int rtow_occluded_device(rtow_ctx *c, int32_t precision, int32_t kernel, const v
 int rtow_occluded(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, uint8_t *occluded,
                   rtow_stats_t *stats) {
   return guarded("rtow_occluded", [&] { return impl_occluded(c, precision, kernel, rays, n_rays, occluded, stats); });
+}
+int rtow_closest_point_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_queries, int64_t n,
+                              void *d_hits, void *hip_stream, rtow_stats_t *stats) {
+  return guarded("rtow_closest_point_device",
+                 [&] { return impl_closest_point_device(c, precision, kernel, d_queries, n, d_hits, hip_stream, stats); });
+}
+int rtow_closest_point(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
+                       rtow_point_hit_t *hits, rtow_stats_t *stats) {
+  return guarded("rtow_closest_point", [&] { return impl_closest_point(c, precision, kernel, queries, n, hits, stats); });
 }
 int rtow_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
   return guarded("rtow_scene_refit", [&] { return impl_scene_refit(c, s); });

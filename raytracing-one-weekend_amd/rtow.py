@@ -119,10 +119,40 @@ class Hit(C.Structure):
     ]
 
 
+class PointQuery(C.Structure):
+    """rtow_point_query_t (48 B): the nearest primitive is reported if its distance <= max_dist."""
+    _fields_ = [("point", d3), ("time", C.c_double), ("max_dist", C.c_double), ("pad_", C.c_double)]
+
+
+class PointHit(C.Structure):
+    """rtow_point_hit_t (48 B): dist = inf and prim = kind = material = -1 on a miss."""
+    _fields_ = [
+        ("dist", C.c_double), ("point", d3),
+        ("prim", C.c_int32), ("kind", C.c_int32), ("material", C.c_int32), ("pad_", C.c_int32),
+    ]
+
+
 # numpy views of the same layouts (arrays of rays / hits for rtow_intersect*)
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("time", "<f8"), ("direction", "<f8", (3,)), ("tmax", "<f8")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("prim", "<i4"), ("kind", "<i4"),
                       ("material", "<i4"), ("front_face", "<i4")])
+
+
+# rtow_point_query_t / rtow_point_hit_t (rtow_closest_point*)
+POINT_QUERY_DTYPE = np.dtype([("point", "<f8", (3,)), ("time", "<f8"), ("max_dist", "<f8"), ("pad_", "<f8")])
+POINT_HIT_DTYPE = np.dtype([("dist", "<f8"), ("point", "<f8", (3,)), ("prim", "<i4"), ("kind", "<i4"),
+                            ("material", "<i4"), ("pad_", "<i4")])
+
+
+def make_point_queries(points, time=0.0, max_dist=float("inf")):
+    """A POINT_QUERY_DTYPE array from [n, 3] points (time and max_dist: scalars or [n])."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    q = np.empty(len(p), dtype=POINT_QUERY_DTYPE)
+    q["point"] = p
+    q["time"] = time
+    q["max_dist"] = max_dist
+    q["pad_"] = 0.0
+    return q
 
 
 def make_rays(origins, directions, time=0.0, tmax=float("inf")):
@@ -150,7 +180,7 @@ EXPORTS = [
     "rtow_multi_render", "rtow_multi_destroy", "rtow_host_reftree_info",
     "rtow_render_device_rgb8", "rtow_multi_render_rgb8", "rtow_multi_frame_breakdown",
     "rtow_intersect_device", "rtow_intersect", "rtow_occluded_device", "rtow_occluded",
-    "rtow_scene_refit", "rtow_refit_info",
+    "rtow_scene_refit", "rtow_refit_info", "rtow_closest_point_device", "rtow_closest_point",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -237,6 +267,11 @@ def lib():
                                            C.c_void_p, C.POINTER(Stats)]
         L.rtow_occluded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.POINTER(Stats)]
+    if hasattr(L, "rtow_closest_point"):
+        L.rtow_closest_point_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_void_p, C.POINTER(Stats)]
+        L.rtow_closest_point.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.POINTER(Stats)]
     if hasattr(L, "rtow_scene_refit"):
         L.rtow_scene_refit.argtypes = [C.c_void_p, C.POINTER(Scene)]
         L.rtow_refit_info.argtypes = [C.c_void_p, C.POINTER(RefitInfo)]
@@ -485,6 +520,28 @@ class Context:
         check(lib().rtow_occluded_device(self._h, precision, kernel, C.c_void_p(d_rays), n, C.c_void_p(d_occluded),
                                          C.c_void_p(stream), C.byref(st) if st is not None else None),
               "rtow_occluded_device")
+        return st
+
+    def closest_point(self, queries, precision=F64_FAST, kernel=KERNEL_AUTO, want_stats=False):
+        """Nearest primitive to every point (a POINT_QUERY_DTYPE array, host memory) within its max_dist: a
+        POINT_HIT_DTYPE array, and Stats with `want_stats` (rtow_closest_point)."""
+        q = np.ascontiguousarray(queries, dtype=POINT_QUERY_DTYPE).reshape(-1)
+        hits = np.empty(len(q), dtype=POINT_HIT_DTYPE)
+        st = Stats() if want_stats else None
+        check(lib().rtow_closest_point(self._h, precision, kernel, q.ctypes.data_as(C.c_void_p), len(q),
+                                       hits.ctypes.data_as(C.c_void_p), C.byref(st) if st is not None else None),
+              "rtow_closest_point")
+        return (hits, st) if want_stats else hits
+
+    def closest_point_device(self, d_q: int, n: int, d_hits: int, precision=F64_FAST, kernel=KERNEL_AUTO,
+                             stream: int = 0, want_stats=False):
+        """The same on device buffers (raw pointers, both 16-byte aligned: n x 48-byte queries, n x 48-byte hits),
+        enqueued on `stream` (rtow_closest_point_device); returns Stats with `want_stats` (then synchronised), else
+        None."""
+        st = Stats() if want_stats else None
+        check(lib().rtow_closest_point_device(self._h, precision, kernel, C.c_void_p(d_q), n, C.c_void_p(d_hits),
+                                              C.c_void_p(stream), C.byref(st) if st is not None else None),
+              "rtow_closest_point_device")
         return st
 
     def profile_collect(self):
