@@ -247,26 +247,15 @@ int grid_build_phase3(void *handle, const float gminf[3], const float cellf[3], 
                       unsigned long long total_ids, unsigned char *blob_dev, uint32_t off_cells, uint32_t off_ids,
                       void *stream, const double *sph, uint32_t off_fat, const double *mov, int ns, uint32_t fat_stride);
 void grid_build_release(void *handle);
-// csrc/rtow_query_{strict,fast}.hip (rtow_query.h)
-int launch_query_strict(const TraceParams &p, const void *rays, void *hits, uint32_t n, const int32_t *map,
-                        unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
-int launch_query_fast(const TraceParams &p, const void *rays, void *hits, uint32_t n, const int32_t *map,
-                      unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
-int query_occupancy_strict(int kernel, int block, unsigned lds_bytes, int *vgprs);
-int query_occupancy_fast(int kernel, int block, unsigned lds_bytes, int *vgprs);
-// csrc/rtow_occlude_{strict,fast}.hip (rtow_occlude.h)
-int launch_occlude_strict(const TraceParams &p, const void *rays, void *occluded, uint32_t n, unsigned long long *counters,
-                          int kernel, int grid, int block, unsigned lds_bytes, void *stream);
-int launch_occlude_fast(const TraceParams &p, const void *rays, void *occluded, uint32_t n, unsigned long long *counters,
-                        int kernel, int grid, int block, unsigned lds_bytes, void *stream);
-int occlude_occupancy_strict(int kernel, int block, unsigned lds_bytes, int *vgprs);
-int occlude_occupancy_fast(int kernel, int block, unsigned lds_bytes, int *vgprs);
-int launch_pointq_strict(const TraceParams &p, const void *queries, void *hits, uint32_t n, const int32_t *map,
-                         unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
-int launch_pointq_fast(const TraceParams &p, const void *queries, void *hits, uint32_t n, const int32_t *map,
-                       unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
-int pointq_occupancy_strict(int kernel, int block, unsigned lds_bytes, int *vgprs);
-int pointq_occupancy_fast(int kernel, int block, unsigned lds_bytes, int *vgprs);
+// csrc/rtow_{query,occlude,pointq}_{strict,fast}.hip (rtow_query.h, rtow_occlude.h, rtow_pointq.h): the three query kinds
+// share one launcher and one occupancy signature (`map` is unused by the occlusion query)
+using QueryLaunchFn = int(const TraceParams &p, const void *in, void *out, uint32_t n, const int32_t *map,
+                          unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
+using QueryOccupancyFn = int(int kernel, int block, unsigned lds_bytes, int *vgprs);
+QueryLaunchFn launch_query_strict, launch_query_fast, launch_occlude_strict, launch_occlude_fast, launch_pointq_strict,
+    launch_pointq_fast;
+QueryOccupancyFn query_occupancy_strict, query_occupancy_fast, occlude_occupancy_strict, occlude_occupancy_fast,
+    pointq_occupancy_strict, pointq_occupancy_fast;
 // csrc/rtow_refit.hip (rtow_scene_refit): 0, or 1 when a launch failed
 int refit_records(const double *g_sph, const double *g_mov, const double *g_tri, int ns, int nm, int nt, double *sph,
                   double *sph_r, double *mov, double *tri, double *tri16, void *stream);
@@ -1773,10 +1762,41 @@ static int query_map(rtow_ctx *c, int which, const int32_t **out) {
   return RTOW_OK;
 }
 
-// What the two ray queries (rtow_intersect*, rtow_occluded*) share around their kernels.  query_begin: the argument
-// checks after the buffers', the strategy (the render's resolution and residency rules), the launch shape, the stats
-// header.  query_launch: the grid from the kernel's occupancy, the BVH4 spill, the walk fields, and the launch between
-// events on the caller's stream (ordered behind the last upload); with stats, the counters and times.
+// What the three queries (rtow_intersect*, rtow_occluded*, rtow_closest_point*) share around their kernels.  QueryKind:
+// what tells them apart on the host.  query_begin: the argument checks after the buffers', the strategy (the render's
+// resolution and residency rules), the launch shape, the stats header.  query_launch: the grid from the kernel's
+// occupancy, the BVH4 spill, the walk fields, and the launch between events on the caller's stream (ordered behind the
+// last upload); with stats, the counters and times.  query_device / query_host: the two entry forms.
+struct QueryKind {
+  size_t in_bytes, out_bytes;                // record sizes (include/rtow.h)
+  unsigned in_align, out_align;              // alignment required of the device buffers
+  const char *count, *in_name, *out_name;    // the words of the error texts
+  bool mapped;                               // results name primitives by insertion index: needs query_map
+  bool point;                                // point walks: resolve_point_kernel, and BRUTE stages no triangle tiles
+  bool brute_tests_all;                      // its STREAM walk tests every primitive uncounted: prim_tests = n * n_prims
+  DevBuf rtow_ctx::*out_buf;                 // the host form's device result buffer (its input goes through q_rays)
+  rtow::QueryLaunchFn *launch[2];            // [0] strict, [1] fast
+  rtow::QueryOccupancyFn *occupancy[2];
+};
+// closest hit
+static const QueryKind kIntersect = {
+    .in_bytes = sizeof(rtow_ray_t), .out_bytes = sizeof(rtow_hit_t), .in_align = 16, .out_align = 8,
+    .count = "n_rays", .in_name = "ray", .out_name = "hit", .mapped = true, .point = false, .brute_tests_all = true,
+    .out_buf = &rtow_ctx::q_hits, .launch = {rtow::launch_query_strict, rtow::launch_query_fast},
+    .occupancy = {rtow::query_occupancy_strict, rtow::query_occupancy_fast}};
+// any hit: the closest-hit query's contract without its hit records (so no query_map: nothing to translate)
+static const QueryKind kOccluded = {
+    .in_bytes = sizeof(rtow_ray_t), .out_bytes = 1, .in_align = 16, .out_align = 1,
+    .count = "n_rays", .in_name = "ray", .out_name = "result", .mapped = false, .point = false, .brute_tests_all = false,
+    .out_buf = &rtow_ctx::q_occ, .launch = {rtow::launch_occlude_strict, rtow::launch_occlude_fast},
+    .occupancy = {rtow::occlude_occupancy_strict, rtow::occlude_occupancy_fast}};
+// closest point: the closest-hit query's contract (arguments, ordering, stats, query_map) with the point walks
+static const QueryKind kClosestPoint = {
+    .in_bytes = sizeof(rtow_point_query_t), .out_bytes = sizeof(rtow_point_hit_t), .in_align = 16, .out_align = 16,
+    .count = "n", .in_name = "query", .out_name = "hit", .mapped = true, .point = true, .brute_tests_all = false,
+    .out_buf = &rtow_ctx::q_hits, .launch = {rtow::launch_pointq_strict, rtow::launch_pointq_fast},
+    .occupancy = {rtow::pointq_occupancy_strict, rtow::pointq_occupancy_fast}};
+
 struct QueryRun {
   int kernel = 0;
   bool strict = false;
@@ -1871,139 +1891,52 @@ static int query_launch(rtow_ctx *c, const QueryRun &q, int64_t n_rays, int occ,
   return RTOW_OK;
 }
 
-static int impl_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_rays, int64_t n_rays,
-                                 void *d_hits, void *hip_stream, rtow_stats_t *stats) {
+static int query_device(rtow_ctx *c, const QueryKind &k, int32_t precision, int32_t kernel_req, const void *d_in, int64_t n,
+                        void *d_out, void *hip_stream, rtow_stats_t *stats) {
   if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
-  if (n_rays > 0 && (!d_rays || !d_hits)) return fail(RTOW_EINVAL, "NULL ray or hit buffer");
-  if (((uintptr_t)d_rays & 15u) != 0u || ((uintptr_t)d_hits & 7u) != 0u)
-    return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned, hit buffer 8-byte aligned");
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "%s %lld outside [0, 2^31 - 64]", k.count, (long long)n);
+  if (n > 0 && (!d_in || !d_out)) return fail(RTOW_EINVAL, "NULL %s or %s buffer", k.in_name, k.out_name);
+  if (((uintptr_t)d_in & (k.in_align - 1u)) != 0u)
+    return fail(RTOW_EINVAL, "%s buffer must be %u-byte aligned", k.in_name, k.in_align);
+  if (((uintptr_t)d_out & (k.out_align - 1u)) != 0u)
+    return fail(RTOW_EINVAL, "%s buffer must be %u-byte aligned", k.out_name, k.out_align);
   QueryRun q;
   int rc;
-  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
-  if (n_rays == 0) return RTOW_OK;
-
-  const int kernel = q.kernel;
-  const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
-  const int32_t *map = nullptr;
-  if ((rc = query_map(c, which, &map))) return rc;
-  const int block = q.shape.block;
-  const unsigned lds = q.shape.lds_bytes;
-  const int occ = q.strict ? rtow::query_occupancy_strict(kernel, block, lds, nullptr)
-                           : rtow::query_occupancy_fast(kernel, block, lds, nullptr);
-  rc = query_launch(c, q, n_rays, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
-    return q.strict ? rtow::launch_query_strict(P, d_rays, d_hits, (uint32_t)n_rays, map, counters, kernel, grid, block, lds,
-                                                hip_stream)
-                    : rtow::launch_query_fast(P, d_rays, d_hits, (uint32_t)n_rays, map, counters, kernel, grid, block, lds,
-                                              hip_stream);
-  });
-  if (rc == RTOW_OK && stats && kernel == RTOW_KERNEL_BRUTE)
-    stats->prim_tests = (uint64_t)n_rays * (uint64_t)c->n_prims;  // (the closest-hit STREAM walk tests every primitive)
-  return rc;
-}
-
-// Any-hit queries: the closest-hit query's contract without its hit records (so no query_map: nothing to translate).
-static int impl_occluded_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_rays, int64_t n_rays,
-                                void *d_occluded, void *hip_stream, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
-  if (n_rays > 0 && (!d_rays || !d_occluded)) return fail(RTOW_EINVAL, "NULL ray or result buffer");
-  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
-  QueryRun q;
-  int rc;
-  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
-  if (n_rays == 0) return RTOW_OK;
-
-  const int kernel = q.kernel;
-  const int block = q.shape.block;
-  const unsigned lds = q.shape.lds_bytes;
-  const int occ = q.strict ? rtow::occlude_occupancy_strict(kernel, block, lds, nullptr)
-                           : rtow::occlude_occupancy_fast(kernel, block, lds, nullptr);
-  return query_launch(c, q, n_rays, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
-    return q.strict ? rtow::launch_occlude_strict(P, d_rays, d_occluded, (uint32_t)n_rays, counters, kernel, grid, block, lds,
-                                                  hip_stream)
-                    : rtow::launch_occlude_fast(P, d_rays, d_occluded, (uint32_t)n_rays, counters, kernel, grid, block, lds,
-                                                hip_stream);
-  });
-}
-
-static int impl_occluded(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
-                         uint8_t *occluded, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
-  if (n_rays > 0 && (!rays || !occluded)) return fail(RTOW_EINVAL, "NULL ray or result array");
-  if (n_rays == 0) return impl_occluded_device(c, precision, kernel, nullptr, 0, nullptr, nullptr, stats);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  int rc;
-  if ((rc = c->q_rays.ensure((size_t)n_rays * sizeof(rtow_ray_t))) || (rc = c->q_occ.ensure((size_t)n_rays))) return rc;
-  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n_rays * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
-  if ((rc = impl_occluded_device(c, precision, kernel, c->q_rays.p, n_rays, c->q_occ.p, nullptr, stats))) return rc;
-  HIPCHK(hipMemcpy(occluded, c->q_occ.p, (size_t)n_rays, hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-
-// Closest-point queries: the closest-hit query's contract (arguments, ordering, stats, query_map) with the point walks.
-static int impl_closest_point_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_queries, int64_t n,
-                                     void *d_hits, void *hip_stream, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n %lld outside [0, 2^31 - 64]", (long long)n);
-  if (n > 0 && (!d_queries || !d_hits)) return fail(RTOW_EINVAL, "NULL query or hit buffer");
-  if (((uintptr_t)d_queries & 15u) != 0u || ((uintptr_t)d_hits & 15u) != 0u)
-    return fail(RTOW_EINVAL, "query and hit buffers must be 16-byte aligned");
-  QueryRun q;
-  int rc;
-  if ((rc = query_begin(c, precision, kernel_req, stats, q, true))) return rc;
+  if ((rc = query_begin(c, precision, kernel_req, stats, q, k.point))) return rc;
   if (n == 0) return RTOW_OK;
 
   const int kernel = q.kernel;
-  const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
   const int32_t *map = nullptr;
-  if ((rc = query_map(c, which, &map))) return rc;
+  if (k.mapped) {
+    const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
+    if ((rc = query_map(c, which, &map))) return rc;
+  }
   const int block = q.shape.block;
-  const unsigned lds = kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;  // (BRUTE: no triangle tiles)
-  const int occ = q.strict ? rtow::pointq_occupancy_strict(kernel, block, lds, nullptr)
-                           : rtow::pointq_occupancy_fast(kernel, block, lds, nullptr);
-  return query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
-    return q.strict ? rtow::launch_pointq_strict(P, d_queries, d_hits, (uint32_t)n, map, counters, kernel, grid, block, lds,
-                                                 hip_stream)
-                    : rtow::launch_pointq_fast(P, d_queries, d_hits, (uint32_t)n, map, counters, kernel, grid, block, lds,
-                                               hip_stream);
+  const unsigned lds = k.point && kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;
+  const int build = q.strict ? 0 : 1;
+  const int occ = k.occupancy[build](kernel, block, lds, nullptr);
+  rc = query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
+    return k.launch[build](P, d_in, d_out, (uint32_t)n, map, counters, kernel, grid, block, lds, hip_stream);
   });
+  if (rc == RTOW_OK && stats && k.brute_tests_all && kernel == RTOW_KERNEL_BRUTE)
+    stats->prim_tests = (uint64_t)n * (uint64_t)c->n_prims;
+  return rc;
 }
 
-static int impl_closest_point(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
-                              rtow_point_hit_t *hits, rtow_stats_t *stats) {
+static int query_host(rtow_ctx *c, const QueryKind &k, int32_t precision, int32_t kernel, const void *in, int64_t n, void *out,
+                      rtow_stats_t *stats) {
   if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n %lld outside [0, 2^31 - 64]", (long long)n);
-  if (n > 0 && (!queries || !hits)) return fail(RTOW_EINVAL, "NULL query or hit array");
-  if (n == 0) return impl_closest_point_device(c, precision, kernel, nullptr, 0, nullptr, nullptr, stats);
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "%s %lld outside [0, 2^31 - 64]", k.count, (long long)n);
+  if (n > 0 && (!in || !out)) return fail(RTOW_EINVAL, "NULL %s or %s array", k.in_name, k.out_name);
+  if (n == 0) return query_device(c, k, precision, kernel, nullptr, 0, nullptr, nullptr, stats);
   if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
   HIPCHK(hipSetDevice(c->device));
+  DevBuf &d_out = c->*k.out_buf;
   int rc;
-  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_point_query_t))) ||
-      (rc = c->q_hits.ensure((size_t)n * sizeof(rtow_point_hit_t))))
-    return rc;
-  HIPCHK(hipMemcpy(c->q_rays.p, queries, (size_t)n * sizeof(rtow_point_query_t), hipMemcpyHostToDevice));
-  if ((rc = impl_closest_point_device(c, precision, kernel, c->q_rays.p, n, c->q_hits.p, nullptr, stats))) return rc;
-  HIPCHK(hipMemcpy(hits, c->q_hits.p, (size_t)n * sizeof(rtow_point_hit_t), hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-
-static int impl_intersect(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
-                          rtow_hit_t *hits, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n_rays < 0 || n_rays > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n_rays);
-  if (n_rays > 0 && (!rays || !hits)) return fail(RTOW_EINVAL, "NULL ray or hit array");
-  if (n_rays == 0) return impl_intersect_device(c, precision, kernel, nullptr, 0, nullptr, nullptr, stats);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  int rc;
-  if ((rc = c->q_rays.ensure((size_t)n_rays * sizeof(rtow_ray_t))) || (rc = c->q_hits.ensure((size_t)n_rays * sizeof(rtow_hit_t))))
-    return rc;
-  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n_rays * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
-  if ((rc = impl_intersect_device(c, precision, kernel, c->q_rays.p, n_rays, c->q_hits.p, nullptr, stats))) return rc;
-  HIPCHK(hipMemcpy(hits, c->q_hits.p, (size_t)n_rays * sizeof(rtow_hit_t), hipMemcpyDeviceToHost));
+  if ((rc = c->q_rays.ensure((size_t)n * k.in_bytes)) || (rc = d_out.ensure((size_t)n * k.out_bytes))) return rc;
+  HIPCHK(hipMemcpy(c->q_rays.p, in, (size_t)n * k.in_bytes, hipMemcpyHostToDevice));
+  if ((rc = query_device(c, k, precision, kernel, c->q_rays.p, n, d_out.p, nullptr, stats))) return rc;
+  HIPCHK(hipMemcpy(out, d_out.p, (size_t)n * k.out_bytes, hipMemcpyDeviceToHost));
   return RTOW_OK;
 }
 
@@ -2525,29 +2458,29 @@ int rtow_render_device_rgb8(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb8,
 int rtow_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays, void *d_hits,
                           void *hip_stream, rtow_stats_t *stats) {
   return guarded("rtow_intersect_device",
-                 [&] { return impl_intersect_device(c, precision, kernel, d_rays, n_rays, d_hits, hip_stream, stats); });
+                 [&] { return query_device(c, kIntersect, precision, kernel, d_rays, n_rays, d_hits, hip_stream, stats); });
 }
 int rtow_intersect(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, rtow_hit_t *hits,
                    rtow_stats_t *stats) {
-  return guarded("rtow_intersect", [&] { return impl_intersect(c, precision, kernel, rays, n_rays, hits, stats); });
+  return guarded("rtow_intersect", [&] { return query_host(c, kIntersect, precision, kernel, rays, n_rays, hits, stats); });
 }
 int rtow_occluded_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays,
                          void *d_occluded, void *hip_stream, rtow_stats_t *stats) {
   return guarded("rtow_occluded_device",
-                 [&] { return impl_occluded_device(c, precision, kernel, d_rays, n_rays, d_occluded, hip_stream, stats); });
+                 [&] { return query_device(c, kOccluded, precision, kernel, d_rays, n_rays, d_occluded, hip_stream, stats); });
 }
 int rtow_occluded(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, uint8_t *occluded,
                   rtow_stats_t *stats) {
-  return guarded("rtow_occluded", [&] { return impl_occluded(c, precision, kernel, rays, n_rays, occluded, stats); });
+  return guarded("rtow_occluded", [&] { return query_host(c, kOccluded, precision, kernel, rays, n_rays, occluded, stats); });
 }
 int rtow_closest_point_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_queries, int64_t n,
                               void *d_hits, void *hip_stream, rtow_stats_t *stats) {
   return guarded("rtow_closest_point_device",
-                 [&] { return impl_closest_point_device(c, precision, kernel, d_queries, n, d_hits, hip_stream, stats); });
+                 [&] { return query_device(c, kClosestPoint, precision, kernel, d_queries, n, d_hits, hip_stream, stats); });
 }
 int rtow_closest_point(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
                        rtow_point_hit_t *hits, rtow_stats_t *stats) {
-  return guarded("rtow_closest_point", [&] { return impl_closest_point(c, precision, kernel, queries, n, hits, stats); });
+  return guarded("rtow_closest_point", [&] { return query_host(c, kClosestPoint, precision, kernel, queries, n, hits, stats); });
 }
 int rtow_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
   return guarded("rtow_scene_refit", [&] { return impl_scene_refit(c, s); });

@@ -41,8 +41,7 @@ namespace {
 #ifndef RTOW_FAST_MATH
 #include "rtow_trace_reftree.h"
 #endif
-
-constexpr uint32_t kORayBytes = 64u;  // rtow_ray_t, include/rtow.h
+#include "rtow_kernel_frame.h"
 
 struct OccludeParams {
   TraceParams P;               // the scene (P.sc) and the walks' launch fields: spill, n_lanes, leaf_votes
@@ -350,7 +349,7 @@ __device__ __forceinline__ bool any_hit_stream(const DevScene &sc, V3d o, V3d d,
     const int n = sc.n_tri;
     const int base = sc.n_sph + sc.n_mov;
     if (__any(open)) {
-      const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+      const unsigned lane = lane_id();
       const uint32_t slice = (threadIdx.x >> 6) * (2u * kStreamTileBytes);
       const unsigned char *src = (const unsigned char *)sc.tri;
       const uint32_t total = (uint32_t)n * 96u;
@@ -412,46 +411,19 @@ __device__ __forceinline__ bool any_hit_stream(const DevScene &sc, V3d o, V3d d,
   return best.prim >= 0;
 }
 
-__device__ __forceinline__ unsigned o_lane_id() {
-  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
-
-// KERNEL: 1 = STREAM, 2 = BVH, 3 = GRID, 4 = BVH4, 5 = REFTREE (strict build only); LDS: as in rtow_query.h
+// KERNEL: 1 = STREAM, 2 = BVH, 3 = GRID, 4 = BVH4, 5 = REFTREE (strict build only); LDS: the scene image is staged in
+// LDS (stage_scene, rtow_kernel_frame.h)
 template <int KERNEL, bool LDS>
 __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     RTOW_OCAT(rtow_occlude_, RTOW_SUFFIX)(const OccludeParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
-  const unsigned lane = o_lane_id();
+  const unsigned lane = lane_id();
   [[maybe_unused]] const uint32_t lane_g = blockIdx.x * blockDim.x + threadIdx.x;
 
-  // ---- scene image in LDS: what the trace kernel stages for the same strategy (rtow_trace_body.h) ----
   Image<LDS> im;
-  im.g = KERNEL == 3 ? sc.gblob : sc.blob;
   [[maybe_unused]] Bvh4Reader<LDS> im4;
-  if constexpr (KERNEL == 4) {
-    im4.g = sc.blob4;
-    im4.lds_limit = sc.b4_lds_limit;
-    im4.aux_src = sc.b4_aux_src;
-    im4.aux_lds = sc.b4_aux_lds;
-    const uint4 *src = reinterpret_cast<const uint4 *>(sc.blob4);
-    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
-    const uint32_t n16 = sc.b4_lds_limit / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    if (sc.b4_aux_src < sc.blob4_bytes) {
-      const uint4 *asrc = reinterpret_cast<const uint4 *>(sc.blob4 + sc.b4_aux_src);
-      uint4 *adst = reinterpret_cast<uint4 *>(rtow_lds + sc.b4_aux_lds);
-      const uint32_t a16 = (sc.blob4_bytes - sc.b4_aux_src) / 16u;
-      for (uint32_t i = threadIdx.x; i < a16; i += blockDim.x) adst[i] = asrc[i];
-    }
-    __syncthreads();
-  } else if constexpr ((KERNEL == 2 || KERNEL == 3) && LDS) {
-    const uint4 *src = reinterpret_cast<const uint4 *>(im.g);
-    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
-    const uint32_t n16 = (KERNEL == 3 ? sc.gblob_bytes : sc.blob_bytes) / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-  }
+  stage_scene<KERNEL, LDS>(sc, im, im4);
 
   uint32_t nnode = 0u, nprim = 0u;
   const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
@@ -464,7 +436,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     real rtime = 0;
     double tmax = 0.0;
     if (in) {
-      const vd2 *r = reinterpret_cast<const vd2 *>(Q.rays + (size_t)i * kORayBytes);
+      const vd2 *r = reinterpret_cast<const vd2 *>(Q.rays + (size_t)i * kRayBytes);
       const vd2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];  // {ox, oy} {oz, time} {dx, dy} {dz, tmax}
       ro = {r0.x, r0.y, r1.x};
       rtime = r1.y;
@@ -496,12 +468,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
   }
 
   // statistics: one atomic per wave and counter
-  unsigned long long c0 = nprim, c1 = nnode;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    c0 += __shfl_down(c0, off);
-    c1 += __shfl_down(c1, off);
-  }
+  const unsigned long long c0 = wave_sum(nprim), c1 = wave_sum(nnode);
   if (lane == 0) {
     atomicAdd(&Q.counters[0], c0);
     atomicAdd(&Q.counters[1], c1);
@@ -510,89 +477,47 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 
 }  // namespace
 
-template <class Kern>
-static int o_no_static_lds(Kern k) {  // the walks address the dynamic LDS block from 0 (rtow_trace_math.h lds_read)
-  hipFuncAttributes fa;
-  const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k));
-  if (e != hipSuccess) return (int)e;
-  return fa.sharedSizeBytes == 0 ? 0 : (int)hipErrorInvalidValue;
-}
+#include "rtow_kernel_launch.h"
 
 template <int K, bool L>
-static const void *occlude_fn() {
-  return reinterpret_cast<const void *>(RTOW_OCAT(rtow_occlude_, RTOW_SUFFIX)<K, L>);
+static KernelVariant<OccludeParams> occlude_kernel(unsigned lds_bytes) {
+  return kernel_variant<RTOW_OCAT(rtow_occlude_, RTOW_SUFFIX)<K, L>, OccludeParams>(lds_bytes);
 }
 
-template <int K, bool L>
-static int launch_o(const OccludeParams &q, int grid, int block, unsigned lds_bytes, hipStream_t st) {
-  auto k = RTOW_OCAT(rtow_occlude_, RTOW_SUFFIX)<K, L>;
-  static const int lds_ok = o_no_static_lds(k);
-  if (lds_ok != 0) return lds_ok;
-  if (lds_bytes > 48 * 1024) {
-    const hipError_t e =
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
+// kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE (strict build).  `lds_bytes` > 0 selects the variant that stages
+// the image in LDS (2, 3); for 4 the image staged whole (b4_half == 0) selects the full-LDS variant, as in the render.
+static KernelVariant<OccludeParams> occlude_variant(int kernel, unsigned lds_bytes, bool b4_full) {
+  switch (kernel) {
+    case 1: return occlude_kernel<1, false>(lds_bytes);  // (LDS: the tiled triangle loop's per-wave tiles)
+    case 2: return lds_bytes > 0 ? occlude_kernel<2, true>(lds_bytes) : occlude_kernel<2, false>(0);
+    case 3: return lds_bytes > 0 ? occlude_kernel<3, true>(lds_bytes) : occlude_kernel<3, false>(0);
+    case 4: return b4_full ? occlude_kernel<4, true>(lds_bytes) : occlude_kernel<4, false>(lds_bytes);
+#ifndef RTOW_FAST_MATH
+    case 5: return occlude_kernel<5, false>(0);
+#endif
+    default: return {};
   }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds_bytes, st, q);
-  return (int)hipGetLastError();
 }
 
-// kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE (strict build); `lds_bytes` selects the variant as in rtow_query.h
+// (`map`: the query launchers' common signature; an occlusion result names no primitive)
 int RTOW_OCAT(launch_occlude_, RTOW_SUFFIX)(const TraceParams &p, const void *rays, void *occluded, uint32_t n,
-                                            unsigned long long *counters, int kernel, int grid, int block,
-                                            unsigned lds_bytes, void *stream) {
+                                            const int32_t *map, unsigned long long *counters, int kernel, int grid,
+                                            int block, unsigned lds_bytes, void *stream) {
   OccludeParams q;
   q.P = p;
   q.rays = (const unsigned char *)rays;
   q.occluded = (unsigned char *)occluded;
   q.n = n;
   q.counters = counters;
-  hipStream_t st = (hipStream_t)stream;
-  const bool lds = lds_bytes > 0;
-  switch (kernel) {
-    case 1: return launch_o<1, false>(q, grid, block, lds_bytes, st);  // (LDS: the tiled triangle loop's per-wave tiles)
-    case 2: return lds ? launch_o<2, true>(q, grid, block, lds_bytes, st) : launch_o<2, false>(q, grid, block, 0, st);
-    case 3: return lds ? launch_o<3, true>(q, grid, block, lds_bytes, st) : launch_o<3, false>(q, grid, block, 0, st);
-    case 4:
-      return p.sc.b4_half == 0u ? launch_o<4, true>(q, grid, block, lds_bytes, st)
-                                : launch_o<4, false>(q, grid, block, lds_bytes, st);
-#ifndef RTOW_FAST_MATH
-    case 5: return launch_o<5, false>(q, grid, block, 0, st);
-#endif
-    default: return (int)hipErrorInvalidValue;
-  }
+  const KernelVariant<OccludeParams> v = occlude_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
+  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
 }
 
-// Workgroups per CU that stay resident: the rule of query_occupancy_* (rtow_query.h).
+// Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h).  Both 4-wide variants have the same
+// launch bounds; the full-LDS one stands for both.
 int RTOW_OCAT(occlude_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
-  const bool lds = lds_bytes > 0;
-  const void *fn;
-  switch (kernel) {
-    case 1: fn = occlude_fn<1, false>(); break;
-    case 2: fn = lds ? occlude_fn<2, true>() : occlude_fn<2, false>(); break;
-    case 3: fn = lds ? occlude_fn<3, true>() : occlude_fn<3, false>(); break;
-    case 4: fn = occlude_fn<4, true>(); break;  // (both variants have the same launch bounds)
-#ifndef RTOW_FAST_MATH
-    case 5: fn = occlude_fn<5, false>(); break;
-#endif
-    default: return -1;
-  }
-  if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
-  if (fa.sharedSizeBytes != 0) return -1;
-  const int regs = fa.numRegs > 0 ? fa.numRegs : 128;
-  if (vgprs) *vgprs = regs;
-  const int alloc = ((regs + 7) / 8) * 8;
-  int waves_per_simd = 512 / alloc;
-  if (waves_per_simd > 8) waves_per_simd = 8;
-  if (waves_per_simd < 1) waves_per_simd = 1;
-  int nb = (waves_per_simd * 4) / (block / 64);
-  if (lds_bytes > 0) {
-    const int by_lds = (int)((160u * 1024u) / lds_bytes);
-    if (by_lds < nb) nb = by_lds;
-  }
-  return nb < 1 ? 1 : nb;
+  const KernelVariant<OccludeParams> v = occlude_variant(kernel, lds_bytes, true);
+  return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }
 
 }  // namespace rtow

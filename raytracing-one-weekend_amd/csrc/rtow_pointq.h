@@ -53,6 +53,7 @@ namespace {
 #include "rtow_trace_stamps.h"
 #include "rtow_trace_bvh.h"
 #include "rtow_trace_bvh4.h"
+#include "rtow_kernel_frame.h"
 
 constexpr uint32_t kPQueryBytes = 48u, kPHitBytes = 48u;  // rtow_point_query_t, rtow_point_hit_t (include/rtow.h)
 
@@ -430,45 +431,17 @@ __device__ __forceinline__ void closest_bvh4(const Bvh4Reader<FULL> &im, const D
   }
 }
 
-__device__ __forceinline__ unsigned p_lane_id() {
-  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
-
-// KERNEL: 1 = BRUTE, 2 = BVH, 4 = BVH4; LDS: as in rtow_query.h
+// KERNEL: 1 = BRUTE, 2 = BVH, 4 = BVH4; LDS: the scene image is staged in LDS (stage_scene, rtow_kernel_frame.h)
 template <int KERNEL, bool LDS>
 __global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_PCAT(rtow_pointq_, RTOW_SUFFIX)(const PointParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
-  const unsigned lane = p_lane_id();
+  const unsigned lane = lane_id();
   [[maybe_unused]] const uint32_t lane_g = blockIdx.x * blockDim.x + threadIdx.x;
 
-  // ---- scene image in LDS: what the trace kernel stages for the same strategy (rtow_trace_body.h) ----
   Image<LDS> im;
-  im.g = sc.blob;
   [[maybe_unused]] Bvh4Reader<LDS> im4;
-  if constexpr (KERNEL == 4) {
-    im4.g = sc.blob4;
-    im4.lds_limit = sc.b4_lds_limit;
-    im4.aux_src = sc.b4_aux_src;
-    im4.aux_lds = sc.b4_aux_lds;
-    const uint4 *src = reinterpret_cast<const uint4 *>(sc.blob4);
-    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
-    const uint32_t n16 = sc.b4_lds_limit / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    if (sc.b4_aux_src < sc.blob4_bytes) {
-      const uint4 *asrc = reinterpret_cast<const uint4 *>(sc.blob4 + sc.b4_aux_src);
-      uint4 *adst = reinterpret_cast<uint4 *>(rtow_lds + sc.b4_aux_lds);
-      const uint32_t a16 = (sc.blob4_bytes - sc.b4_aux_src) / 16u;
-      for (uint32_t i = threadIdx.x; i < a16; i += blockDim.x) adst[i] = asrc[i];
-    }
-    __syncthreads();
-  } else if constexpr (KERNEL == 2 && LDS) {
-    const uint4 *src = reinterpret_cast<const uint4 *>(im.g);
-    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
-    const uint32_t n16 = sc.blob_bytes / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-  }
+  stage_scene<KERNEL, LDS>(sc, im, im4);
 
   uint32_t nnode = 0u, nprim = 0u;
   const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
@@ -535,12 +508,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_PCAT(rtow_point
   }
 
   // statistics: one atomic per wave and counter
-  unsigned long long c0 = nprim, c1 = nnode;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    c0 += __shfl_down(c0, off);
-    c1 += __shfl_down(c1, off);
-  }
+  const unsigned long long c0 = wave_sum(nprim), c1 = wave_sum(nnode);
   if (lane == 0) {
     atomicAdd(&Q.counters[0], c0);
     atomicAdd(&Q.counters[1], c1);
@@ -549,35 +517,24 @@ __global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_PCAT(rtow_point
 
 }  // namespace
 
-template <class Kern>
-static int p_no_static_lds(Kern k) {  // the walks address the dynamic LDS block from 0 (rtow_trace_math.h lds_read)
-  hipFuncAttributes fa;
-  const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k));
-  if (e != hipSuccess) return (int)e;
-  return fa.sharedSizeBytes == 0 ? 0 : (int)hipErrorInvalidValue;
-}
+#include "rtow_kernel_launch.h"
 
 template <int K, bool L>
-static const void *pointq_fn() {
-  return reinterpret_cast<const void *>(RTOW_PCAT(rtow_pointq_, RTOW_SUFFIX)<K, L>);
-}
-
-template <int K, bool L>
-static int launch_p(const PointParams &q, int grid, int block, unsigned lds_bytes, hipStream_t st) {
-  auto k = RTOW_PCAT(rtow_pointq_, RTOW_SUFFIX)<K, L>;
-  static const int lds_ok = p_no_static_lds(k);
-  if (lds_ok != 0) return lds_ok;
-  if (lds_bytes > 48 * 1024) {
-    const hipError_t e =
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds_bytes, st, q);
-  return (int)hipGetLastError();
+static KernelVariant<PointParams> pointq_kernel(unsigned lds_bytes) {
+  return kernel_variant<RTOW_PCAT(rtow_pointq_, RTOW_SUFFIX)<K, L>, PointParams>(lds_bytes);
 }
 
 // kernel: 1 BRUTE, 2 BVH, 4 BVH4.  `lds_bytes` > 0 selects the BVH variant that stages the image in LDS; for 4 the image
 // staged whole (b4_half == 0) selects the full-LDS variant, as in the render.  BRUTE uses no LDS.
+static KernelVariant<PointParams> pointq_variant(int kernel, unsigned lds_bytes, bool b4_full) {
+  switch (kernel) {
+    case 1: return pointq_kernel<1, false>(0);
+    case 2: return lds_bytes > 0 ? pointq_kernel<2, true>(lds_bytes) : pointq_kernel<2, false>(0);
+    case 4: return b4_full ? pointq_kernel<4, true>(lds_bytes) : pointq_kernel<4, false>(lds_bytes);
+    default: return {};
+  }
+}
+
 int RTOW_PCAT(launch_pointq_, RTOW_SUFFIX)(const TraceParams &p, const void *queries, void *hits, uint32_t n,
                                            const int32_t *map, unsigned long long *counters, int kernel, int grid,
                                            int block, unsigned lds_bytes, void *stream) {
@@ -588,44 +545,15 @@ int RTOW_PCAT(launch_pointq_, RTOW_SUFFIX)(const TraceParams &p, const void *que
   q.n = n;
   q.map = map;
   q.counters = counters;
-  hipStream_t st = (hipStream_t)stream;
-  const bool lds = lds_bytes > 0;
-  switch (kernel) {
-    case 1: return launch_p<1, false>(q, grid, block, 0, st);
-    case 2: return lds ? launch_p<2, true>(q, grid, block, lds_bytes, st) : launch_p<2, false>(q, grid, block, 0, st);
-    case 4:
-      return p.sc.b4_half == 0u ? launch_p<4, true>(q, grid, block, lds_bytes, st)
-                                : launch_p<4, false>(q, grid, block, lds_bytes, st);
-    default: return (int)hipErrorInvalidValue;
-  }
+  const KernelVariant<PointParams> v = pointq_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
+  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
 }
 
-// Workgroups per CU that stay resident: the rule of query_occupancy_* (rtow_query.h).
+// Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h).  Both 4-wide variants have the same
+// launch bounds; the full-LDS one stands for both.
 int RTOW_PCAT(pointq_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
-  const bool lds = lds_bytes > 0;
-  const void *fn;
-  switch (kernel) {
-    case 1: fn = pointq_fn<1, false>(); break;
-    case 2: fn = lds ? pointq_fn<2, true>() : pointq_fn<2, false>(); break;
-    case 4: fn = pointq_fn<4, true>(); break;  // (both variants have the same launch bounds)
-    default: return -1;
-  }
-  if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
-  if (fa.sharedSizeBytes != 0) return -1;
-  const int regs = fa.numRegs > 0 ? fa.numRegs : 128;
-  if (vgprs) *vgprs = regs;
-  const int alloc = ((regs + 7) / 8) * 8;
-  int waves_per_simd = 512 / alloc;
-  if (waves_per_simd > 8) waves_per_simd = 8;
-  if (waves_per_simd < 1) waves_per_simd = 1;
-  int nb = (waves_per_simd * 4) / (block / 64);
-  if (lds_bytes > 0) {
-    const int by_lds = (int)((160u * 1024u) / lds_bytes);
-    if (by_lds < nb) nb = by_lds;
-  }
-  return nb < 1 ? 1 : nb;
+  const KernelVariant<PointParams> v = pointq_variant(kernel, lds_bytes, true);
+  return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }
 
 }  // namespace rtow

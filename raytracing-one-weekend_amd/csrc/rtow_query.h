@@ -43,9 +43,9 @@ namespace {
 #ifndef RTOW_FAST_MATH
 #include "rtow_trace_reftree.h"
 #endif
+#include "rtow_kernel_frame.h"
 
-// The layouts of rtow_ray_t (64 B) and rtow_hit_t (72 B), include/rtow.h.
-constexpr uint32_t kRayBytes = 64u, kHitBytes = 72u;
+constexpr uint32_t kHitBytes = 72u;  // rtow_hit_t, include/rtow.h
 
 struct QueryParams {
   TraceParams P;               // the scene (P.sc) and the walks' launch fields: spill, n_lanes, leaf_votes, walk_max_open
@@ -68,10 +68,6 @@ __device__ __forceinline__ double plus_zero(double v) {
   return __longlong_as_double((long long)(b == 0x8000000000000000ull ? 0ull : b));
 }
 
-__device__ __forceinline__ unsigned q_lane_id() {
-  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
-
 // KERNEL: 1 = STREAM, 2 = BVH, 3 = GRID, 4 = BVH4, 5 = REFTREE (strict build only); LDS: the scene image is staged in
 // LDS (2 and 3; for 4: the whole image, else the top of its tree — the traversal stack is in LDS either way)
 template <int KERNEL, bool LDS>
@@ -79,36 +75,12 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     RTOW_QCAT(rtow_query_, RTOW_SUFFIX)(const QueryParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
-  const unsigned lane = q_lane_id();
+  const unsigned lane = lane_id();
   [[maybe_unused]] const uint32_t lane_g = blockIdx.x * blockDim.x + threadIdx.x;
 
-  // ---- scene image in LDS: what the trace kernel stages for the same strategy (rtow_trace_body.h) ----
   Image<LDS> im;
-  im.g = KERNEL == 3 ? sc.gblob : sc.blob;
   [[maybe_unused]] Bvh4Reader<LDS> im4;
-  if constexpr (KERNEL == 4) {
-    im4.g = sc.blob4;
-    im4.lds_limit = sc.b4_lds_limit;
-    im4.aux_src = sc.b4_aux_src;
-    im4.aux_lds = sc.b4_aux_lds;
-    const uint4 *src = reinterpret_cast<const uint4 *>(sc.blob4);
-    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
-    const uint32_t n16 = sc.b4_lds_limit / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    if (sc.b4_aux_src < sc.blob4_bytes) {
-      const uint4 *asrc = reinterpret_cast<const uint4 *>(sc.blob4 + sc.b4_aux_src);
-      uint4 *adst = reinterpret_cast<uint4 *>(rtow_lds + sc.b4_aux_lds);
-      const uint32_t a16 = (sc.blob4_bytes - sc.b4_aux_src) / 16u;
-      for (uint32_t i = threadIdx.x; i < a16; i += blockDim.x) adst[i] = asrc[i];
-    }
-    __syncthreads();
-  } else if constexpr ((KERNEL == 2 || KERNEL == 3) && LDS) {
-    const uint4 *src = reinterpret_cast<const uint4 *>(im.g);
-    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
-    const uint32_t n16 = (KERNEL == 3 ? sc.gblob_bytes : sc.blob_bytes) / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-  }
+  stage_scene<KERNEL, LDS>(sc, im, im4);
 
   uint32_t nnode = 0u, nprim = 0u;
   Stamps<false> stamps;
@@ -237,12 +209,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
   }
 
   // statistics: one atomic per wave and counter
-  unsigned long long c0 = nprim, c1 = nnode;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    c0 += __shfl_down(c0, off);
-    c1 += __shfl_down(c1, off);
-  }
+  const unsigned long long c0 = wave_sum(nprim), c1 = wave_sum(nnode);
   if (lane == 0) {
     atomicAdd(&Q.counters[0], c0);
     atomicAdd(&Q.counters[1], c1);
@@ -251,35 +218,28 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 
 }  // namespace
 
-template <class Kern>
-static int q_no_static_lds(Kern k) {  // the walks address the dynamic LDS block from 0 (rtow_trace_math.h lds_read)
-  hipFuncAttributes fa;
-  const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k));
-  if (e != hipSuccess) return (int)e;
-  return fa.sharedSizeBytes == 0 ? 0 : (int)hipErrorInvalidValue;
-}
-
-template <int K, bool L>
-static const void *query_fn() {
-  return reinterpret_cast<const void *>(RTOW_QCAT(rtow_query_, RTOW_SUFFIX)<K, L>);
-}
-
-template <int K, bool L>
-static int launch_q(const QueryParams &q, int grid, int block, unsigned lds_bytes, hipStream_t st) {
-  auto k = RTOW_QCAT(rtow_query_, RTOW_SUFFIX)<K, L>;
-  static const int lds_ok = q_no_static_lds(k);
-  if (lds_ok != 0) return lds_ok;
-  if (lds_bytes > 48 * 1024) {
-    const hipError_t e =
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds_bytes, st, q);
-  return (int)hipGetLastError();
-}
+#include "rtow_kernel_launch.h"
 
 // kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE (strict build).  `lds_bytes` > 0 selects the variant that stages
 // the image in LDS (2, 3); for 4 the image staged whole (b4_half == 0) selects the full-LDS variant, as in the render.
+template <int K, bool L>
+static KernelVariant<QueryParams> query_kernel(unsigned lds_bytes) {
+  return kernel_variant<RTOW_QCAT(rtow_query_, RTOW_SUFFIX)<K, L>, QueryParams>(lds_bytes);
+}
+
+static KernelVariant<QueryParams> query_variant(int kernel, unsigned lds_bytes, bool b4_full) {
+  switch (kernel) {
+    case 1: return query_kernel<1, false>(lds_bytes);  // (LDS: the tiled triangle loop's per-wave tiles)
+    case 2: return lds_bytes > 0 ? query_kernel<2, true>(lds_bytes) : query_kernel<2, false>(0);
+    case 3: return lds_bytes > 0 ? query_kernel<3, true>(lds_bytes) : query_kernel<3, false>(0);
+    case 4: return b4_full ? query_kernel<4, true>(lds_bytes) : query_kernel<4, false>(lds_bytes);
+#ifndef RTOW_FAST_MATH
+    case 5: return query_kernel<5, false>(0);
+#endif
+    default: return {};
+  }
+}
+
 int RTOW_QCAT(launch_query_, RTOW_SUFFIX)(const TraceParams &p, const void *rays, void *hits, uint32_t n,
                                           const int32_t *map, unsigned long long *counters, int kernel, int grid,
                                           int block, unsigned lds_bytes, void *stream) {
@@ -290,53 +250,15 @@ int RTOW_QCAT(launch_query_, RTOW_SUFFIX)(const TraceParams &p, const void *rays
   q.n = n;
   q.map = map;
   q.counters = counters;
-  hipStream_t st = (hipStream_t)stream;
-  const bool lds = lds_bytes > 0;
-  switch (kernel) {
-    case 1: return launch_q<1, false>(q, grid, block, lds_bytes, st);  // (LDS: the tiled triangle loop's per-wave tiles)
-    case 2: return lds ? launch_q<2, true>(q, grid, block, lds_bytes, st) : launch_q<2, false>(q, grid, block, 0, st);
-    case 3: return lds ? launch_q<3, true>(q, grid, block, lds_bytes, st) : launch_q<3, false>(q, grid, block, 0, st);
-    case 4:
-      return p.sc.b4_half == 0u ? launch_q<4, true>(q, grid, block, lds_bytes, st)
-                                : launch_q<4, false>(q, grid, block, lds_bytes, st);
-#ifndef RTOW_FAST_MATH
-    case 5: return launch_q<5, false>(q, grid, block, 0, st);
-#endif
-    default: return (int)hipErrorInvalidValue;
-  }
+  const KernelVariant<QueryParams> v = query_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
+  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
 }
 
-// Workgroups per CU that stay resident (the rule of trace_occupancy_*, rtow_trace_body.h): min over the register file
-// (512 VGPRs per SIMD lane in granules of 8, at most 8 waves per SIMD), the four SIMDs and the 160 KiB of LDS.
+// Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h).  Both 4-wide variants have the same
+// launch bounds; the full-LDS one stands for both.
 int RTOW_QCAT(query_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
-  const bool lds = lds_bytes > 0;
-  const void *fn;
-  switch (kernel) {
-    case 1: fn = query_fn<1, false>(); break;
-    case 2: fn = lds ? query_fn<2, true>() : query_fn<2, false>(); break;
-    case 3: fn = lds ? query_fn<3, true>() : query_fn<3, false>(); break;
-    case 4: fn = query_fn<4, true>(); break;  // (both variants have the same launch bounds)
-#ifndef RTOW_FAST_MATH
-    case 5: fn = query_fn<5, false>(); break;
-#endif
-    default: return -1;
-  }
-  if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
-  if (fa.sharedSizeBytes != 0) return -1;
-  const int regs = fa.numRegs > 0 ? fa.numRegs : 128;
-  if (vgprs) *vgprs = regs;
-  const int alloc = ((regs + 7) / 8) * 8;
-  int waves_per_simd = 512 / alloc;
-  if (waves_per_simd > 8) waves_per_simd = 8;
-  if (waves_per_simd < 1) waves_per_simd = 1;
-  int nb = (waves_per_simd * 4) / (block / 64);
-  if (lds_bytes > 0) {
-    const int by_lds = (int)((160u * 1024u) / lds_bytes);
-    if (by_lds < nb) nb = by_lds;
-  }
-  return nb < 1 ? 1 : nb;
+  const KernelVariant<QueryParams> v = query_variant(kernel, lds_bytes, true);
+  return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }
 
 }  // namespace rtow

@@ -73,6 +73,7 @@ namespace {
 #ifndef RTOW_FAST_MATH
 #include "rtow_trace_reftree.h"
 #endif
+#include "rtow_kernel_frame.h"
 
 // --------------------------------------------------------------- the kernel ---
 // n / d for a divisor fixed per launch: q = (((n - t) >> 1) + t) >> shift, t = mulhi(n, magic)
@@ -83,10 +84,6 @@ __device__ __forceinline__ uint32_t fastdiv(uint32_t n, FastDiv f) {
 }
 
 constexpr uint32_t kItemBatch = 64;  // work items fetched per global atomic (per wave)
-
-__device__ __forceinline__ unsigned lane_id() {
-  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
 
 // cross-lane reads (ds_bpermute: lane i receives the value of lane src_i; all lanes active)
 __device__ __forceinline__ uint32_t lane_read(uint32_t src, uint32_t v) {
@@ -102,9 +99,6 @@ __device__ __forceinline__ double wave_bcast_f64(double v, int src_lane) {  // s
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, src_lane);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), src_lane);
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
 // ---- work items ------------------------------------------------------------------------------
@@ -291,32 +285,8 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
   const uint32_t npix_local = (uint32_t)P.local_rows * (uint32_t)P.W;
 
   Image<LDS> im;
-  im.g = KERNEL == 3 ? sc.gblob : sc.blob;
   [[maybe_unused]] Bvh4Reader<LDS> im4;  // LDS: the whole image is staged; otherwise the top of the tree
-  if constexpr (KERNEL == 4) {
-    im4.g = sc.blob4;
-    im4.lds_limit = sc.b4_lds_limit;
-    im4.aux_src = sc.b4_aux_src;
-    im4.aux_lds = sc.b4_aux_lds;
-    const uint4 *src = reinterpret_cast<const uint4 *>(sc.blob4);
-    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
-    const uint32_t n16 = sc.b4_lds_limit / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    if (sc.b4_aux_src < sc.blob4_bytes) {  // the end of the image (materials, material indices): 16-byte aligned sections
-      const uint4 *asrc = reinterpret_cast<const uint4 *>(sc.blob4 + sc.b4_aux_src);
-      uint4 *adst = reinterpret_cast<uint4 *>(rtow_lds + sc.b4_aux_lds);
-      const uint32_t a16 = (sc.blob4_bytes - sc.b4_aux_src) / 16u;
-      for (uint32_t i = threadIdx.x; i < a16; i += blockDim.x) adst[i] = asrc[i];
-    }
-    __syncthreads();
-  } else if constexpr (KERNEL >= 2 && LDS) {
-    // stage the scene image: coalesced 16-byte loads, 16-byte LDS stores
-    const uint4 *src = reinterpret_cast<const uint4 *>(im.g);
-    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
-    const uint32_t n16 = (KERNEL == 3 ? sc.gblob_bytes : sc.blob_bytes) / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-  }
+  stage_scene<KERNEL, LDS>(sc, im, im4);
 
   // per-lane state
   bool done = false;
@@ -993,122 +963,57 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 
 }  // namespace
 
-// The trace kernels address the dynamic LDS block from 0 (lds_read / lds_write, rtow_trace_bvh4.h): an instantiation
-// that had static LDS of its own would read the wrong bytes.  Checked once per instantiation, on the kernel that is
-// actually launched (the occupancy query below looks at one representative only).
-template <class Kern>
-static int no_static_lds(Kern k) {
-  hipFuncAttributes fa;
-  const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k));
-  if (e != hipSuccess) return (int)e;
-  return fa.sharedSizeBytes == 0 ? 0 : (int)hipErrorInvalidValue;
-}
+#include "rtow_kernel_launch.h"
 
-template <bool L, bool S>
-static int launch_sm4(const TraceParams &p, int grid, int block, unsigned lds_bytes, hipStream_t st) {
-  auto k = RTOW_CAT(rtow_trace4_, RTOW_SUFFIX)<L, S>;
-  static const int lds_ok = no_static_lds(k);
-  if (lds_ok != 0) return lds_ok;
-  if (lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds_bytes, st, p);
-  return (int)hipGetLastError();
-}
-
-// kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4; +16 = diagnostic region stamps (LDS variants only)
 template <int K, bool L, bool S, int SPEC = 0>
-static int launch_one(const TraceParams &p, int grid, int block, unsigned lds_bytes, hipStream_t st) {
-  auto k = RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<K, L, S, SPEC>;
-  static const int lds_ok = no_static_lds(k);  // (one static per instantiation)
-  if (lds_ok != 0) return lds_ok;
-  if (lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
+static KernelVariant<TraceParams> trace_kernel(unsigned lds_bytes) {
+  return kernel_variant<RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<K, L, S, SPEC>, TraceParams>(lds_bytes);
+}
+template <bool L, bool S>
+static KernelVariant<TraceParams> trace4_kernel(unsigned lds_bytes) {
+  return kernel_variant<RTOW_CAT(rtow_trace4_, RTOW_SUFFIX)<L, S>, TraceParams>(lds_bytes);
+}
+
+// kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE; +16 = diagnostic region stamps (LDS variants only).  `lds_bytes`
+// > 0 selects the variant that stages the image in LDS (2, 3); `spec`: the GRID kernel's scene-class specialisation.
+// BVH4: `b4_full` (binary32 nodes <=> the image staged whole) selects the full-LDS variant, `b4_trips` the
+// trip-structured form (default; RTOW_BVH4_SM selects the state machine).
+static KernelVariant<TraceParams> trace_variant(int kernel, unsigned lds_bytes, uint32_t spec, bool b4_full,
+                                                bool b4_trips) {
+  const bool lds = lds_bytes > 0;
+  switch (kernel) {
+    case 1: return trace_kernel<1, false, false>(lds_bytes);  // (LDS: the tiled triangle loop's per-wave tiles)
+    case 2: return lds ? trace_kernel<2, true, false>(lds_bytes) : trace_kernel<2, false, false>(0);
+    case 3:
+      if (lds && spec == kSpecStaticSpheres) return trace_kernel<3, true, false, 1>(lds_bytes);
+      if (lds && spec == kSpecMovingSpheres) return trace_kernel<3, true, false, 2>(lds_bytes);
+      return lds ? trace_kernel<3, true, false>(lds_bytes) : trace_kernel<3, false, false>(0);
+    case 4:
+      if (b4_trips) return b4_full ? trace_kernel<4, true, false>(lds_bytes) : trace_kernel<4, false, false>(lds_bytes);
+      return b4_full ? trace4_kernel<true, false>(lds_bytes) : trace4_kernel<false, false>(lds_bytes);
+    case 4 + 16:
+      if (b4_trips) return b4_full ? trace_kernel<4, true, true>(lds_bytes) : trace_kernel<4, false, true>(lds_bytes);
+      return b4_full ? trace4_kernel<true, true>(lds_bytes) : trace4_kernel<false, true>(lds_bytes);
+#ifndef RTOW_FAST_MATH
+    case 5: return trace_kernel<5, false, false>(0);  // the reference's tree: strict build only
+#endif
+    case 2 + 16: return trace_kernel<2, true, true>(lds_bytes);
+    case 3 + 16: return trace_kernel<3, true, true>(lds_bytes);
+    default: return {};
   }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds_bytes, st, p);
-  return (int)hipGetLastError();
 }
 
 int RTOW_CAT(launch_trace_, RTOW_SUFFIX)(const TraceParams &p, int kernel, int grid, int block,
                                          unsigned lds_bytes, void *stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool lds = lds_bytes > 0;
-  switch (kernel) {
-    case 1: return launch_one<1, false, false>(p, grid, block, lds_bytes, st);  // (LDS: the tiled triangle loop's per-wave tiles)
-    case 2: return lds ? launch_one<2, true, false>(p, grid, block, lds_bytes, st)
-                       : launch_one<2, false, false>(p, grid, block, 0, st);
-    case 3:
-      if (lds && p.spec == kSpecStaticSpheres) return launch_one<3, true, false, 1>(p, grid, block, lds_bytes, st);
-      if (lds && p.spec == kSpecMovingSpheres) return launch_one<3, true, false, 2>(p, grid, block, lds_bytes, st);
-      return lds ? launch_one<3, true, false>(p, grid, block, lds_bytes, st)
-                 : launch_one<3, false, false>(p, grid, block, 0, st);
-    case 4:
-    case 4 + 16: {
-      const bool full = p.sc.b4_half == 0u, stamps = kernel == 4 + 16;  // (binary32 nodes <=> staged whole)
-      if (p.b4_trips)  // the trip-structured form (default); RTOW_BVH4_SM selects the state machine
-        return full ? (stamps ? launch_one<4, true, true>(p, grid, block, lds_bytes, st)
-                              : launch_one<4, true, false>(p, grid, block, lds_bytes, st))
-                    : (stamps ? launch_one<4, false, true>(p, grid, block, lds_bytes, st)
-                              : launch_one<4, false, false>(p, grid, block, lds_bytes, st));
-      return full ? (stamps ? launch_sm4<true, true>(p, grid, block, lds_bytes, st)
-                            : launch_sm4<true, false>(p, grid, block, lds_bytes, st))
-                  : (stamps ? launch_sm4<false, true>(p, grid, block, lds_bytes, st)
-                            : launch_sm4<false, false>(p, grid, block, lds_bytes, st));
-    }
-#ifndef RTOW_FAST_MATH
-    case 5: return launch_one<5, false, false>(p, grid, block, 0, st);  // the reference's tree: strict build only
-#endif
-    case 2 + 16: return launch_one<2, true, true>(p, grid, block, lds_bytes, st);
-    case 3 + 16: return launch_one<3, true, true>(p, grid, block, lds_bytes, st);
-    default: return (int)hipErrorInvalidValue;
-  }
+  const KernelVariant<TraceParams> v = trace_variant(kernel, lds_bytes, p.spec, p.sc.b4_half == 0u, p.b4_trips != 0u);
+  return v.fn ? v.launch(p, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
 }
 
-// Workgroups per CU that stay resident: min over the register file (512 VGPRs per
-// SIMD lane, allocated in granules of 8), the 32-wave CU limit and the 160 KiB of LDS.
-// (The runtime's occupancy query ignores LDS above 64 KiB per CU on this stack; a grid
-// that turns out larger than resident only queues the surplus workgroups, which then
-// find the work queue empty — there is no inter-workgroup dependency.)
+// Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h), by the unspecialised kernel of the
+// strategy.  Both 4-wide variants have the same launch bounds; the full-LDS one stands for both.
 int RTOW_CAT(trace_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes) {
-  const void *fn;
-  const bool lds = lds_bytes > 0;
-#ifndef RTOW_FAST_MATH
-  if (kernel == 5)
-    fn = reinterpret_cast<const void *>(RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<5, false, false>);
-  else
-#endif
-  if (kernel == 4)  // (both variants have the same launch bounds; the full-LDS one stands for both)
-    fn = reinterpret_cast<const void *>(RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<4, true, false>);
-  else if (kernel == 3)
-    fn = lds ? reinterpret_cast<const void *>(RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<3, true, false>)
-             : reinterpret_cast<const void *>(RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<3, false, false>);
-  else if (kernel == 2)
-    fn = lds ? reinterpret_cast<const void *>(RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<2, true, false>)
-             : reinterpret_cast<const void *>(RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<2, false, false>);
-  else
-    fn = reinterpret_cast<const void *>(RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<1, false, false>);
-  if (lds_bytes > 48 * 1024)
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
-  if (fa.sharedSizeBytes != 0) return -1;  // (the 4-wide walk addresses the dynamic LDS block from 0, rtow_trace_bvh4.h lds_read)
-  const int regs = fa.numRegs > 0 ? fa.numRegs : 128;
-  const int alloc = ((regs + 7) / 8) * 8;
-  int waves_per_simd = 512 / alloc;
-  if (waves_per_simd > 8) waves_per_simd = 8;
-  if (waves_per_simd < 1) waves_per_simd = 1;
-  const int waves_per_block = block / 64;
-  int nb = (waves_per_simd * 4) / waves_per_block;
-  if (lds_bytes > 0) {
-    const int by_lds = (int)((160u * 1024u) / lds_bytes);
-    if (by_lds < nb) nb = by_lds;
-  }
-  if (nb < 1) nb = 1;
-  return nb;
+  const KernelVariant<TraceParams> v = trace_variant(kernel, lds_bytes, kSpecGeneric, true, true);
+  return resident_blocks(v.fn, block, v.lds_bytes, nullptr);
 }
 
 }  // namespace rtow

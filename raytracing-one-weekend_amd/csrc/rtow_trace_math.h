@@ -159,7 +159,7 @@ typedef _Float16 vh4 __attribute__((ext_vector_type(4)));   // four binary16 pla
 #define RTOW_AS_LDS __attribute__((address_space(3)))
 #define RTOW_AS_GLB __attribute__((address_space(1)))
 // `off` IS the LDS address: the trace kernels have no static LDS, so the dynamic block (rtow_lds) starts at 0 —
-// checked on the host (trace_occupancy_*: hipFuncAttributes::sharedSizeBytes == 0).  Written as `rtow_lds + off` the
+// checked on the host (rtow_kernel_launch.h: hipFuncAttributes::sharedSizeBytes == 0).  Written as `rtow_lds + off` the
 // compiler kept a `v_add_u32 v, 0, v` per access (the symbol's address, resolved too late to fold): nine per node
 // step of the 4-wide walk.
 template <class T>

@@ -36,23 +36,7 @@ __global__ void __launch_bounds__(1024) RTOW_CAT(rtow_trace4_, RTOW_SUFFIX)(cons
   const uint32_t kRestartVotes = P.sm4_restart, kScatterVotes = P.sm4_scatter, kLeafVotes = P.sm4_leaf;  // (wave-uniform)
 
   Bvh4Reader<FULL> im;
-  im.g = sc.blob4;
-  im.lds_limit = sc.b4_lds_limit;
-  im.aux_src = sc.b4_aux_src;
-  im.aux_lds = sc.b4_aux_lds;
-  {
-    const uint4 *src = reinterpret_cast<const uint4 *>(sc.blob4);
-    uint4 *dst = reinterpret_cast<uint4 *>(rtow_lds);
-    const uint32_t n16 = sc.b4_lds_limit / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    if (sc.b4_aux_src < sc.blob4_bytes) {  // the end of the image (materials, material indices)
-      const uint4 *asrc = reinterpret_cast<const uint4 *>(sc.blob4 + sc.b4_aux_src);
-      uint4 *adst = reinterpret_cast<uint4 *>(rtow_lds + sc.b4_aux_lds);
-      const uint32_t a16 = (sc.blob4_bytes - sc.b4_aux_src) / 16u;
-      for (uint32_t i = threadIdx.x; i < a16; i += blockDim.x) adst[i] = asrc[i];
-    }
-    __syncthreads();
-  }
+  stage_bvh4(sc, im);
 
   // ---- per-lane state ---------------------------------------------------------------------
   enum : uint32_t { PH_ITEM = 0, PH_SAMPLE, PH_START, PH_WALK, PH_HIT, PH_MISS, PH_DEAD };
