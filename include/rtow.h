@@ -306,6 +306,16 @@ int rtow_debug_counters(rtow_ctx *ctx, unsigned long long *out48);
  * without a GPU). */
 int rtow_debug_schedule(rtow_ctx *ctx, const rtow_config_t *cfg, uint32_t *out_pairs, int32_t capacity_pairs);
 
+/* Diagnostic only (pure host arithmetic, usable without a GPU): the order in which the work queue of a render of
+ * `cfg` of `scene` runs its 64-pixel tiles.  table_out[queue position] = tile (row-major over this rank's tile rows;
+ * the queue is consumed from its far end, so position 0 runs LAST), empty_out[tile] = 1 when no ray the camera can
+ * generate through the tile's pixels (any jitter, any lens point, any shutter time) can reach a primitive.  The empty
+ * tiles hold the positions [0, *n_empty): they are traced last.  RTOW_TILE_ORDER=0 in the environment switches the
+ * classification off (no tile is reported empty, the order is that of the rows alone).  Returns the number of tiles
+ * (0 when the launch is not tiled) and writes at most `capacity` entries of each array. */
+int rtow_debug_tile_order(const rtow_scene_t *scene, const rtow_config_t *cfg, uint32_t *table_out, unsigned char *empty_out,
+                          int32_t capacity, int32_t *n_empty, int32_t *tile_w_log2, int32_t *tile_h_log2);
+
 /* Diagnostic only: copies a resident scene image to the host (which: 0 BVH image, 1 grid image,
  * 2 / 3 the same of the RTOW_F32 build, 4 the 4-wide BVH image of a triangle mesh, 5 the 48-byte frame record
  * of the 4-wide walk: double c[3], float is[3] (binary16 planes decode as c + h * is per axis), uint32_t half

@@ -317,6 +317,9 @@ struct Knobs {
   bool stream_scalar = false;     // RTOW_STREAM_SCALAR: the STREAM kernel's triangle loop through scalar loads at every size (A/B
                                   //   against the LDS-tiled loop; rounds 1-5a)
   bool no_spec = false;           // RTOW_NO_SPEC: always the generic GRID kernel (A/B against the scene-class specialisations)
+  bool tile_order = true;         // RTOW_TILE_ORDER=0: the queue keeps the row order alone (one segment); default: the tiles through
+                                  //   which no camera ray can reach a primitive are traced last (tile_classify)
+  int empty_levels = 3;           // RTOW_EMPTY_LEVELS: levels of a tile one atomic buys in the queue's empty-tile segment (1..16)
   int tail_bound = 0;             // RTOW_TAIL_BOUND (tests only): trips of the end-of-launch protocol before a wave gives up
                                   //   its samples (0 = the structural bound); a small value forces the RTOW_EHIP path
   void read() {
@@ -362,6 +365,8 @@ struct Knobs {
     sched_chunk = std::min(std::max(geti("RTOW_SCHED_CHUNK", 10), 0), 4096);
     sched_chunk_mesh = std::min(std::max(geti("RTOW_SCHED_CHUNK_MESH", 16), 0), 4096);
     tail_bound = std::max(geti("RTOW_TAIL_BOUND", 0), 0);
+    tile_order = geti("RTOW_TILE_ORDER", 1) != 0;
+    empty_levels = std::min(std::max(geti("RTOW_EMPTY_LEVELS", 3), 1), 16);
     no_spec = std::getenv("RTOW_NO_SPEC") != nullptr;
     stream_scalar = std::getenv("RTOW_STREAM_SCALAR") != nullptr;
     if (const char *e = std::getenv("RTOW_PLOC_RADIUS")) ploc_radius = std::min(std::max(std::atoi(e), 0), 64);
@@ -409,7 +414,15 @@ struct rtow_ctx {
     std::vector<double> sg, mg, tg;
     std::vector<int32_t> pk, pi;
     bool have_order = false;
+    rtow_camera_t cam{};
   } host_scene;
+  // Queue order of the 64-pixel tiles (tile_queue_table): device table, queue position of a tile -> tile, made by the
+  // first render that needs it and kept while what it depends on stays: the resident scene (scene_gen counts uploads
+  // and refits), the image size, this rank's strips, the tile shape and the ordering knobs.
+  DevBuf tile_table;
+  long long tile_key[10] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t tile_empty = 0;       // tiles of the table's empty segment
+  long long scene_gen = 0;
   DevBuf rtree;
   bool have_rtree = false;
   PinnedArena arena;     // staging of the scene uploads
@@ -520,7 +533,7 @@ void rtow_ctx_destroy(rtow_ctx *c) {
                     &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_occ, &c->q_map[0], &c->q_map[1],
                     &c->q_map[2], &c->rf.map2, &c->rf.map4, &c->rf.par2, &c->rf.par4, &c->rf.need4, &c->rf.flags,
                     &c->rf.nbox2, &c->rf.nbox4, &c->rf.sbox4, &c->rf.pbox, &c->rf.partials, &c->rf.area, &c->rf.g_sph,
-                    &c->rf.g_mov, &c->rf.g_tri})
+                    &c->rf.g_mov, &c->rf.g_tri, &c->tile_table})
     b->release();
   for (hipEvent_t e : c->rf.ev)
     if (e) (void)hipEventDestroy(e);
@@ -686,6 +699,7 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
   c->have_scene = false;
   c->have_rtree = false;
   c->q_map_ok[0] = c->q_map_ok[1] = c->q_map_ok[2] = false;  // (the ray queries' id tables belong to the old scene)
+  c->scene_gen++;  // (the tile table belongs to the old scene)
   c->rf.ready = false;
   c->rf.refits = 0;
   c->rf.refit_ms = 0.0;
@@ -697,6 +711,7 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
     h.sg.assign(s->sphere_geom, s->sphere_geom + 4 * (size_t)s->n_spheres);
     h.mg.assign(s->moving_geom, s->moving_geom + 8 * (size_t)s->n_moving);
     h.tg.assign(s->triangle_geom, s->triangle_geom + 9 * (size_t)s->n_triangles);
+    h.cam = s->camera;
     h.have_order = s->prim_kind && s->prim_index;
     if (h.have_order) {
       for (int i = 0; i < s->n_prims; ++i) {
@@ -1241,6 +1256,182 @@ static void tile_shape(const rtow_config_t *cfg, int rows, uint32_t &th, uint32_
   }
 }
 
+// ---- queue order of the tiles ------------------------------------------------------------------------------------
+// Which of this rank's 64-pixel tiles are EMPTY: no ray the camera can generate through any of their pixels — the whole
+// jitter square of every pixel, the whole lens disk, for a moving sphere the whole shutter interval — can reach any
+// primitive.  Every sample of such a tile is exactly one segment (the sky), so the work is cheap, uniform and cannot
+// start a long path: the queue ends on it (tile_queue_table).  A hint only: it decides when a tile is traced, never
+// what is rendered, and errs to "not empty" — a camera frame that is not the reference's (horizontal along u, vertical
+// along v, the viewport straight ahead), a primitive around the lens: nothing is empty.
+//   * A primitive is its bounding sphere (c, r): a sphere itself, the ball swept by a moving sphere between the
+//     shutter's ends (centre c0 + t (c1 - c0), t in [t0, t1]), the ball around a triangle's box centre through its vertices.
+//   * The lens is folded into the radius.  A ray from the lens point o' (|o' - o| <= lens) through the viewport point
+//     P is, at the parameter s where it has depth z = s fd, the pinhole ray o -> P displaced by (o' - o)(1 - s): by at
+//     most lens for z <= 2 fd and lens (z / fd - 1) beyond.  The ray enters the sphere at a depth z_max or less (see
+//     below), so if the lens ray meets the sphere, the pinhole ray through the same viewport point meets the sphere
+//     of radius R = r + lens max(1, z_max / fd - 1).  From here on only pinhole rays and inflated spheres.
+//   * A tile is the cone around the direction through its centre that holds the directions through all of its
+//     jittered pixel positions: columns [j0, j0 + tw] / (W - 1), rows [H - i0 - th, H - i0] / (H - 1) of the viewport,
+//     half-angle asin(half diagonal / distance of the centre).  It can see the sphere when the angle between the two
+//     axes is at most asin(R / |c - o|) + that half-angle.  Per sphere the test runs over the tiles of its screen
+//     rectangle only (the tangents from the eye to its outline in the camera's two axis planes), so the cost is a
+//     few dozen operations per sphere and tile it may touch.  Radii and half-angles carry a relative slack of 1e-6:
+//     far above the rounding of this arithmetic and of the binary32 build's rays, far below a pixel.
+static void tile_classify(const rtow_ctx::HostSceneCopy &h, const rtow_config_t *cfg, uint32_t th, uint32_t tw, int rows,
+                          std::vector<unsigned char> &empty) {
+  const uint32_t tpr = (uint32_t)cfg->image_width >> tw, ntr = (uint32_t)rows >> th, nt = tpr * ntr;
+  empty.assign(nt, 0);
+  const rtow_camera_t &cam = h.cam;
+  const int W = cfg->image_width, H = cfg->image_height;
+  if (W < 2 || H < 2 || nt == 0) return;
+  auto dot3 = [](const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+  const double lenH = std::sqrt(dot3(cam.horizontal, cam.horizontal)), lenV = std::sqrt(dot3(cam.vertical, cam.vertical));
+  double mid[3];
+  for (int k = 0; k < 3; ++k) mid[k] = cam.lower_left_corner[k] + 0.5 * cam.horizontal[k] + 0.5 * cam.vertical[k] - cam.origin[k];
+  const double fd = -dot3(mid, cam.w);  // the viewport lies fd along -w
+  const double lens = std::fabs(cam.lens_radius);
+  if (!(lenH > 0.0 && lenV > 0.0 && fd > 0.0) || !std::isfinite(lenH + lenV + fd + lens)) return;
+  {  // the frame the rectangles below assume
+    const double tol = 1e-9;
+    bool ok = std::fabs(dot3(cam.u, cam.u) - 1.0) < tol && std::fabs(dot3(cam.v, cam.v) - 1.0) < tol &&
+              std::fabs(dot3(cam.w, cam.w) - 1.0) < tol && std::fabs(dot3(cam.u, cam.v)) < tol &&
+              std::fabs(dot3(cam.u, cam.w)) < tol && std::fabs(dot3(cam.v, cam.w)) < tol;
+    ok = ok && std::fabs(dot3(cam.horizontal, cam.u) - lenH) < tol * lenH && std::fabs(dot3(cam.vertical, cam.v) - lenV) < tol * lenV;
+    ok = ok && std::fabs(dot3(mid, cam.u)) < tol * fd && std::fabs(dot3(mid, cam.v)) < tol * fd;
+    if (!ok) return;
+  }
+  std::vector<int32_t> row_list((size_t)rows);
+  rtow_local_row_list(cfg, row_list.data(), rows);
+  const double wm = (double)(W - 1), hm = (double)(H - 1);
+  const double tile_w = (double)(1u << tw), tile_h = (double)(1u << th);
+  // per tile row / column: the viewport interval it covers; per tile: unit axis and sine / cosine of the half-angle
+  std::vector<double> v_lo(ntr), v_hi(ntr), axis((size_t)nt * 3), sin_b(nt), cos_b(nt);
+  const double half_diag = 0.5 * std::sqrt(tile_w * tile_w * lenH * lenH / (wm * wm) + tile_h * tile_h * lenV * lenV / (hm * hm));
+  for (uint32_t tr = 0; tr < ntr; ++tr) {
+    const double i0 = (double)row_list[(size_t)tr << th];  // (a tile never straddles two strips: its rows are consecutive)
+    v_lo[tr] = ((double)H - i0 - tile_h) / hm;
+    v_hi[tr] = ((double)H - i0) / hm;
+    for (uint32_t tc = 0; tc < tpr; ++tc) {
+      const double sc = ((double)tc + 0.5) * tile_w / wm, vc = 0.5 * (v_lo[tr] + v_hi[tr]);
+      double d[3];
+      for (int k = 0; k < 3; ++k) d[k] = cam.lower_left_corner[k] + sc * cam.horizontal[k] + vc * cam.vertical[k] - cam.origin[k];
+      const double dl = std::sqrt(dot3(d, d));
+      const size_t t = (size_t)tr * tpr + tc;
+      for (int k = 0; k < 3; ++k) axis[3 * t + k] = d[k] / dl;
+      const double sb = std::min(half_diag / dl * (1.0 + 1e-6) + 1e-9, 1.0);
+      sin_b[t] = sb;
+      cos_b[t] = std::sqrt(1.0 - sb * sb);
+    }
+  }
+  std::vector<unsigned char> seen(nt, 0);
+  bool all = false;
+  // tangent slopes x / z from the eye to the disc (p, z; R) of one axis plane, as viewport coordinates
+  auto extent = [](double p, double z, double R, double scale, double &lo, double &hi) {
+    lo = -1e300;
+    hi = 1e300;
+    if (!(z > R)) return;  // the disc reaches the lens plane: every coordinate
+    const double q = std::sqrt(std::max(p * p + z * z - R * R, 0.0));
+    lo = 0.5 + (p * q - R * z) / (z * q + p * R) * scale;
+    hi = 0.5 + (p * q + R * z) / (z * q - p * R) * scale;
+  };
+  auto mark = [&](const double *cc, double r) {
+    if (all) return;
+    if (!std::isfinite(cc[0] + cc[1] + cc[2] + r)) {
+      all = true;
+      return;
+    }
+    double rel[3];
+    for (int k = 0; k < 3; ++k) rel[k] = cc[k] - cam.origin[k];
+    const double px = dot3(rel, cam.u), py = dot3(rel, cam.v), pz = -dot3(rel, cam.w);
+    r = std::fabs(r);
+    const double dist = std::sqrt(dot3(rel, rel));
+    if (!(dist - lens > r)) {  // the lens reaches into the sphere: everything
+      all = true;
+      return;
+    }
+    // depth of the point where a lens ray enters the sphere: at most the far side, and at most the tangent length
+    // from the lens point (entry x exit = the power of the point, entry <= exit) — what keeps the ground in bounds
+    const double z_max = std::min(pz + r, std::sqrt((dist + lens) * (dist + lens) - r * r));
+    double R = r + lens * std::max(1.0, z_max / fd - 1.0);
+    R = R * (1.0 + 1e-6) + 1e-9;
+    if (pz + R <= 0.0) return;  // wholly behind the lens plane: every camera ray runs forward
+    if (!(dist > R)) {  // the eye is inside the inflated sphere: everything
+      all = true;
+      return;
+    }
+    double s0, s1, t0, t1;
+    extent(px, pz, R, fd / lenH, s0, s1);
+    extent(py, pz, R, fd / lenV, t0, t1);
+    const double c0 = std::floor(s0 * wm / tile_w) - 1.0, c1 = std::floor(s1 * wm / tile_w) + 1.0;
+    if (c1 < 0.0 || c0 > (double)(tpr - 1u)) return;
+    const uint32_t ca = (uint32_t)std::max(c0, 0.0), cb = (uint32_t)std::min(c1, (double)(tpr - 1u));
+    const double pad = tile_h / hm;  // (one tile of margin, as for the columns: the cone test decides)
+    const double sa = R / dist, csa = std::sqrt(1.0 - sa * sa);
+    const double ax[3] = {rel[0] / dist, rel[1] / dist, rel[2] / dist};
+    for (uint32_t tr = 0; tr < ntr; ++tr) {
+      if (v_hi[tr] + pad < t0 || v_lo[tr] - pad > t1) continue;
+      for (uint32_t tc = ca; tc <= cb; ++tc) {
+        const size_t t = (size_t)tr * tpr + tc;
+        if (seen[t]) continue;
+        // angle between the axes <= alpha + beta (both below a right angle)
+        const double cos_reach = csa * cos_b[t] - sa * sin_b[t];
+        if (dot3(&axis[3 * t], ax) >= cos_reach) seen[t] = 1;
+      }
+    }
+  };
+  for (size_t i = 0; i < h.sg.size() / 4; ++i) mark(&h.sg[4 * i], h.sg[4 * i + 3]);
+  for (size_t i = 0; i < h.mg.size() / 8; ++i) {
+    const double *m = &h.mg[8 * i];  // c0 xyz, c1 xyz, r: centre c0 + t (c1 - c0) for t in the shutter interval
+    double a[3], b[3], mc[3], dd = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      a[k] = m[k] + cam.t0 * (m[3 + k] - m[k]);
+      b[k] = m[k] + cam.t1 * (m[3 + k] - m[k]);
+      mc[k] = 0.5 * (a[k] + b[k]);
+      dd += (b[k] - a[k]) * (b[k] - a[k]);
+    }
+    mark(mc, std::fabs(m[6]) + 0.5 * std::sqrt(dd));
+  }
+  for (size_t i = 0; i < h.tg.size() / 9; ++i) {
+    const double *g = &h.tg[9 * i];
+    double mc[3], rr = 0.0;
+    for (int k = 0; k < 3; ++k)
+      mc[k] = 0.5 * (std::min(g[k], std::min(g[3 + k], g[6 + k])) + std::max(g[k], std::max(g[3 + k], g[6 + k])));
+    for (int q = 0; q < 3; ++q) {
+      double d2 = 0.0;
+      for (int k = 0; k < 3; ++k) d2 += (g[3 * q + k] - mc[k]) * (g[3 * q + k] - mc[k]);
+      rr = std::max(rr, d2);
+    }
+    mark(mc, std::sqrt(rr));
+  }
+  if (all) return;
+  for (uint32_t t = 0; t < nt; ++t) empty[t] = !seen[t];
+}
+
+// table[queue position of a tile] = tile (row-major over this rank's tile rows).  The queue is consumed from its far
+// end, so position 0 runs LAST.  Two segments: the empty tiles (tile_classify) at positions [0, n_empty), everything
+// else above them; inside each the row order that was the whole order before — the rows below the top band top-down
+// first (the horizon rows of an outdoor scene, its costliest), the top band (sky_rows tile rows) last — so a scene
+// with no empty tile, or `ordered` false (RTOW_TILE_ORDER=0), runs exactly as it did.
+static uint32_t tile_queue_table(const std::vector<unsigned char> &empty, bool ordered, uint32_t tpr, uint32_t ntr,
+                                 uint32_t sky_rows, std::vector<uint32_t> &table) {
+  const uint32_t nt = tpr * ntr;
+  table.resize(nt);
+  uint32_t n_empty = 0;
+  if (ordered)
+    for (uint32_t t = 0; t < nt; ++t) n_empty += empty[t] ? 1u : 0u;
+  uint32_t pe = 0, pf = n_empty;
+  for (uint32_t t = 0; t < nt; ++t) {
+    const uint32_t trq = t / tpr, tc = t - trq * tpr;
+    const uint32_t tr = trq >= sky_rows ? sky_rows + (ntr - 1u - trq) : trq;
+    const uint32_t tile = tr * tpr + tc;
+    if (ordered && empty[tile])
+      table[pe++] = tile;
+    else
+      table[pf++] = tile;
+  }
+  return n_empty;
+}
+
 static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums, void *hip_stream,
                          rtow_stats_t *stats, const LevelPlan &plan, int lvl_first, int lvl_count, int accumulate);
 
@@ -1566,9 +1757,28 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
   P.div_tpr_n = th ? (uint32_t)cfg->image_width >> tw : 1u;
   P.div_tpr = make_fastdiv(P.div_tpr_n);
   P.n_tile_rows = th ? (uint32_t)rows >> th : 1u;
-  {
-    const int eighths = c->knobs.sky_eighths;  // the top eighth of the image is traced last (RTOW_SKY_EIGHTHS: 0..8)
-    P.sky_rows = th ? P.n_tile_rows * (uint32_t)eighths / 8u : 0u;
+  P.tile_table = nullptr;
+  P.n_items_first = P.n_items;
+  P.empty_batch = 64u;
+  if (th) {
+    // the top eighth of the image is traced last (RTOW_SKY_EIGHTHS: 0..8), and behind it the tiles that see nothing
+    const uint32_t sky_rows = P.n_tile_rows * (uint32_t)c->knobs.sky_eighths / 8u;
+    const long long key[10] = {1, c->scene_gen, cfg->image_width, cfg->image_height, cfg->rank, cfg->nranks, cfg->tile_rows,
+                               (long long)th, (long long)sky_rows, c->knobs.tile_order ? 1 : 0};
+    if (std::memcmp(key, c->tile_key, sizeof key) != 0) {  // (repeated renders of a resident scene reuse the table)
+      std::vector<unsigned char> empty;
+      std::vector<uint32_t> table;
+      if (c->knobs.tile_order) tile_classify(c->host_scene, cfg, th, tw, rows, empty);
+      c->tile_empty = tile_queue_table(empty, c->knobs.tile_order, P.div_tpr_n, P.n_tile_rows, sky_rows, table);
+      if ((rc = c->tile_table.ensure(table.size() * sizeof(uint32_t)))) return rc;
+      c->tile_key[0] = -1;
+      HIPCHK(hipStreamSynchronize(st));  // (an earlier launch on this stream may still read the old table)
+      HIPCHK(hipMemcpy(c->tile_table.p, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      std::memcpy(c->tile_key, key, sizeof key);
+    }
+    P.tile_table = (const uint32_t *)c->tile_table.p;
+    P.n_items_first = P.n_items - c->tile_empty * 64u * (uint32_t)streams_now;
+    P.empty_batch = 64u * (uint32_t)c->knobs.empty_levels;
   }
   P.partials = (double *)c->partials.p;
   P.stack = (uint32_t *)c->stack.p;
@@ -2399,6 +2609,8 @@ static int impl_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
   h.sg.assign(s->sphere_geom, s->sphere_geom + 4 * (size_t)ns);
   h.mg.assign(s->moving_geom, s->moving_geom + 8 * (size_t)nm);
   h.tg.assign(s->triangle_geom, s->triangle_geom + 9 * (size_t)nt);
+  h.cam = cam;
+  c->scene_gen++;  // (geometry may have moved into tiles that were empty)
   c->have_rtree = false;
   c->q_map_ok[1] = c->q_map_ok[2] = false;  // (rebuilt from the refit's slot maps; table 0 does not move)
 
@@ -2484,6 +2696,41 @@ int rtow_closest_point(rtow_ctx *c, int32_t precision, int32_t kernel, const rto
 }
 int rtow_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
   return guarded("rtow_scene_refit", [&] { return impl_scene_refit(c, s); });
+}
+// (diagnostic / tests; pure host arithmetic, usable without a GPU) the queue order of the tiles of a render of `cfg` of
+// `scene` by a context with the default knobs (include/rtow.h)
+int rtow_debug_tile_order(const rtow_scene_t *scene, const rtow_config_t *cfg, uint32_t *table_out, unsigned char *empty_out,
+                          int32_t capacity, int32_t *n_empty, int32_t *tile_w_log2, int32_t *tile_h_log2) {
+  return guarded("rtow_debug_tile_order", [&]() -> int {
+    int rc = validate_scene(scene);
+    if (rc) return rc;
+    if ((rc = validate_cfg(cfg))) return rc;
+    Knobs knobs;
+    knobs.read();
+    rtow_ctx::HostSceneCopy h;
+    h.sg.assign(scene->sphere_geom, scene->sphere_geom + 4 * (size_t)scene->n_spheres);
+    h.mg.assign(scene->moving_geom, scene->moving_geom + 8 * (size_t)scene->n_moving);
+    h.tg.assign(scene->triangle_geom, scene->triangle_geom + 9 * (size_t)scene->n_triangles);
+    h.cam = scene->camera;
+    const int rows = rtow_local_rows(cfg);
+    uint32_t th = 0, tw = 0;
+    if (!knobs.no_tiles) tile_shape(cfg, rows, th, tw);
+    if (tile_w_log2) *tile_w_log2 = (int32_t)tw;
+    if (tile_h_log2) *tile_h_log2 = (int32_t)th;
+    if (n_empty) *n_empty = 0;
+    if (!th) return 0;
+    const uint32_t tpr = (uint32_t)cfg->image_width >> tw, ntr = (uint32_t)rows >> th;
+    std::vector<unsigned char> empty;
+    std::vector<uint32_t> table;
+    if (knobs.tile_order) tile_classify(h, cfg, th, tw, rows, empty);
+    const uint32_t ne = tile_queue_table(empty, knobs.tile_order, tpr, ntr, ntr * (uint32_t)knobs.sky_eighths / 8u, table);
+    if (n_empty) *n_empty = (int32_t)ne;
+    for (size_t i = 0; i < table.size() && (int32_t)i < capacity; ++i) {
+      if (table_out) table_out[i] = table[i];
+      if (empty_out) empty_out[i] = knobs.tile_order ? empty[i] : 0;
+    }
+    return (int)table.size();
+  });
 }
 int rtow_debug_schedule(rtow_ctx *c, const rtow_config_t *cfg, uint32_t *out, int32_t capacity_pairs) {
   return guarded("rtow_debug_schedule", [&] { return impl_debug_schedule(c, cfg, out, capacity_pairs); });

@@ -120,7 +120,12 @@ struct TraceParams {
   uint32_t tile_w_log2, tile_h_log2;
   FastDiv div_tpr;         // tiles per row = W >> tile_w_log2
   uint32_t div_tpr_n;      // the divisor itself
-  uint32_t n_tile_rows, sky_rows;  // tiled order: tile rows of this rank, and how many of the top ones come last
+  uint32_t n_tile_rows;    // tile rows of this rank
+  // tiled order: queue position of a tile -> tile (row-major over this rank's tile rows), made by the host
+  // (rtow_capi.cpp, tile_queue_table): the tiles that see no primitive come last.  Read once per batch, with a scalar load.
+  const uint32_t *tile_table;
+  uint32_t n_items_first;  // queue positions below this one belong to tiles that see something; the rest to empty tiles,
+  uint32_t empty_batch;    // ... whose items (one segment per sample) are bought this many at a time instead of 64
   double *partials;        // [nstreams][local_rows*W][3]
   uint32_t *stack;         // [max_child_rays][n_lanes] material index per bounce
   uint32_t *spill;         // BVH4 kernel: traversal stack entries beyond the LDS part, [entry][n_lanes]

@@ -131,8 +131,13 @@ __device__ __forceinline__ unsigned long long take_items(ItemPool &pool, unsigne
     uint32_t batch = kItemBatch;
     (void)left;
 #else
-    uint32_t batch = (uint32_t)(left / ((unsigned long long)n_waves * 4ull));
-    batch = batch > kItemBatch ? kItemBatch : batch;
+    // (the tail of the queue holds the tiles that see nothing, decode_item: an item there is one segment per sample
+    // against the launch's average of several, so a wave buys several levels of a tile at once — a batch that lasts
+    // about as long as one of the first segment, and the one counter word sees no more requests than before)
+    const bool sky = pool.seen >= (unsigned long long)kp->n_items_first;
+    const uint32_t batch_max = sky ? kp->empty_batch : kItemBatch;
+    uint32_t batch = (uint32_t)((sky ? left * (unsigned long long)(batch_max >> 6) : left) / ((unsigned long long)n_waves * 4ull));
+    batch = batch > batch_max ? batch_max : batch;
     batch = batch < want - avail ? want - avail : batch;
 #endif
     const int leader = __ffsll((long long)need_mask) - 1;
@@ -157,13 +162,15 @@ __device__ __forceinline__ unsigned long long take_items(ItemPool &pool, unsigne
 }
 
 // Queue position -> (partial-sum slot, column, global row, first sample index).
-// Queue order.  Tiled mode: tile-major, stream-minor — all streams of a 64-pixel tile are
-// adjacent, tiles run top-to-bottom, and the queue is consumed from its far end, so a launch
-// ENDS on the top rows of the image for every stream.  In the reference's scenes that is sky
-// (the top 8 % of the cover image: one-segment paths), so most waves run out of work together:
-// waves finishing > 0.2 ms after they find the queue empty fell from 51 % to 5 % (+1.9 %).
-// (Stream-major order ended only the last stream on the sky; ending on the bottom rows —
-// near ground, short paths — measures the same.)  The partial-sum slot stays [stream][pixel].
+// Queue order.  Tiled mode: tile-major, level-minor — all levels of a 64-pixel tile are adjacent — and the queue is
+// consumed from its far end.  Which tile sits at which queue position is a table made by the host (rtow_capi.cpp,
+// tile_queue_table): the tiles through which the camera can see a primitive come first, the horizon rows of an
+// outdoor scene ahead of the rest and the top eighth of the image behind it, and the tiles that see nothing — sky,
+// one segment per sample, no long path can start there — come last, so the waves that run out of work while the
+// last long paths end still find short, uniform items.  The partial-sum slot stays [level][pixel of the real tile].
+// The 64 positions of a (tile, level) group differ only in the pixel inside the tile, and a wave's batch is one such
+// group (two or three where the lanes straddle a batch boundary): everything but the in-tile offset is decoded once
+// per group on the scalar unit — the table entry is one scalar load — and the lanes of the group pick it up.
 struct ItemPos {
   uint32_t item, j, gi, sample0;
   int32_t count;  // samples of the item (the launch's last level may be longer than the others)
@@ -171,33 +178,49 @@ struct ItemPos {
 __device__ __forceinline__ ItemPos decode_item(const RTOW_CONST TraceParams *kp, uint32_t mine, uint32_t npix_local) {
   ItemPos ip;
   const uint32_t qi = kp->n_items - 1u - mine;
-  uint32_t k, lp, lr;
   if (kp->tile_h_log2 == 0u) {  // row-major, stream-major
-    k = fastdiv(qi, FastDiv{kp->div_npix.magic, kp->div_npix.shift});
-    lp = qi - k * npix_local;
-    lr = fastdiv(lp, FastDiv{kp->div_w.magic, kp->div_w.shift});
+    const uint32_t k = fastdiv(qi, FastDiv{kp->div_npix.magic, kp->div_npix.shift});
+    const uint32_t lp = qi - k * npix_local;
+    const uint32_t lr = fastdiv(lp, FastDiv{kp->div_w.magic, kp->div_w.shift});
     ip.j = lp - lr * (uint32_t)kp->W;
-  } else {  // 64-pixel tiles: a wave's batch of 64 items is one compact tile of one stream
-    const uint32_t g64 = qi >> 6, w = qi & 63u;
-    const uint32_t t = fastdiv(g64, FastDiv{kp->div_ns.magic, kp->div_ns.shift});
-    k = g64 - t * (uint32_t)kp->nstreams;
-    const uint32_t trq = fastdiv(t, FastDiv{kp->div_tpr.magic, kp->div_tpr.shift});  // tile row by queue position
-    const uint32_t tc = t - trq * (kp->div_tpr_n);
-    // Tile rows are consumed from the highest position down.  Positions >= sky_rows hold the
-    // rows below the top band, top-down (the horizon rows of an outdoor scene — its costliest —
-    // go first); the top band (sky_rows tile rows, typically one-segment paths) comes last.
-    const uint32_t tr = trq >= kp->sky_rows ? kp->sky_rows + (kp->n_tile_rows - 1u - trq) : trq;
-    lp = ((tr * kp->div_tpr_n + tc) << 6) | w;
-    lr = (tr << kp->tile_h_log2) + (w >> kp->tile_w_log2);
-    ip.j = (tc << kp->tile_w_log2) + (w & ((1u << kp->tile_w_log2) - 1u));
+    ip.item = k * npix_local + lp;  // partial-sum slot
+    // local row -> global row: this rank's q-th strip is global strip q*nranks+rank
+    const uint32_t q = fastdiv(lr, FastDiv{kp->div_tile.magic, kp->div_tile.shift});
+    const uint32_t rr = lr - q * (uint32_t)kp->tile_rows;
+    ip.gi = (q * (uint32_t)kp->nranks + (uint32_t)kp->rank) * (uint32_t)kp->tile_rows + rr;
+    ip.sample0 = kp->sample_base + k * (uint32_t)kp->spt;  // first sample index of this level
+    ip.count = k + 1u == (uint32_t)kp->nstreams ? kp->spt_last : kp->spt;
+    return ip;
   }
-  ip.item = k * npix_local + lp;  // partial-sum slot
-  // local row -> global row: this rank's q-th strip is global strip q*nranks+rank
-  const uint32_t q = fastdiv(lr, FastDiv{kp->div_tile.magic, kp->div_tile.shift});
-  const uint32_t rr = lr - q * (uint32_t)kp->tile_rows;
-  ip.gi = (q * (uint32_t)kp->nranks + (uint32_t)kp->rank) * (uint32_t)kp->tile_rows + rr;
-  ip.sample0 = kp->sample_base + k * (uint32_t)kp->spt;  // first sample index of this level
-  ip.count = k + 1u == (uint32_t)kp->nstreams ? kp->spt_last : kp->spt;
+  // 64-pixel tiles: the lanes of one (tile, level) group at a time, the group of the first lane still waiting
+  const uint32_t g64 = qi >> 6, w = qi & 63u;
+  const RTOW_CONST uint32_t *table = (const RTOW_CONST uint32_t *)kp->tile_table;
+  ip.item = ip.j = ip.gi = ip.sample0 = 0u;
+  ip.count = 0;
+  for (;;) {
+    const uint32_t ug = (uint32_t)__builtin_amdgcn_readfirstlane((int)g64);  // wave-uniform from here to the select
+    const uint32_t t = fastdiv(ug, FastDiv{kp->div_ns.magic, kp->div_ns.shift});
+    const uint32_t k = ug - t * (uint32_t)kp->nstreams;
+    const uint32_t tile = table[t];
+    const uint32_t tr = fastdiv(tile, FastDiv{kp->div_tpr.magic, kp->div_tpr.shift});
+    const uint32_t tc = tile - tr * kp->div_tpr_n;
+    // first local row of the tile -> global row (a tile never straddles two strips: its rows are consecutive)
+    const uint32_t lr0 = tr << kp->tile_h_log2;
+    const uint32_t q = fastdiv(lr0, FastDiv{kp->div_tile.magic, kp->div_tile.shift});
+    const uint32_t gi0 = (q * (uint32_t)kp->nranks + (uint32_t)kp->rank) * (uint32_t)kp->tile_rows + (lr0 - q * (uint32_t)kp->tile_rows);
+    const uint32_t item0 = k * npix_local + (tile << 6);
+    const uint32_t j0 = tc << kp->tile_w_log2;
+    const uint32_t s0 = kp->sample_base + k * (uint32_t)kp->spt;
+    const int32_t cnt = k + 1u == (uint32_t)kp->nstreams ? kp->spt_last : kp->spt;
+    if (g64 == ug) {
+      ip.item = item0 + w;  // partial-sum slot
+      ip.j = j0 + (w & ((1u << kp->tile_w_log2) - 1u));
+      ip.gi = gi0 + (w >> kp->tile_w_log2);
+      ip.sample0 = s0;
+      ip.count = cnt;
+      break;
+    }
+  }
   return ip;
 }
 

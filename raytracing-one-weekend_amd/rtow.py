@@ -181,6 +181,7 @@ EXPORTS = [
     "rtow_render_device_rgb8", "rtow_multi_render_rgb8", "rtow_multi_frame_breakdown",
     "rtow_intersect_device", "rtow_intersect", "rtow_occluded_device", "rtow_occluded",
     "rtow_scene_refit", "rtow_refit_info", "rtow_closest_point_device", "rtow_closest_point",
+    "rtow_debug_tile_order",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -278,6 +279,10 @@ def lib():
     L.rtow_profile_collect.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     if hasattr(L, "rtow_debug_schedule"):  # (absent from older builds loaded through RTOW_LIB for A/B runs)
         L.rtow_debug_schedule.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(C.c_uint32), C.c_int32]
+    if hasattr(L, "rtow_debug_tile_order"):
+        L.rtow_debug_tile_order.argtypes = [C.POINTER(Scene), C.POINTER(Config), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_ubyte), C.c_int32, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     ver = L.rtow_abi_version()
     if ver != RTOW_ABI_VERSION and not ("RTOW_LIB" in os.environ and ver >= 4):  # (older builds: A/B runs only)
         raise RtowError("librtow.so ABI version mismatch")
