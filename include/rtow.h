@@ -473,6 +473,53 @@ int rtow_closest_point_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, 
 int rtow_closest_point(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
                        rtow_point_hit_t *hits, rtow_stats_t *stats);
 
+/* ---- radiance queries ---------------------------------------------------------------------------------------------------
+ * "How much light arrives along this ray?" — the reference's ray_color (src/render.cpp:112-129) for caller rays: light
+ * probes, lightmap texels, a camera of the caller's own.  For ray i the result is the sum over j = 0 .. samples_per_ray - 1
+ * of ray_color(ray_i, max_child_rays), added in sample order by one lane starting from +0.0: SUMS, like
+ * rtow_render_device — the caller divides.  A hit with no child rays left is black (src/render.cpp:115).
+ *
+ *   rays       rtow_ray_t, as for rtow_intersect.  `time` is the path's shutter time and is handed on to every scattered
+ *              ray; `tmax` is not read: paths are unbounded, like the reference's.
+ *   Philox     sample j of ray i draws as (pixel, sample) = (ids[i][0], ids[i][1] + sample_first + j), the sums mod 2^32;
+ *              without ids (NULL) as (i, sample_first + j).  Bounce b draws request 1 + b; request 0 belongs to the
+ *              render's camera and is never drawn.  So a ray a render generated for (pixel, sample), queried with that
+ *              identity and the render's seed and max_child_rays, gives that sample's colour; and a caller who wants more
+ *              parallelism than one lane per ray repeats the ray with different first sample indices.
+ *   precision  RTOW_F64_STRICT: bit-identical to the oracle's ray_color on that ray and identity, under every kernel and
+ *                               with either builder: attenuations are folded from the end of the path,
+ *                               a1*(a2*(...*sky)), as the strict render does;
+ *              RTOW_F64_FAST:   the fast build's walks, the forward product ((a1*a2)*...)*sky, contracted arithmetic;
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ *              In both builds a ray with k samples equals the in-order sum of k one-sample queries bit for bit, and the
+ *              result does not depend on how the rays were scheduled.
+ *   kernel     as rtow_intersect_device: the same resolution, fallbacks, residency rules (RTOW_ENOSCENE after a lean
+ *              upload) and kernel_used; RTOW_KERNEL_REFTREE is strict only.
+ * d_rays (16-byte aligned), d_ids (uint32_t[n_rays][2], 8-byte aligned, or NULL) and d_rgb_sums (double[n_rays][3], 8-byte
+ * aligned) are DEVICE pointers; nothing beyond n_rays results is written.  Enqueued on hip_stream with the ordering rule
+ * of rtow_intersect_device (a non-blocking stream is made to wait for the last upload or refit); returns without
+ * synchronising unless stats != NULL, which synchronises and fills samples = n_rays * samples_per_ray, segments (traced,
+ * from a device counter), prim_tests, node_tests, kernel_ms, total_ms, kernel_used; local_rows = 0.
+ * Errors: RTOW_EINVAL for a NULL ctx or params, NULL rays or result with n_rays > 0, n_rays < 0 or > 2^31 - 64, rays not
+ * 16-byte aligned, ids or result not 8-byte aligned, samples_per_ray < 1, max_child_rays < 0, an unknown precision or
+ * kernel; RTOW_ENOSCENE without a resident scene.  n_rays == 0 returns RTOW_OK and launches nothing.  One call in flight
+ * per context.  The render path is not involved: the profile ring and the dropped-sample word are untouched, and a render
+ * after any number of radiance queries is bit-identical to one without them. */
+typedef struct rtow_radiance_params_t {   /* 24 B */
+  uint64_t seed;            /* Philox key, as rtow_config_t::seed */
+  int32_t samples_per_ray;  /* >= 1: paths traced per ray, summed in sample order */
+  int32_t max_child_rays;   /* >= 0: the render's depth */
+  uint32_t sample_first;    /* added (mod 2^32) to every ray's first sample index */
+  int32_t pad_;
+} rtow_radiance_params_t;
+
+int rtow_radiance_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params,
+                         const void *d_rays, int64_t n_rays, const void *d_ids /* uint32_t[n_rays][2] or NULL */,
+                         void *d_rgb_sums /* double[n_rays][3] */, void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
+int rtow_radiance(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params,
+                  const rtow_ray_t *rays, int64_t n_rays, const uint32_t *ids, double *rgb_sums, rtow_stats_t *stats);
+
 /* ---- in-place refit of the resident scene (moving geometry) ---------------------------------------------------------
  * Replace the geometry, materials and camera of the scene resident in ctx, keeping its trees' topology: the node
  * structure, leaf membership and leaf order of the binary and 4-wide BVHs stay as built; records, boxes and planes are

@@ -256,6 +256,13 @@ QueryLaunchFn launch_query_strict, launch_query_fast, launch_occlude_strict, lau
     launch_pointq_fast;
 QueryOccupancyFn query_occupancy_strict, query_occupancy_fast, occlude_occupancy_strict, occlude_occupancy_fast,
     pointq_occupancy_strict, pointq_occupancy_fast;
+// csrc/rtow_radiance_{strict,fast}.hip (rtow_radiance.h): the radiance query; `p` carries the seed, max_child_rays and
+// the strict build's path stack beside the walks' fields
+using RadianceLaunchFn = int(const TraceParams &p, const void *rays, const void *ids, void *out, uint32_t n,
+                             int32_t samples_per_ray, uint32_t sample_first, unsigned long long *counters, int kernel,
+                             int grid, int block, unsigned lds_bytes, void *stream);
+RadianceLaunchFn launch_radiance_strict, launch_radiance_fast;
+QueryOccupancyFn radiance_occupancy_strict, radiance_occupancy_fast;
 // csrc/rtow_refit.hip (rtow_scene_refit): 0, or 1 when a launch failed
 int refit_records(const double *g_sph, const double *g_mov, const double *g_tri, int ns, int nm, int nt, double *sph,
                   double *sph_r, double *mov, double *tri, double *tri16, void *stream);
@@ -322,6 +329,8 @@ struct Knobs {
   int empty_levels = 3;           // RTOW_EMPTY_LEVELS: levels of a tile one atomic buys in the queue's empty-tile segment (1..16)
   int tail_bound = 0;             // RTOW_TAIL_BOUND (tests only): trips of the end-of-launch protocol before a wave gives up
                                   //   its samples (0 = the structural bound); a small value forces the RTOW_EHIP path
+  int radiance_blocks = 0;        // RTOW_RADIANCE_BLOCKS (tests only): cap on the workgroups of a radiance query (0 = none), so
+                                  //   that a small batch makes every lane take many rays
   void read() {
     auto geti = [](const char *n, int d) { const char *e = std::getenv(n); return e ? std::atoi(e) : d; };
     auto getd = [](const char *n, double d) { const char *e = std::getenv(n); return e ? std::atof(e) : d; };
@@ -365,6 +374,7 @@ struct Knobs {
     sched_chunk = std::min(std::max(geti("RTOW_SCHED_CHUNK", 10), 0), 4096);
     sched_chunk_mesh = std::min(std::max(geti("RTOW_SCHED_CHUNK_MESH", 16), 0), 4096);
     tail_bound = std::max(geti("RTOW_TAIL_BOUND", 0), 0);
+    radiance_blocks = std::max(geti("RTOW_RADIANCE_BLOCKS", 0), 0);
     tile_order = geti("RTOW_TILE_ORDER", 1) != 0;
     empty_levels = std::min(std::max(geti("RTOW_EMPTY_LEVELS", 3), 1), 16);
     no_spec = std::getenv("RTOW_NO_SPEC") != nullptr;
@@ -452,6 +462,7 @@ struct rtow_ctx {
   // touches the render's workspace, profile ring or dropped-sample word); the walk-id -> insertion-index tables are built
   // at the first closest-hit query that needs them after an upload (query_map)
   DevBuf q_counters, q_spill, q_rays, q_hits, q_occ, q_map[3];
+  DevBuf q_stack, q_ids, q_rgb;  // rtow_radiance*: the strict build's path stack (sized per launch), the host form's staging
   bool q_map_ok[3] = {false, false, false};
   hipEvent_t q_ev[4] = {};
   unsigned long long *h_qcounters = nullptr;
@@ -531,7 +542,8 @@ void rtow_ctx_destroy(rtow_ctx *c) {
                     &c->blob32, &c->gblob32, &c->cam32_dev, &c->blob4,
                     &c->partials, &c->stack, &c->counters, &c->spill, &c->out, &c->out8, &c->rtree, &c->counters_init,
                     &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_occ, &c->q_map[0], &c->q_map[1],
-                    &c->q_map[2], &c->rf.map2, &c->rf.map4, &c->rf.par2, &c->rf.par4, &c->rf.need4, &c->rf.flags,
+                    &c->q_map[2], &c->q_stack, &c->q_ids, &c->q_rgb,
+                    &c->rf.map2, &c->rf.map4, &c->rf.par2, &c->rf.par4, &c->rf.need4, &c->rf.flags,
                     &c->rf.nbox2, &c->rf.nbox4, &c->rf.sbox4, &c->rf.pbox, &c->rf.partials, &c->rf.area, &c->rf.g_sph,
                     &c->rf.g_mov, &c->rf.g_tri, &c->tile_table})
     b->release();
@@ -2007,10 +2019,12 @@ static const QueryKind kClosestPoint = {
     .out_buf = &rtow_ctx::q_hits, .launch = {rtow::launch_pointq_strict, rtow::launch_pointq_fast},
     .occupancy = {rtow::pointq_occupancy_strict, rtow::pointq_occupancy_fast}};
 
+constexpr size_t kQueryCounters = 4;  // [0] primitive tests, [1] node tests; the radiance query: [2] segments, [3] queue head
 struct QueryRun {
   int kernel = 0;
   bool strict = false;
   LaunchShape shape;
+  int block_cap = 0;  // > 0: at most this many workgroups (the radiance query's test knob)
 };
 // The point query's strategy: AUTO takes the best resident tree (BVH4, else BVH, else BRUTE: it never fails on a resident
 // scene); GRID has no point walk and is answered by the binary BVH; then the render's fallbacks and residency rules.
@@ -2054,9 +2068,10 @@ static int query_launch(rtow_ctx *c, const QueryRun &q, int64_t n_rays, int occ,
   long long grid = (long long)c->num_cus * occ;
   const long long need_blocks = (n_rays + block - 1) / block;
   grid = std::max(std::min(grid, need_blocks), 1ll);
+  if (q.block_cap > 0) grid = std::min(grid, (long long)q.block_cap);
   const unsigned long long n_lanes = (unsigned long long)grid * block;
   int rc;
-  if ((rc = c->q_counters.ensure(2 * sizeof(unsigned long long)))) return rc;
+  if ((rc = c->q_counters.ensure(kQueryCounters * sizeof(unsigned long long)))) return rc;
   if (kernel == RTOW_KERNEL_BVH4) {
     const int extra = std::max(q.shape.stack_bound - (int)q.shape.scene.b4_stack_k, 0);
     if ((rc = c->q_spill.ensure(std::max<size_t>((size_t)extra * (size_t)n_lanes * sizeof(uint32_t), 16)))) return rc;
@@ -2075,18 +2090,18 @@ static int query_launch(rtow_ctx *c, const QueryRun &q, int64_t n_rays, int occ,
   hipStream_t st = (hipStream_t)hip_stream;
   if (stats && !c->q_ev[0]) {
     for (hipEvent_t &e : c->q_ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipHostMalloc((void **)&c->h_qcounters, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **)&c->h_qcounters, kQueryCounters * sizeof(unsigned long long), hipHostMallocDefault));
   }
   if (st != nullptr) HIPCHK(hipStreamWaitEvent(st, c->upload_ev, 0));  // the scene upload was queued on the null stream
   if (stats) HIPCHK(hipEventRecord(c->q_ev[0], st));
-  HIPCHK(hipMemsetAsync(c->q_counters.p, 0, 2 * sizeof(unsigned long long), st));
+  HIPCHK(hipMemsetAsync(c->q_counters.p, 0, kQueryCounters * sizeof(unsigned long long), st));
   if (stats) HIPCHK(hipEventRecord(c->q_ev[1], st));
   auto *counters = (unsigned long long *)c->q_counters.p;
   const int lrc = launch(P, counters, (int)grid);
   if (lrc != 0) return fail(RTOW_EHIP, "query kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
   if (stats) {
     HIPCHK(hipEventRecord(c->q_ev[2], st));
-    HIPCHK(hipMemcpyAsync(c->h_qcounters, counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_qcounters, counters, kQueryCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(c->q_ev[3], st));
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0.f;
@@ -2147,6 +2162,76 @@ static int query_host(rtow_ctx *c, const QueryKind &k, int32_t precision, int32_
   HIPCHK(hipMemcpy(c->q_rays.p, in, (size_t)n * k.in_bytes, hipMemcpyHostToDevice));
   if ((rc = query_device(c, k, precision, kernel, c->q_rays.p, n, d_out.p, nullptr, stats))) return rc;
   HIPCHK(hipMemcpy(out, d_out.p, (size_t)n * k.out_bytes, hipMemcpyDeviceToHost));
+  return RTOW_OK;
+}
+
+// The radiance query (rtow_radiance*, csrc/rtow_radiance.h): the ray queries' strategy, launch shape, ordering and stats
+// (query_begin / query_launch) around a kernel that traces whole paths.  The launch fills what the paths need beyond the
+// walks' fields: the Philox key, the depth and — strict build — a path stack of its own, sized for this launch's lanes.
+static int radiance_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const rtow_radiance_params_t *prm,
+                           const void *d_rays, int64_t n, const void *d_ids, void *d_out, void *hip_stream,
+                           rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (!prm) return fail(RTOW_EINVAL, "params is NULL");
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
+  if (n > 0 && (!d_rays || !d_out)) return fail(RTOW_EINVAL, "NULL ray or result buffer");
+  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
+  if (((uintptr_t)d_ids & 7u) != 0u) return fail(RTOW_EINVAL, "ids buffer must be 8-byte aligned");
+  if (((uintptr_t)d_out & 7u) != 0u) return fail(RTOW_EINVAL, "result buffer must be 8-byte aligned");
+  if (prm->samples_per_ray < 1) return fail(RTOW_EINVAL, "samples_per_ray %d < 1", prm->samples_per_ray);
+  if (prm->max_child_rays < 0) return fail(RTOW_EINVAL, "max_child_rays %d < 0", prm->max_child_rays);
+  QueryRun q;
+  int rc;
+  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
+  if (n == 0) return RTOW_OK;
+  q.block_cap = c->knobs.radiance_blocks;
+
+  const int kernel = q.kernel;
+  const int block = q.shape.block;
+  const unsigned lds = q.shape.lds_bytes;
+  const int build = q.strict ? 0 : 1;
+  rtow::RadianceLaunchFn *const launch[2] = {rtow::launch_radiance_strict, rtow::launch_radiance_fast};
+  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::radiance_occupancy_strict, rtow::radiance_occupancy_fast};
+  const int occ = occupancy[build](kernel, block, lds, nullptr);
+  int stack_rc = RTOW_OK;
+  rc = query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P0, unsigned long long *counters, int grid) {
+    rtow::TraceParams P = P0;
+    P.seed_lo = (uint32_t)(prm->seed & 0xffffffffu);
+    P.seed_hi = (uint32_t)(prm->seed >> 32);
+    P.max_child_rays = prm->max_child_rays;
+    if (q.strict) {  // [bounce][lane] material indices
+      const size_t words = (size_t)prm->max_child_rays * (size_t)P.n_lanes;
+      if ((stack_rc = c->q_stack.ensure(std::max<size_t>(words * sizeof(uint32_t), 16)))) return (int)hipErrorOutOfMemory;
+      P.stack = (uint32_t *)c->q_stack.p;
+    }
+    return launch[build](P, d_rays, d_ids, d_out, (uint32_t)n, prm->samples_per_ray, prm->sample_first, counters, kernel, grid,
+                         block, lds, hip_stream);
+  });
+  if (stack_rc != RTOW_OK) return stack_rc;
+  if (rc == RTOW_OK && stats) {
+    stats->samples = (uint64_t)n * (uint64_t)prm->samples_per_ray;
+    stats->segments = c->h_qcounters[2];
+  }
+  return rc;
+}
+
+static int radiance_host(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_radiance_params_t *prm,
+                         const rtow_ray_t *rays, int64_t n, const uint32_t *ids, double *out, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
+  if (n > 0 && (!rays || !out)) return fail(RTOW_EINVAL, "NULL ray or result array");
+  if (n == 0) return radiance_device(c, precision, kernel, prm, nullptr, 0, nullptr, nullptr, nullptr, stats);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_ray_t))) || (rc = c->q_rgb.ensure((size_t)n * 24)) ||
+      (ids && (rc = c->q_ids.ensure((size_t)n * 8))))
+    return rc;
+  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
+  if (ids) HIPCHK(hipMemcpy(c->q_ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+  if ((rc = radiance_device(c, precision, kernel, prm, c->q_rays.p, n, ids ? c->q_ids.p : nullptr, c->q_rgb.p, nullptr, stats)))
+    return rc;
+  HIPCHK(hipMemcpy(out, c->q_rgb.p, (size_t)n * 24, hipMemcpyDeviceToHost));
   return RTOW_OK;
 }
 
@@ -2693,6 +2778,17 @@ int rtow_closest_point_device(rtow_ctx *c, int32_t precision, int32_t kernel, co
 int rtow_closest_point(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
                        rtow_point_hit_t *hits, rtow_stats_t *stats) {
   return guarded("rtow_closest_point", [&] { return query_host(c, kClosestPoint, precision, kernel, queries, n, hits, stats); });
+}
+int rtow_radiance_device(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params,
+                         const void *d_rays, int64_t n_rays, const void *d_ids, void *d_rgb_sums, void *hip_stream,
+                         rtow_stats_t *stats) {
+  return guarded("rtow_radiance_device", [&] {
+    return radiance_device(c, precision, kernel, params, d_rays, n_rays, d_ids, d_rgb_sums, hip_stream, stats);
+  });
+}
+int rtow_radiance(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params, const rtow_ray_t *rays,
+                  int64_t n_rays, const uint32_t *ids, double *rgb_sums, rtow_stats_t *stats) {
+  return guarded("rtow_radiance", [&] { return radiance_host(c, precision, kernel, params, rays, n_rays, ids, rgb_sums, stats); });
 }
 int rtow_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
   return guarded("rtow_scene_refit", [&] { return impl_scene_refit(c, s); });

@@ -132,6 +132,12 @@ class PointHit(C.Structure):
     ]
 
 
+class RadianceParams(C.Structure):
+    """rtow_radiance_params_t (24 B): Philox key, samples per ray, depth, offset of every ray's first sample index."""
+    _fields_ = [("seed", C.c_uint64), ("samples_per_ray", C.c_int32), ("max_child_rays", C.c_int32),
+                ("sample_first", C.c_uint32), ("pad_", C.c_int32)]
+
+
 # numpy views of the same layouts (arrays of rays / hits for rtow_intersect*)
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("time", "<f8"), ("direction", "<f8", (3,)), ("tmax", "<f8")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("prim", "<i4"), ("kind", "<i4"),
@@ -181,7 +187,7 @@ EXPORTS = [
     "rtow_render_device_rgb8", "rtow_multi_render_rgb8", "rtow_multi_frame_breakdown",
     "rtow_intersect_device", "rtow_intersect", "rtow_occluded_device", "rtow_occluded",
     "rtow_scene_refit", "rtow_refit_info", "rtow_closest_point_device", "rtow_closest_point",
-    "rtow_debug_tile_order",
+    "rtow_debug_tile_order", "rtow_radiance_device", "rtow_radiance",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -273,6 +279,11 @@ def lib():
                                                 C.c_void_p, C.POINTER(Stats)]
         L.rtow_closest_point.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                          C.POINTER(Stats)]
+    if hasattr(L, "rtow_radiance"):
+        L.rtow_radiance_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RadianceParams), C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rtow_radiance.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RadianceParams), C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     if hasattr(L, "rtow_scene_refit"):
         L.rtow_scene_refit.argtypes = [C.c_void_p, C.POINTER(Scene)]
         L.rtow_refit_info.argtypes = [C.c_void_p, C.POINTER(RefitInfo)]
@@ -547,6 +558,38 @@ class Context:
         check(lib().rtow_closest_point_device(self._h, precision, kernel, C.c_void_p(d_q), n, C.c_void_p(d_hits),
                                               C.c_void_p(stream), C.byref(st) if st is not None else None),
               "rtow_closest_point_device")
+        return st
+
+    def radiance(self, rays, samples_per_ray=1, max_child_rays=50, seed=1, ids=None, sample_first=0, precision=F64_FAST,
+                 kernel=KERNEL_AUTO, want_stats=False):
+        """Path-traced radiance along every ray (a RAY_DTYPE array, host memory; tmax is not read): an [n, 3] float64
+        array of SUMS over `samples_per_ray` paths of depth `max_child_rays`, and Stats with `want_stats`
+        (rtow_radiance).  `ids`: [n, 2] uint32 (pixel, first sample) Philox identities; None: (i, 0)."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        out = np.empty((len(r), 3), dtype=np.float64)
+        idp = None
+        if ids is not None:
+            ida = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1, 2)
+            if len(ida) != len(r):
+                raise ValueError("ids must be [n, 2]")
+            idp = ida.ctypes.data_as(C.c_void_p)
+        prm = RadianceParams(seed, samples_per_ray, max_child_rays, sample_first, 0)
+        st = Stats() if want_stats else None
+        check(lib().rtow_radiance(self._h, precision, kernel, C.byref(prm), r.ctypes.data_as(C.c_void_p), len(r), idp,
+                                  out.ctypes.data_as(C.c_void_p), C.byref(st) if st is not None else None),
+              "rtow_radiance")
+        return (out, st) if want_stats else out
+
+    def radiance_device(self, d_rays: int, n: int, d_ids: int, d_rgb: int, samples_per_ray=1, max_child_rays=50, seed=1,
+                        sample_first=0, precision=F64_FAST, kernel=KERNEL_AUTO, stream: int = 0, want_stats=False):
+        """The same on device buffers (raw pointers: n x 64-byte rays, n x 2 uint32 ids or 0, n x 3 float64 sums),
+        enqueued on `stream` (rtow_radiance_device); returns Stats with `want_stats` (then synchronised), else None."""
+        prm = RadianceParams(seed, samples_per_ray, max_child_rays, sample_first, 0)
+        st = Stats() if want_stats else None
+        check(lib().rtow_radiance_device(self._h, precision, kernel, C.byref(prm), C.c_void_p(d_rays), n,
+                                         C.c_void_p(d_ids) if d_ids else None, C.c_void_p(d_rgb), C.c_void_p(stream),
+                                         C.byref(st) if st is not None else None),
+              "rtow_radiance_device")
         return st
 
     def profile_collect(self):
