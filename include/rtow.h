@@ -520,6 +520,66 @@ int rtow_radiance_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const
 int rtow_radiance(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params,
                   const rtow_ray_t *rays, int64_t n_rays, const uint32_t *ids, double *rgb_sums, rtow_stats_t *stats);
 
+/* ---- the camera stage: primaries of the resident camera, first-hit guide buffers ----------------------------------------
+ * The one piece of the render the queries above leave out: Camera::get_ray (src/render.cpp:158-159,
+ * src/common-model.cpp:156-167) for the camera of the scene resident in ctx (after the last upload or refit), fed from
+ * request 0 of (pixel, sample) — pixel jitter, shutter time and lens point exactly as the render draws them.
+ *
+ * Both calls read `cfg` as rtow_render_device does: image_width / image_height and seed; rank / nranks / tile_rows select
+ * this rank's rows (ascending, rtow_local_row_list); the sample set is the one a render of cfg traces — samples
+ * [0, spp_eff) with spp_eff = samples_per_pixel / nstreams * nstreams when stream_count == 0, otherwise the samples of
+ * streams [stream_first, stream_first + stream_count), each stream samples_per_pixel / nstreams long.  max_child_rays and
+ * accumulate are ignored.  precision: RTOW_F64_STRICT or RTOW_F64_FAST; RTOW_F32 is refused (RTOW_EINVAL).  Stream
+ * ordering, errors, RTOW_ENOSCENE and "nothing to do launches nothing" follow rtow_intersect_device.  The render path is
+ * not involved: the profile ring, the dropped-sample word and the workspace are untouched, and a render after any number
+ * of these calls is bit-identical to one without them.
+ *
+ * rtow_camera_rays*: n = local_rows * image_width * samples rays (rtow_camera_ray_count; must not exceed 2^31 - 64),
+ * pixel-major over the rank's rows, a pixel's samples ascending.  ids[i] = (global row-major pixel index, sample index):
+ * the Philox identity rtow_radiance takes, so radiance(camera_rays(cfg), ids, seed, max_child_rays) added per pixel in
+ * sample order IS the render (bit for bit in the strict build with nstreams == 1).  tmax = +inf.
+ *   RTOW_F64_STRICT: origin, direction and time are bit-identical to the reference's get_ray on the oracle's draws;
+ *   RTOW_F64_FAST:   the fast render's camera arithmetic (contracted; u and v multiply by 1 / (W - 1) and 1 / (H - 1)).
+ * The kernel reads the camera alone: cfg->kernel is ignored except that an unknown value is RTOW_EINVAL, and the call
+ * works after the lean upload of rtow_render too.  d_rays: rtow_ray_t[n], DEVICE memory, 16-byte aligned; d_ids:
+ * uint32_t[n][2], DEVICE memory, 8-byte aligned, or NULL (no ids are written).  Returns without synchronising.
+ *
+ * rtow_guides*: what a denoiser takes beside the beauty image, with the render's own jitter, lens and shutter samples, so
+ * that depth of field and motion blur agree between the guides and the image.  Per pixel, SUMS over the pixel's samples
+ * (the caller divides: hits / samples is coverage, depth / hits the mean distance over the hits), added by one lane in
+ * sample order from +0.0.  Per sample, with the primary (o, d, time) and its closest hit over [0.001, inf):
+ *   hit   albedo += the attenuation the reference's scatter returns: the albedo (Lambertian, Metal), (1, 1, 1) (Dielectric);
+ *         normal += the unit shading normal: a sphere's Hit::normal (normalize(p - c), facing the ray), a triangle's
+ *                   n / sqrt(n . n) with n = e1 x e2;
+ *         depth  += t * sqrt(d . d), the distance from the ray origin;   hits += 1;
+ *   miss  albedo += the reference's sky for d (ray_color's miss branch); normal, depth and hits add nothing.
+ * The operand order of every expression is written in csrc/rtow_guides.h; RTOW_F64_STRICT evaluates it without
+ * contraction (bit-identical to that order in IEEE binary64, under every kernel, with either builder and for every
+ * partition of the image), RTOW_F64_FAST contracted with the fast build's sqrt, rcp and div.  No result is NaN for a
+ * finite scene.  cfg->kernel: resolution, fallbacks, residency rules (RTOW_ENOSCENE after a lean upload that did not
+ * build the strategy's structures) and kernel_used as rtow_intersect_device; RTOW_KERNEL_REFTREE is strict only.
+ * d_guides: rtow_guide_t[local_rows * image_width], DEVICE memory, 16-byte aligned, row-major over this rank's rows.
+ * With stats it synchronises and fills samples = segments = pixels * samples, prim_tests, node_tests, kernel_ms,
+ * total_ms, kernel_used, local_rows. */
+typedef struct rtow_guide_t { /* 64 B: four 16-byte stores per pixel */
+  double albedo[3];
+  double normal[3];
+  double depth;
+  double hits;
+} rtow_guide_t;
+
+int rtow_camera_rays_device(rtow_ctx *ctx, const rtow_config_t *cfg, void *d_rays /* rtow_ray_t[n] */,
+                            void *d_ids /* uint32_t[n][2] (pixel, sample) or NULL */, void *hip_stream);
+/* The same to host memory (device staging owned by the context, the null stream); synchronous.  ids may be NULL. */
+int rtow_camera_rays(rtow_ctx *ctx, const rtow_config_t *cfg, rtow_ray_t *rays, uint32_t *ids);
+/* n of the two calls above, or a negative RTOW_E* code for an invalid cfg — pure host arithmetic, usable without a GPU. */
+int64_t rtow_camera_ray_count(const rtow_config_t *cfg);
+
+int rtow_guides_device(rtow_ctx *ctx, const rtow_config_t *cfg, void *d_guides /* rtow_guide_t[local_rows * W] */,
+                       void *hip_stream, rtow_stats_t *stats);
+/* The same to host memory (device staging owned by the context, the null stream); synchronous. */
+int rtow_guides(rtow_ctx *ctx, const rtow_config_t *cfg, rtow_guide_t *guides, rtow_stats_t *stats);
+
 /* ---- in-place refit of the resident scene (moving geometry) ---------------------------------------------------------
  * Replace the geometry, materials and camera of the scene resident in ctx, keeping its trees' topology: the node
  * structure, leaf membership and leaf order of the binary and 4-wide BVHs stay as built; records, boxes and planes are

@@ -263,6 +263,15 @@ using RadianceLaunchFn = int(const TraceParams &p, const void *rays, const void 
                              int grid, int block, unsigned lds_bytes, void *stream);
 RadianceLaunchFn launch_radiance_strict, launch_radiance_fast;
 QueryOccupancyFn radiance_occupancy_strict, radiance_occupancy_fast;
+// csrc/rtow_guides_{strict,fast}.hip (rtow_guides.h): the camera stage — the primaries of the resident camera and the
+// first-hit guide buffers; `p` carries the camera, the image size, the rank's rows and the seed beside the walks' fields
+using GuidesLaunchFn = int(const TraceParams &p, void *out, uint32_t n, uint32_t sample_first, int32_t samples,
+                           unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
+using CameraRaysLaunchFn = int(const TraceParams &p, void *rays, void *ids, uint32_t n, uint32_t sample_first,
+                               int32_t samples, int grid, int block, void *stream);
+GuidesLaunchFn launch_guides_strict, launch_guides_fast;
+CameraRaysLaunchFn launch_camera_rays_strict, launch_camera_rays_fast;
+QueryOccupancyFn guides_occupancy_strict, guides_occupancy_fast;
 // csrc/rtow_refit.hip (rtow_scene_refit): 0, or 1 when a launch failed
 int refit_records(const double *g_sph, const double *g_mov, const double *g_tri, int ns, int nm, int nt, double *sph,
                   double *sph_r, double *mov, double *tri, double *tri16, void *stream);
@@ -331,6 +340,7 @@ struct Knobs {
                                   //   its samples (0 = the structural bound); a small value forces the RTOW_EHIP path
   int radiance_blocks = 0;        // RTOW_RADIANCE_BLOCKS (tests only): cap on the workgroups of a radiance query (0 = none), so
                                   //   that a small batch makes every lane take many rays
+  int guides_blocks = 0;          // RTOW_GUIDES_BLOCKS (tests only): the same cap for rtow_guides*: every lane takes many pixels
   void read() {
     auto geti = [](const char *n, int d) { const char *e = std::getenv(n); return e ? std::atoi(e) : d; };
     auto getd = [](const char *n, double d) { const char *e = std::getenv(n); return e ? std::atof(e) : d; };
@@ -375,6 +385,7 @@ struct Knobs {
     sched_chunk_mesh = std::min(std::max(geti("RTOW_SCHED_CHUNK_MESH", 16), 0), 4096);
     tail_bound = std::max(geti("RTOW_TAIL_BOUND", 0), 0);
     radiance_blocks = std::max(geti("RTOW_RADIANCE_BLOCKS", 0), 0);
+    guides_blocks = std::max(geti("RTOW_GUIDES_BLOCKS", 0), 0);
     tile_order = geti("RTOW_TILE_ORDER", 1) != 0;
     empty_levels = std::min(std::max(geti("RTOW_EMPTY_LEVELS", 3), 1), 16);
     no_spec = std::getenv("RTOW_NO_SPEC") != nullptr;
@@ -463,6 +474,7 @@ struct rtow_ctx {
   // at the first closest-hit query that needs them after an upload (query_map)
   DevBuf q_counters, q_spill, q_rays, q_hits, q_occ, q_map[3];
   DevBuf q_stack, q_ids, q_rgb;  // rtow_radiance*: the strict build's path stack (sized per launch), the host form's staging
+  DevBuf q_guides;               // rtow_guides: the host form's staging (rtow_camera_rays stages in q_rays / q_ids)
   bool q_map_ok[3] = {false, false, false};
   hipEvent_t q_ev[4] = {};
   unsigned long long *h_qcounters = nullptr;
@@ -542,7 +554,7 @@ void rtow_ctx_destroy(rtow_ctx *c) {
                     &c->blob32, &c->gblob32, &c->cam32_dev, &c->blob4,
                     &c->partials, &c->stack, &c->counters, &c->spill, &c->out, &c->out8, &c->rtree, &c->counters_init,
                     &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_occ, &c->q_map[0], &c->q_map[1],
-                    &c->q_map[2], &c->q_stack, &c->q_ids, &c->q_rgb,
+                    &c->q_map[2], &c->q_stack, &c->q_ids, &c->q_rgb, &c->q_guides,
                     &c->rf.map2, &c->rf.map4, &c->rf.par2, &c->rf.par4, &c->rf.need4, &c->rf.flags,
                     &c->rf.nbox2, &c->rf.nbox4, &c->rf.sbox4, &c->rf.pbox, &c->rf.partials, &c->rf.area, &c->rf.g_sph,
                     &c->rf.g_mov, &c->rf.g_tri, &c->tile_table})
@@ -2037,17 +2049,24 @@ static int resolve_point_kernel(rtow_ctx *c, int precision, int requested, int *
   return resident_kernel(c, precision, kernel, false, out);
 }
 
+// walk = false (rtow_camera_rays*: a kernel that reads the camera alone): the request is checked but no strategy is
+// resolved — q.kernel stays 0, and a lean upload, which built one strategy's structures only, is as good as a full one
 static int query_begin(rtow_ctx *c, int32_t precision, int32_t kernel_req, rtow_stats_t *stats, QueryRun &q,
-                       bool point = false) {
+                       bool point = false, bool walk = true) {
   if (precision == RTOW_F32) return fail(RTOW_EINVAL, "ray queries: RTOW_F32 is not supported (binary64 builds only)");
   if (precision != RTOW_F64_STRICT && precision != RTOW_F64_FAST) return fail(RTOW_EINVAL, "unknown precision %d", precision);
   if (kernel_req < RTOW_KERNEL_AUTO || kernel_req > RTOW_KERNEL_REFTREE) return fail(RTOW_EINVAL, "unknown kernel %d", kernel_req);
   if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
   HIPCHK(hipSetDevice(c->device));
   int rc;
-  if ((rc = point ? resolve_point_kernel(c, precision, kernel_req, &q.kernel) : resolve_kernel(c, precision, kernel_req, &q.kernel)))
-    return rc;
-  if ((rc = launch_shape(c, q.kernel, false, q.shape))) return rc;
+  if (!walk) {
+    q.kernel = 0;
+    q.shape.block = kBlock;
+  } else {
+    if ((rc = point ? resolve_point_kernel(c, precision, kernel_req, &q.kernel) : resolve_kernel(c, precision, kernel_req, &q.kernel)))
+      return rc;
+    if ((rc = launch_shape(c, q.kernel, false, q.shape))) return rc;
+  }
   q.strict = precision == RTOW_F64_STRICT;
   if (stats) {
     std::memset(stats, 0, sizeof *stats);
@@ -2233,6 +2252,147 @@ static int radiance_host(rtow_ctx *c, int32_t precision, int32_t kernel, const r
     return rc;
   HIPCHK(hipMemcpy(out, c->q_rgb.p, (size_t)n * 24, hipMemcpyDeviceToHost));
   return RTOW_OK;
+}
+
+// The camera stage (rtow_camera_rays*, rtow_guides*, csrc/rtow_guides.h): the queries' strategy, launch shape, ordering and
+// stats (query_begin / query_launch) around kernels that generate the render's primaries themselves.  CameraCall: what a
+// render of `cfg` would trace on this rank — its rows and its sample set (level_plan's strict form: the reference's).
+struct CameraCall {
+  int rows = 0;
+  long long npix = 0;         // rows * W
+  uint32_t sample_first = 0;  // stream_first * (spp / nstreams)
+  long long samples = 0;      // (spp / nstreams) * streams of the call
+};
+static int camera_call(const rtow_config_t *cfg, CameraCall &k) {
+  int rc = validate_cfg(cfg);
+  if (rc) return rc;
+  if (cfg->precision == RTOW_F32) return fail(RTOW_EINVAL, "camera rays / guides: RTOW_F32 is not supported (binary64 builds only)");
+  const long long spt = cfg->samples_per_pixel / cfg->nstreams;  // src/render.cpp:174
+  const long long streams_now = cfg->stream_count > 0 ? cfg->stream_count : cfg->nstreams;
+  if (spt * ((long long)cfg->stream_first + streams_now) > 0xffffffffLL) return fail(RTOW_EINVAL, "sample index beyond 32 bits");
+  k.rows = rtow_local_rows(cfg);
+  k.npix = (long long)k.rows * cfg->image_width;
+  k.sample_first = (uint32_t)((long long)cfg->stream_first * spt);
+  k.samples = spt * streams_now;
+  if (k.samples > 0x7fffffffLL) return fail(RTOW_EINVAL, "%lld samples per pixel in one call", k.samples);
+  return RTOW_OK;
+}
+// the camera's share of the launch parameters: what render_levels sets for the new-ray stage
+static void camera_params(const rtow_ctx *c, const rtow_config_t *cfg, const CameraCall &k, rtow::TraceParams &P) {
+  P.cam = (const rtow::DevCamera *)c->cam_dev.p;
+  P.W = cfg->image_width;
+  P.H = cfg->image_height;
+  P.inv_wm1 = 1.0 / (double)(cfg->image_width - 1);
+  P.inv_hm1 = 1.0 / (double)(cfg->image_height - 1);
+  P.rank = cfg->rank;
+  P.nranks = cfg->nranks;
+  P.tile_rows = cfg->tile_rows;
+  P.local_rows = k.rows;
+  P.seed_lo = (uint32_t)cfg->seed;
+  P.seed_hi = (uint32_t)(cfg->seed >> 32);
+}
+
+static int camera_rays_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_rays, void *d_ids, void *hip_stream) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  CameraCall k;
+  int rc;
+  if ((rc = camera_call(cfg, k))) return rc;
+  const long long n = k.npix * k.samples;  // (< 2^62)
+  if (n > kMaxQueryRays) return fail(RTOW_EINVAL, "rows * width * samples = %lld beyond 2^31 - 64", n);
+  if (n > 0 && !d_rays) return fail(RTOW_EINVAL, "NULL ray buffer");
+  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
+  if (((uintptr_t)d_ids & 7u) != 0u) return fail(RTOW_EINVAL, "ids buffer must be 8-byte aligned");
+  QueryRun q;
+  if ((rc = query_begin(c, cfg->precision, cfg->kernel, nullptr, q, false, false))) return rc;
+  if (n == 0) return RTOW_OK;
+  rtow::CameraRaysLaunchFn *const launch[2] = {rtow::launch_camera_rays_strict, rtow::launch_camera_rays_fast};
+  return query_launch(c, q, n, 8, hip_stream, nullptr, [&](const rtow::TraceParams &P0, unsigned long long *, int grid) {
+    rtow::TraceParams P = P0;
+    camera_params(c, cfg, k, P);
+    return launch[q.strict ? 0 : 1](P, d_rays, d_ids, (uint32_t)n, k.sample_first, (int32_t)k.samples, grid, q.shape.block,
+                                    hip_stream);
+  });
+}
+
+static int camera_rays_host(rtow_ctx *c, const rtow_config_t *cfg, rtow_ray_t *rays, uint32_t *ids) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  CameraCall k;
+  int rc;
+  if ((rc = camera_call(cfg, k))) return rc;
+  const long long n = k.npix * k.samples;  // (< 2^62)
+  if (n > kMaxQueryRays) return fail(RTOW_EINVAL, "rows * width * samples = %lld beyond 2^31 - 64", n);
+  if (n > 0 && !rays) return fail(RTOW_EINVAL, "NULL ray array");
+  if (n == 0) return camera_rays_device(c, cfg, nullptr, nullptr, nullptr);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_ray_t))) || (ids && (rc = c->q_ids.ensure((size_t)n * 8)))) return rc;
+  if ((rc = camera_rays_device(c, cfg, c->q_rays.p, ids ? c->q_ids.p : nullptr, nullptr))) return rc;
+  HIPCHK(hipMemcpy(rays, c->q_rays.p, (size_t)n * sizeof(rtow_ray_t), hipMemcpyDeviceToHost));
+  if (ids) HIPCHK(hipMemcpy(ids, c->q_ids.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return RTOW_OK;
+}
+
+static int guides_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_guides, void *hip_stream, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  CameraCall k;
+  int rc;
+  if ((rc = camera_call(cfg, k))) return rc;
+  // queue positions: 8 x 8 tiles over the rank's rows, 64 positions each (csrc/rtow_guides.h)
+  const long long tiles = (((long long)cfg->image_width + 7) / 8) * (((long long)k.rows + 7) / 8);
+  if (tiles * 64 > 0xfffffff0LL) return fail(RTOW_EINVAL, "too many pixels (%lld)", k.npix);
+  if (k.npix > 0 && !d_guides) return fail(RTOW_EINVAL, "NULL guide buffer");
+  if (((uintptr_t)d_guides & 15u) != 0u) return fail(RTOW_EINVAL, "guide buffer must be 16-byte aligned");
+  QueryRun q;
+  if ((rc = query_begin(c, cfg->precision, cfg->kernel, stats, q))) return rc;
+  if (stats) stats->local_rows = k.rows;
+  if (k.npix == 0) return RTOW_OK;
+  if (k.samples == 0) {  // fewer samples than streams: zero effective samples (src/render.cpp:174), zero sums
+    HIPCHK(hipMemsetAsync(d_guides, 0, (size_t)k.npix * sizeof(rtow_guide_t), (hipStream_t)hip_stream));
+    if (stats) HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
+    return RTOW_OK;
+  }
+  q.block_cap = c->knobs.guides_blocks;
+
+  const int kernel = q.kernel;
+  const int block = q.shape.block;
+  const unsigned lds = q.shape.lds_bytes;
+  const int build = q.strict ? 0 : 1;
+  rtow::GuidesLaunchFn *const launch[2] = {rtow::launch_guides_strict, rtow::launch_guides_fast};
+  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::guides_occupancy_strict, rtow::guides_occupancy_fast};
+  const int occ = occupancy[build](kernel, block, lds, nullptr);
+  rc = query_launch(c, q, tiles * 64, occ, hip_stream, stats, [&](const rtow::TraceParams &P0, unsigned long long *counters, int grid) {
+    rtow::TraceParams P = P0;
+    camera_params(c, cfg, k, P);
+    return launch[build](P, d_guides, (uint32_t)(tiles * 64), k.sample_first, (int32_t)k.samples, counters, kernel, grid, block,
+                         lds, hip_stream);
+  });
+  if (rc == RTOW_OK && stats) {
+    stats->samples = stats->segments = (uint64_t)k.npix * (uint64_t)k.samples;
+    if (kernel == RTOW_KERNEL_BRUTE) stats->prim_tests = stats->segments * (uint64_t)c->n_prims;  // (its walk tests all, uncounted)
+  }
+  return rc;
+}
+
+static int guides_host(rtow_ctx *c, const rtow_config_t *cfg, rtow_guide_t *guides, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  CameraCall k;
+  int rc;
+  if ((rc = camera_call(cfg, k))) return rc;
+  if (k.npix > 0 && !guides) return fail(RTOW_EINVAL, "NULL guide array");
+  if (k.npix == 0) return guides_device(c, cfg, nullptr, nullptr, stats);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = c->q_guides.ensure((size_t)k.npix * sizeof(rtow_guide_t)))) return rc;
+  if ((rc = guides_device(c, cfg, c->q_guides.p, nullptr, stats))) return rc;
+  HIPCHK(hipMemcpy(guides, c->q_guides.p, (size_t)k.npix * sizeof(rtow_guide_t), hipMemcpyDeviceToHost));
+  return RTOW_OK;
+}
+static_assert(sizeof(rtow_guide_t) == 64, "rtow_guide_t is four 16-byte stores");
+
+int64_t rtow_camera_ray_count(const rtow_config_t *cfg) {
+  CameraCall k;
+  if (int rc = camera_call(cfg, k)) return rc;
+  return (int64_t)(k.npix * k.samples);
 }
 
 // Diagnostic: copy a resident scene image to the host (0 BVH, 1 grid, 2 BVH of the f32 build,
@@ -2789,6 +2949,18 @@ int rtow_radiance_device(rtow_ctx *c, int32_t precision, int32_t kernel, const r
 int rtow_radiance(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params, const rtow_ray_t *rays,
                   int64_t n_rays, const uint32_t *ids, double *rgb_sums, rtow_stats_t *stats) {
   return guarded("rtow_radiance", [&] { return radiance_host(c, precision, kernel, params, rays, n_rays, ids, rgb_sums, stats); });
+}
+int rtow_camera_rays_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_rays, void *d_ids, void *hip_stream) {
+  return guarded("rtow_camera_rays_device", [&] { return camera_rays_device(c, cfg, d_rays, d_ids, hip_stream); });
+}
+int rtow_camera_rays(rtow_ctx *c, const rtow_config_t *cfg, rtow_ray_t *rays, uint32_t *ids) {
+  return guarded("rtow_camera_rays", [&] { return camera_rays_host(c, cfg, rays, ids); });
+}
+int rtow_guides_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_guides, void *hip_stream, rtow_stats_t *stats) {
+  return guarded("rtow_guides_device", [&] { return guides_device(c, cfg, d_guides, hip_stream, stats); });
+}
+int rtow_guides(rtow_ctx *c, const rtow_config_t *cfg, rtow_guide_t *guides, rtow_stats_t *stats) {
+  return guarded("rtow_guides", [&] { return guides_host(c, cfg, guides, stats); });
 }
 int rtow_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
   return guarded("rtow_scene_refit", [&] { return impl_scene_refit(c, s); });

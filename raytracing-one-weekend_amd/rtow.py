@@ -132,6 +132,11 @@ class PointHit(C.Structure):
     ]
 
 
+class Guide(C.Structure):
+    """rtow_guide_t (64 B): per-pixel SUMS over the pixel's samples of first-hit albedo, unit normal, distance, hits."""
+    _fields_ = [("albedo", d3), ("normal", d3), ("depth", C.c_double), ("hits", C.c_double)]
+
+
 class RadianceParams(C.Structure):
     """rtow_radiance_params_t (24 B): Philox key, samples per ray, depth, offset of every ray's first sample index."""
     _fields_ = [("seed", C.c_uint64), ("samples_per_ray", C.c_int32), ("max_child_rays", C.c_int32),
@@ -142,6 +147,9 @@ class RadianceParams(C.Structure):
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("time", "<f8"), ("direction", "<f8", (3,)), ("tmax", "<f8")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("prim", "<i4"), ("kind", "<i4"),
                       ("material", "<i4"), ("front_face", "<i4")])
+
+# rtow_guide_t (rtow_guides*): per-pixel SUMS over the pixel's samples
+GUIDE_DTYPE = np.dtype([("albedo", "<f8", (3,)), ("normal", "<f8", (3,)), ("depth", "<f8"), ("hits", "<f8")])
 
 
 # rtow_point_query_t / rtow_point_hit_t (rtow_closest_point*)
@@ -188,6 +196,7 @@ EXPORTS = [
     "rtow_intersect_device", "rtow_intersect", "rtow_occluded_device", "rtow_occluded",
     "rtow_scene_refit", "rtow_refit_info", "rtow_closest_point_device", "rtow_closest_point",
     "rtow_debug_tile_order", "rtow_radiance_device", "rtow_radiance",
+    "rtow_camera_rays_device", "rtow_camera_rays", "rtow_camera_ray_count", "rtow_guides_device", "rtow_guides",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -284,6 +293,13 @@ def lib():
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rtow_radiance.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RadianceParams), C.c_void_p, C.c_int64,
                                     C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    if hasattr(L, "rtow_guides"):
+        L.rtow_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rtow_camera_rays.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p]
+        L.rtow_camera_ray_count.argtypes = [C.POINTER(Config)]
+        L.rtow_camera_ray_count.restype = C.c_int64
+        L.rtow_guides_device.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rtow_guides.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.POINTER(Stats)]
     if hasattr(L, "rtow_scene_refit"):
         L.rtow_scene_refit.argtypes = [C.c_void_p, C.POINTER(Scene)]
         L.rtow_refit_info.argtypes = [C.c_void_p, C.POINTER(RefitInfo)]
@@ -590,6 +606,46 @@ class Context:
                                          C.c_void_p(d_ids) if d_ids else None, C.c_void_p(d_rgb), C.c_void_p(stream),
                                          C.byref(st) if st is not None else None),
               "rtow_radiance_device")
+        return st
+
+    def camera_rays(self, cfg: Config):
+        """The primaries a render of `cfg` generates on this rank, from the resident camera: (rays, ids) — a RAY_DTYPE
+        array of rows x W x samples rays, pixel-major with a pixel's samples ascending, and the [n, 2] uint32 (global
+        pixel, sample) Philox identities `radiance` takes (rtow_camera_rays)."""
+        n = lib().rtow_camera_ray_count(C.byref(cfg))
+        if n < 0:
+            check(int(n), "rtow_camera_ray_count")
+        rays = np.empty(n, dtype=RAY_DTYPE)
+        ids = np.empty((n, 2), dtype=np.uint32)
+        check(lib().rtow_camera_rays(self._h, C.byref(cfg), rays.ctypes.data_as(C.c_void_p),
+                                     ids.ctypes.data_as(C.c_void_p)), "rtow_camera_rays")
+        return rays, ids
+
+    def camera_rays_device(self, cfg: Config, d_rays: int, d_ids: int = 0, stream: int = 0):
+        """The same into device buffers (raw pointers: n x 64-byte rays, n x 2 uint32 ids or 0), enqueued on `stream`
+        (rtow_camera_rays_device)."""
+        check(lib().rtow_camera_rays_device(self._h, C.byref(cfg), C.c_void_p(d_rays), C.c_void_p(d_ids) if d_ids else None,
+                                            C.c_void_p(stream)), "rtow_camera_rays_device")
+
+    def guides(self, cfg: Config, want_stats=False):
+        """First-hit guide buffers of this rank's rows for a denoiser: a [rows, W] GUIDE_DTYPE array of SUMS over the
+        samples a render of `cfg` traces (albedo, unit normal, distance, hit count), and Stats with `want_stats`
+        (rtow_guides)."""
+        rows = lib().rtow_local_rows(C.byref(cfg))
+        if rows < 0:
+            check(rows, "rtow_local_rows")
+        out = np.empty((rows, cfg.image_width), dtype=GUIDE_DTYPE)
+        st = Stats() if want_stats else None
+        check(lib().rtow_guides(self._h, C.byref(cfg), out.ctypes.data_as(C.c_void_p),
+                                C.byref(st) if st is not None else None), "rtow_guides")
+        return (out, st) if want_stats else out
+
+    def guides_device(self, cfg: Config, d_guides: int, stream: int = 0, want_stats=False):
+        """The same into a device buffer (raw pointer: rows x W x 64 bytes, 16-byte aligned), enqueued on `stream`
+        (rtow_guides_device); returns Stats with `want_stats` (then synchronised), else None."""
+        st = Stats() if want_stats else None
+        check(lib().rtow_guides_device(self._h, C.byref(cfg), C.c_void_p(d_guides), C.c_void_p(stream),
+                                       C.byref(st) if st is not None else None), "rtow_guides_device")
         return st
 
     def profile_collect(self):
