@@ -306,6 +306,12 @@ int rtow_debug_counters(rtow_ctx *ctx, unsigned long long *out48);
  * without a GPU). */
 int rtow_debug_schedule(rtow_ctx *ctx, const rtow_config_t *cfg, uint32_t *out_pairs, int32_t capacity_pairs);
 
+/* Diagnostic only: which specialisation of the GRID trace kernel the last trace launch of `ctx` took: 0 generic, 1
+ * static spheres, 2 static + moving spheres, | 4 the two-axis walk of a grid with one layer of cells in y (both cover
+ * scenes).  RTOW_NO_SPEC in the environment of rtow_ctx_create keeps 0, RTOW_NO_FLAT keeps the bit 4 clear.
+ * RTOW_ENOSCENE before the first launch. */
+int rtow_debug_last_spec(rtow_ctx *ctx, uint32_t *out_spec);
+
 /* Diagnostic only (pure host arithmetic, usable without a GPU): the order in which the work queue of a render of
  * `cfg` of `scene` runs its 64-pixel tiles.  table_out[queue position] = tile (row-major over this rank's tile rows;
  * the queue is consumed from its far end, so position 0 runs LAST), empty_out[tile] = 1 when no ray the camera can

@@ -333,6 +333,8 @@ struct Knobs {
   bool stream_scalar = false;     // RTOW_STREAM_SCALAR: the STREAM kernel's triangle loop through scalar loads at every size (A/B
                                   //   against the LDS-tiled loop; rounds 1-5a)
   bool no_spec = false;           // RTOW_NO_SPEC: always the generic GRID kernel (A/B against the scene-class specialisations)
+  bool no_flat = false;           // RTOW_NO_FLAT: the scene-class kernels keep the 3D walk on a grid with one layer in y (A/B and
+                                  //   tests against the two-axis walk, kSpecFlatY)
   bool tile_order = true;         // RTOW_TILE_ORDER=0: the queue keeps the row order alone (one segment); default: the tiles through
                                   //   which no camera ray can reach a primitive are traced last (tile_classify)
   int empty_levels = 3;           // RTOW_EMPTY_LEVELS: levels of a tile one atomic buys in the queue's empty-tile segment (1..16)
@@ -389,6 +391,7 @@ struct Knobs {
     tile_order = geti("RTOW_TILE_ORDER", 1) != 0;
     empty_levels = std::min(std::max(geti("RTOW_EMPTY_LEVELS", 3), 1), 16);
     no_spec = std::getenv("RTOW_NO_SPEC") != nullptr;
+    no_flat = std::getenv("RTOW_NO_FLAT") != nullptr;
     stream_scalar = std::getenv("RTOW_STREAM_SCALAR") != nullptr;
     if (const char *e = std::getenv("RTOW_PLOC_RADIUS")) ploc_radius = std::min(std::max(std::atoi(e), 0), 64);
     if (const char *e = std::getenv("RTOW_DEVICE_TREE"))
@@ -422,6 +425,8 @@ struct rtow_ctx {
   rtow::DevScene ds32{};               // ds with the f32 images' pointers and offsets
   uint32_t gblob_bytes = 0;
   uint32_t grid_fat_stride = 0;  // bytes per fat cell-list entry of the resident grid image (0: plain id lists)
+  int32_t grid_ny = 0;           // n[1] of the resident grid image's header (0: no grid); 1 selects the two-axis walk
+  int64_t last_spec = -1;        // TraceParams::spec of the last trace launch (rtow_debug_last_spec; -1: none yet)
   bool have_grid = false;
   uint32_t blob_bytes = 0;
   long long bvh_nodes = 0;
@@ -1013,6 +1018,7 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
   const double t_grid1 = now_ms();
   c->have_grid = gimg.ok;
   c->grid_fat_stride = (gimg.ok && gimg.off_fat) ? gimg.fat_stride : 0u;
+  c->grid_ny = gimg.ok ? gimg.n[1] : 0;
   c->gblob_bytes = 0;
   if (gimg.ok) {
     if (!grid_on_device && (rc = upload(c->gblob, gimg.blob))) return rc;
@@ -1813,6 +1819,9 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
   if (kernel == RTOW_KERNEL_GRID && lds_bytes > 0 && !f32 && !c->knobs.no_spec && scene.n_tri == 0) {
     if (scene.n_mov == 0 && c->grid_fat_stride == 48u) P.spec = rtow::kSpecStaticSpheres;
     if (scene.n_mov > 0 && c->grid_fat_stride == 80u) P.spec = rtow::kSpecMovingSpheres;
+    // ... and on top of either class, a grid with one layer of cells in y (both cover scenes): the two-axis walk.  From
+    // the header of the image that is resident NOW (every upload and refit, host- or device-built, sets grid_ny)
+    if (P.spec != rtow::kSpecGeneric && c->grid_ny == 1 && !c->knobs.no_flat) P.spec |= rtow::kSpecFlatY;
   }
   P.b4_trips = c->knobs.bvh4_sm ? 0u : 1u;
   {
@@ -1870,6 +1879,7 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
   }
 #endif
   if (lrc != 0) return fail(RTOW_EHIP, "trace kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  c->last_spec = (int64_t)P.spec;
   if (slot >= 0) {
     HIPCHK(hipEventRecord(c->ev[slot][1], st));
     c->ev_count++;
@@ -2456,6 +2466,14 @@ int rtow_debug_counters(rtow_ctx *c, unsigned long long *out48) {
   return RTOW_OK;
 }
 
+// Diagnostic: TraceParams::spec of the last trace launch (rtow_device.h kSpec*): which instantiation of the GRID kernel ran.
+int rtow_debug_last_spec(rtow_ctx *c, uint32_t *out_spec) {
+  if (!c || !out_spec) return fail(RTOW_EINVAL, "NULL argument");
+  if (c->last_spec < 0) return fail(RTOW_ENOSCENE, "no launch yet");
+  *out_spec = (uint32_t)c->last_spec;
+  return RTOW_OK;
+}
+
 // write_color as a device epilogue: 8-bit RGB from the radiance sums.
 int rtow_tonemap_device(rtow_ctx *c, const void *d_rgb_sums, int64_t n_values, int32_t spp_effective,
                         void *d_rgb8, void *hip_stream) {
@@ -2793,6 +2811,7 @@ static int impl_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
   if (c->built & kNeedGrid) {
     c->have_grid = gimg.ok;
     c->grid_fat_stride = (gimg.ok && gimg.off_fat) ? gimg.fat_stride : 0u;
+    c->grid_ny = gimg.ok ? gimg.n[1] : 0;
     c->gblob_bytes = gimg.ok ? (uint32_t)gimg.total_bytes : 0u;
     ds.gblob = (const unsigned char *)c->gblob.p;
     ds.gblob_bytes = c->gblob_bytes;

@@ -130,7 +130,8 @@ struct TraceParams {
   uint32_t *stack;         // [max_child_rays][n_lanes] material index per bounce
   uint32_t *spill;         // BVH4 kernel: traversal stack entries beyond the LDS part, [entry][n_lanes]
   uint32_t spec;           // GRID kernel: scene-class specialisation of the code (0 generic; 1 static spheres only with
-                           // 48-byte fat cell lists; 2 static + moving spheres with 80-byte fat lists) — see kSpec* below
+                           // 48-byte fat cell lists; 2 static + moving spheres with 80-byte fat lists; | 4: one layer of
+                           // cells in y) — see kSpec* below
   uint32_t b4_trips;       // BVH4: 1 = the trip-structured kernel (rtow_trace_body.h, default), 0 = the state machine
   uint32_t fetch_votes;              // trip kernels: lanes that must need a new work item before the fetch block runs
   uint32_t leaf_votes;               // GRID / BVH4 walks: lanes that must hold a queued cell / leaf before a leaf phase runs
@@ -147,6 +148,11 @@ struct TraceParams {
 // registers (127 VGPRs and a private segment against 118 and none) and code layout: the specialised instantiation is
 // 3.5 % faster on the cover scene.  The host picks it from the resident scene (rtow_capi.cpp); the image is the same.
 constexpr uint32_t kSpecGeneric = 0u, kSpecStaticSpheres = 1u, kSpecMovingSpheres = 2u;
+// A bit on top of class 1 or 2: the resident grid has a single layer of cells in y (grid_header() of rtow_grid.h
+// collapses a thin axis: both cover scenes), and the walk is the two-axis DDA of rtow_dda_step.h — same cells, same
+// order, same counters, no y state.  Decided per render from the resident header (rtow_capi.cpp); RTOW_NO_FLAT keeps
+// the class without the bit.
+constexpr uint32_t kSpecFlatY = 4u;
 
 struct ReduceParams {
   const double *partials;  // [stream][tiled pixel][3]

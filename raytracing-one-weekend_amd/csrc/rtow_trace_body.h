@@ -297,7 +297,8 @@ __device__ __forceinline__ bool scatter_dir(Rng &g, uint32_t k0, uint32_t k1, in
 
 // KERNEL: 1 = STREAM, 2 = BVH, 3 = GRID, 4 = BVH4;  LDS: scene image staged in LDS (2 and 3; the
 // BVH4 kernel always uses LDS: the image or its top, and the traversal stack)
-// SPEC: scene-class specialisation (GRID kernel only; rtow_device.h kSpec*)
+// SPEC: scene-class specialisation (GRID kernel only; rtow_device.h kSpec*): the class in its low two bits, | kSpecFlatY
+// for the two-axis walk of a grid with one layer in y
 template <int KERNEL, bool LDS, bool STAMPS = false, int SPEC = 0>
 __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     RTOW_CAT(rtow_trace_, RTOW_SUFFIX)(const TraceParams P) {
@@ -610,8 +611,8 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
         const uint32_t o_tri = KERNEL == 3 ? sc.g_off_tri : sc.off_tri;
         const uint32_t o_pmat = KERNEL == 3 ? sc.g_off_pmat : sc.off_pmat;
         const uint32_t o_mats = KERNEL == 3 ? sc.g_off_mats : sc.off_mats;
-        if constexpr (SPEC == 1) __builtin_assume(pid < sc.n_sph);
-        if constexpr (SPEC == 2) __builtin_assume(pid < sc.n_sph + sc.n_mov);
+        if constexpr ((SPEC & 3) == 1) __builtin_assume(pid < sc.n_sph);
+        if constexpr ((SPEC & 3) == 2) __builtin_assume(pid < sc.n_sph + sc.n_mov);
         if (pid < sc.n_sph + sc.n_mov) {
           V3 center;
           bool inward;  // negative radius: only the sign of the signed r*r is used here
@@ -845,8 +846,8 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
                                            P.walk_cap, P.walk_max_open);
     } else if constexpr (KERNEL == 3) {
       if constexpr (STAMPS) stamps.primary = __ballot(tracing && depth == P.max_child_rays);
-      best = closest_hit_grid<LDS, STAMPS, SPEC>(im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps, best, t_resume, P.walk_cap,
-                                           P.walk_max_open, P.leaf_votes);
+      best = closest_hit_grid<LDS, STAMPS, (SPEC & 3), (SPEC & (int)kSpecFlatY) != 0>(
+          im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps, best, t_resume, P.walk_cap, P.walk_max_open, P.leaf_votes);
     } else if constexpr (KERNEL == 2) {
       // the walk uses wave votes, so every lane of the wave enters it
       best = closest_hit_bvh<LDS, STAMPS>(im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps);
@@ -1010,6 +1011,8 @@ static KernelVariant<TraceParams> trace_variant(int kernel, unsigned lds_bytes, 
     case 3:
       if (lds && spec == kSpecStaticSpheres) return trace_kernel<3, true, false, 1>(lds_bytes);
       if (lds && spec == kSpecMovingSpheres) return trace_kernel<3, true, false, 2>(lds_bytes);
+      if (lds && spec == (kSpecStaticSpheres | kSpecFlatY)) return trace_kernel<3, true, false, 1 | (int)kSpecFlatY>(lds_bytes);
+      if (lds && spec == (kSpecMovingSpheres | kSpecFlatY)) return trace_kernel<3, true, false, 2 | (int)kSpecFlatY>(lds_bytes);
       return lds ? trace_kernel<3, true, false>(lds_bytes) : trace_kernel<3, false, false>(0);
     case 4:
       if (b4_trips) return b4_full ? trace_kernel<4, true, false>(lds_bytes) : trace_kernel<4, false, false>(lds_bytes);

@@ -1,6 +1,7 @@
 // rtow_trace_grid.h — part of the trace kernels (included by rtow_trace_body.h inside namespace rtow::{anonymous};
 // see that file for the execution model).  The uniform-grid (3D-DDA) walk.
 #pragma once
+#include "rtow_dda_step.h"
 // --------------------------------------------------------- closest hit: GRID ---
 // 3D-DDA over the uniform grid of rtow_grid.h.  Primitives far larger than the rest (the
 // ground sphere) are not in the grid; every ray tests that short list first.  Cells are
@@ -19,7 +20,10 @@
 // point or its predecessor, so no cell is skipped; a cell tested twice changes nothing).  Because of that
 // step back, `cap` must be at least 3 (the host clamps it): at most two consecutive cell crossings share one
 // ray parameter, so three steps always end in a cell that starts later than the one the lane resumed in.
-template <bool LDS, bool ST, int SPEC = 0>
+//
+// FLAT (kSpecFlatY, rtow_device.h): the resident grid has ONE layer of cells in y.  The set-up and the step are the
+// two-axis forms of rtow_dda_step.h: same cells in the same order, same t_entry; everything else is untouched.
+template <bool LDS, bool ST, int SPEC = 0, bool FLAT = false>
 __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const DevScene &sc, V3 o,
                                                     V3 d, real time, bool active, uint32_t &nnode,
                                                     uint32_t &nprim, Stamps<ST> &stamps, Closest best,
@@ -122,20 +126,35 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
   const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tmax32));
   bool walking = active && t0 <= t1 * 1.00002f;
 
-  // starting cell and DDA state
-  const float px = fmaf(t0, dx, ox), py = fmaf(t0, dy, oy), pz = fmaf(t0, dz, oz);
-  int c0 = (int)floorf((px - gx) * icx), c1 = (int)floorf((py - gy) * icy), c2 = (int)floorf((pz - gz) * icz);
-  c0 = min(max(c0, 0), nx - 1);
-  c1 = min(max(c1, 0), ny - 1);
-  c2 = min(max(c2, 0), nz - 1);
+  // starting cell and DDA state (rtow_dda_step.h)
   const bool fx = dx >= 0.0f, fy = dy >= 0.0f, fz = dz >= 0.0f;
-  float tmx = fmaf(fmaf((float)(c0 + (fx ? 1 : 0)), cx, gx), ix, -oix);
-  float tmy = fmaf(fmaf((float)(c1 + (fy ? 1 : 0)), cy, gy), iy, -oiy);
-  float tmz = fmaf(fmaf((float)(c2 + (fz ? 1 : 0)), cz, gz), iz, -oiz);
-  const float tdx = fabsf(cx * ix), tdy = fabsf(cy * iy), tdz = fabsf(cz * iz);
-  int remx = fx ? nx - 1 - c0 : c0, remy = fy ? ny - 1 - c1 : c1, remz = fz ? nz - 1 - c2 : c2;
-  const int incx = fx ? 1 : -1, incy = fy ? nx : -nx, incz = fz ? nx * ny : -(nx * ny);
-  int idx = (c2 * ny + c1) * nx + c0;
+  const float tdx = fabsf(cx * ix), tdz = fabsf(cz * iz);
+  const float px = fmaf(t0, dx, ox), pz = fmaf(t0, dz, oz);
+  int c0 = (int)floorf((px - gx) * icx), c2 = (int)floorf((pz - gz) * icz);
+  c0 = min(max(c0, 0), nx - 1);
+  c2 = min(max(c2, 0), nz - 1);
+  typename DdaWalkOf<FLAT>::type w;
+  w.tmx = fmaf(fmaf((float)(c0 + (fx ? 1 : 0)), cx, gx), ix, -oix);
+  w.tmz = fmaf(fmaf((float)(c2 + (fz ? 1 : 0)), cz, gz), iz, -oiz);
+  w.tdx = tdx, w.tdz = tdz;
+  w.remx = fx ? nx - 1 - c0 : c0, w.remz = fz ? nz - 1 - c2 : c2;
+  w.incx = fx ? 1 : -1;
+  if constexpr (FLAT) {
+    // one layer in y (the host checked the header: ny == 1): the y cell is 0, its far wall is the slab's exit plane —
+    // the generic tmy, fmaf(fmaf((float)(fy ? 1 : 0), cy, gy), iy, -oiy), is `by` or `ay` of the clip above
+    w.ty_exit = fy ? by : ay;
+    w.incz = fz ? nx : -nx;
+    w.idx = c2 * nx + c0;
+  } else {
+    const float py = fmaf(t0, dy, oy);
+    int c1 = (int)floorf((py - gy) * icy);
+    c1 = min(max(c1, 0), ny - 1);
+    w.tmy = fmaf(fmaf((float)(c1 + (fy ? 1 : 0)), cy, gy), iy, -oiy);
+    w.tdy = fabsf(cy * iy);
+    w.remy = fy ? ny - 1 - c1 : c1;
+    w.incy = fy ? nx : -nx, w.incz = fz ? nx * ny : -(nx * ny);
+    w.idx = (c2 * ny + c1) * nx + c0;
+  }
 
   stage_prio<kPrioStage>();
   uint32_t q0 = 0u, q1 = 0u;
@@ -149,7 +168,7 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
       if (m_step != 0ull && (m_step & ~stamps.primary) == 0ull) stamps.iters_cam += 1;
     }
     if (walking && q1 == 0u) {  // (a lane with two cells queued waits for the next leaf phase)
-      const uint32_t cw = im.u32(sc.g_off_cells + 4u * (uint32_t)idx);
+      const uint32_t cw = im.u32(sc.g_off_cells + 4u * (uint32_t)w.idx);
       ++nnode;
       if (cw != 0u) {
         if (q0 == 0u)
@@ -157,20 +176,7 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
         else
           q1 = cw;
       }
-      // leave through the nearest cell wall (x before y before z when equal): one v_min3 and two equality tests
-      const float tnext = fminf(fminf(tmx, tmy), tmz);
-      const bool sx = tmx == tnext;
-      const bool sy = !sx && tmy == tnext;
-      const int rem = sx ? remx : (sy ? remy : remz);
-      walking = rem > 0 && !(tnext > tmax32);
-      t_entry = tnext;
-      idx += sx ? incx : (sy ? incy : incz);
-      tmx += sx ? tdx : 0.0f;
-      tmy += sy ? tdy : 0.0f;
-      tmz += (!sx && !sy) ? tdz : 0.0f;
-      remx -= sx ? 1 : 0;
-      remy -= sy ? 1 : 0;
-      remz -= (!sx && !sy) ? 1 : 0;
+      walking = dda_step(w, tmax32, t_entry);
     }
     const unsigned long long m_walking = __ballot(walking);
     const bool any_walking = m_walking != 0ull;

@@ -25,6 +25,7 @@ MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2
 PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_TRIANGLE = 0, 1, 2
 F64_STRICT, F64_FAST, F32 = 0, 1, 2
 KERNEL_AUTO, KERNEL_BRUTE, KERNEL_BVH, KERNEL_GRID, KERNEL_BVH4, KERNEL_REFTREE = 0, 1, 2, 3, 4, 5
+SPEC_GENERIC, SPEC_STATIC_SPHERES, SPEC_MOVING_SPHERES, SPEC_FLAT_Y = 0, 1, 2, 4  # Context.last_spec()
 MODEL_OO, MODEL_VARIANT, MODEL_WORLD = 0, 1, 2  # scene models of the host scene scripts (include/rtow.h)
 BUILDER_HOST_SAH, BUILDER_DEVICE_LBVH, BUILDER_AUTO = 0, 1, 2
 
@@ -197,6 +198,7 @@ EXPORTS = [
     "rtow_scene_refit", "rtow_refit_info", "rtow_closest_point_device", "rtow_closest_point",
     "rtow_debug_tile_order", "rtow_radiance_device", "rtow_radiance",
     "rtow_camera_rays_device", "rtow_camera_rays", "rtow_camera_ray_count", "rtow_guides_device", "rtow_guides",
+    "rtow_debug_last_spec",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -310,6 +312,8 @@ def lib():
         L.rtow_debug_tile_order.argtypes = [C.POINTER(Scene), C.POINTER(Config), C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_ubyte), C.c_int32, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    if hasattr(L, "rtow_debug_last_spec"):
+        L.rtow_debug_last_spec.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     ver = L.rtow_abi_version()
     if ver != RTOW_ABI_VERSION and not ("RTOW_LIB" in os.environ and ver >= 4):  # (older builds: A/B runs only)
         raise RtowError("librtow.so ABI version mismatch")
@@ -457,6 +461,13 @@ class Context:
         buf = (C.c_ubyte * max(n.value, 1))()
         check(lib().rtow_debug_image(self._h, which, buf, n.value, C.byref(n)), "rtow_debug_image")
         return bytes(buf[:n.value])
+
+    def last_spec(self) -> int:
+        """Specialisation of the GRID trace kernel the last trace launch took (rtow_debug_last_spec): 0 generic, 1 static
+        spheres, 2 static + moving spheres, | SPEC_FLAT_Y for the two-axis walk of a grid with one layer in y."""
+        v = C.c_uint32()
+        check(lib().rtow_debug_last_spec(self._h, C.byref(v)), "rtow_debug_last_spec")
+        return int(v.value)
 
     def build_info(self) -> BuildInfo:
         bi = BuildInfo()
