@@ -29,6 +29,26 @@ change its answer is, and the gap between its nearest and its second-nearest hit
     to 17 for the contractions: every fma saves one rounding in each of the eight two-term sums above).  The fat 48-byte
     cell-list entries test h = o.d - C.d and c' = |o|^2 - 2 C.o + (|C|^2 - r^2) in WORLD coordinates, so fast S_q takes
     |o_i| + |c_i| where strict takes |o_i - c_i|.  tau_fast = 2 * 17 u = 34 u.
+  * f32 (RTOW_F32: rtow_trace_f32.hip; sphere_test<float> / triangle_test<float> of rtow_trace_hit.h on the binary32
+    records of leaf_test, rtow_trace_bvh.h; u32 = 2^-24).  Every record word is the binary64 record's rounded (1).
+    Sphere, the strict form oc = o - c on rounded o and c, so S takes |o_i| + |c_i| like the fast world form: the
+    moving centre c0 + time * delta (delta 1, product 2, sum 3), oc (4), h (7), c' (+1 for the record's r^2: 8), disc
+    (10).  Triangle, the det-multiplied form: det = -d.n (n 1, +3: 4), ao = o - A (2), ao x d (4), ud, vd (7),
+    ud + vd <= det (8), td = ao.n (5), tmin * det (5): 8.  K32_ARITH = 10 is this arithmetic alone.  The ray: a primary
+    is llc + u h + v w - from in binary32 (rtow_trace_body.h): cam32 (1), u = (j + ju) * inv_wm1 (sum 1, product 2),
+    u * h (3), + llc (4), + v * w (5), - from (6) — K_CAM = 6 roundings on the magnitudes |llc_i| + |u h_i| + |v w_i| +
+    |from_i|, which stand for |d_i| (and |origin_i| + the lens offset for |o_i|) in S_q; the quadratic terms of disc
+    see them twice (+12 on 10): K32 = 22, no discount for contractions (they are the compiler's choice), tau_f32 =
+    2 * 22 u32 = 44 u32.  fast_rcp / fast_rsqrt / fast_sqrt for float (rtow_trace_math.h: the hardware's 1 ulp
+    seed, one Newton step on rcp and rsq) are within these counts like the fast build's.  The binary32 Closest::t
+    adds u32 |t| to every t bound (also to those of spheres tested in binary64).  Spheres that a kernel tests in
+    binary64 on the widened ray (the GRID walk's large list, every sphere of the BVH and STREAM kernels) see the
+    ray's error alone: `large`.  Because S_q on |o_i| + |c_i| overstates the strict form's error by (|o| + |c|) /
+    |o - c| squared, a second bound stands beside it where the ray's error is known in absolute terms (operr, derr):
+    TAU_ARITH S_q' + 2 D_q with S_q' on |o_i - c_i|, and for a sphere D_disc = 2 a max(|r|, b) |do + s dd| + |disc| da / a
+    (disc = a (r^2 - b^2): the line moves by |do + s dd| at its point nearest the centre) and the t bound through
+    dt = (p - c).(do + t dd) / sqrt(disc); tests/test_f32_audit_host.py holds both bounds to binary32 restatements of
+    the tests.
   * every other test in the fast build (1/a by rcp + Newton, t = td * rcp(det), the t * det forms of the triangle test)
     is within those counts.
   * tmin / tmax against a root t: decided when |t - tmin| (|t - tmax|) exceeds t's bound E_t (below).
@@ -62,13 +82,21 @@ import numpy as np
 U = 2.0 ** -53
 TMIN = 0.001
 CUT = 1e-6
-STRICT, FAST = "strict", "fast"
-TAU = {STRICT: 18 * U, FAST: 34 * U}
+U32 = 2.0 ** -24
+STRICT, FAST, F32 = "strict", "fast", "f32"
+K32 = 22  # (the header's count for the binary32 build)
+K32_ARITH = 10  # (... of the binary32 tests alone, on the values they are given)
+TAU = {STRICT: 18 * U, FAST: 34 * U, F32: 2 * K32 * U32}
+TAU_ARITH = 2 * K32_ARITH * U32
 GF = 32 * U
 SPHERE, MOVING, TRIANGLE = 0, 1, 2
 MISS, HIT, UND = 0, 1, 2
 _SQRT_BITS = 130
 _FTMIN, _FCUT = Fr(TMIN), Fr(CUT)
+
+
+def _second(x, y):
+    return y
 
 
 class CheckError(AssertionError):
@@ -155,8 +183,13 @@ def _gt(x: Fr, band: float) -> bool:
 
 
 # ---- the exact path, one pair ---------------------------------------------------------------------------------------
-def exact_triangle(o, d, tmax, A, B, C, tau, unit_cut=False):
-    """(hit, decided-or-not outcome, t Fraction, E, outs): see Cand."""
+def _cross_abs(x, y):
+    return [x[1] * y[2] + y[1] * x[2], x[2] * y[0] + y[2] * x[0], x[0] * y[1] + y[0] * x[1]]
+
+
+def exact_triangle(o, d, tmax, A, B, C, tau, unit_cut=False, u=U, aomag=None, dmag=None, pert=None):
+    """(hit, decided-or-not outcome, t Fraction, E, outs): see Cand.  aomag, dmag: the magnitudes that stand for
+    |o - A| and |d| in S (the binary32 build: rounded inputs, camera rays), default the operands' own."""
     o, d, A, B, C = _f3(o), _f3(d), _f3(A), _f3(B), _f3(C)
     e1 = [B[k] - A[k] for k in range(3)]
     e2 = [C[k] - A[k] for k in range(3)]
@@ -167,29 +200,52 @@ def exact_triangle(o, d, tmax, A, B, C, tau, unit_cut=False):
     ud, vd, td = _dot(e2, dao), -_dot(e1, dao), _dot(ao, n)
     fa = lambda v: [abs(float(x)) for x in v]  # noqa: E731
     E1a, E2a, AOa, Da = fa(e1), fa(e2), fa(ao), fa(d)
+    if aomag is not None:
+        AOa = [float(x) for x in aomag]
+    if dmag is not None:
+        Da = [float(x) for x in dmag]
     Na = [E1a[1] * E2a[2] + E2a[1] * E1a[2], E1a[2] * E2a[0] + E2a[2] * E1a[0], E1a[0] * E2a[1] + E2a[0] * E1a[1]]
     DAOa = [AOa[1] * Da[2] + Da[1] * AOa[2], AOa[2] * Da[0] + Da[2] * AOa[0], AOa[0] * Da[1] + Da[0] * AOa[1]]
     S_det, S_ud, S_vd, S_td = (sum(x * y for x, y in zip(p, q)) for p, q in ((Da, Na), (E2a, DAOa), (E1a, DAOa), (AOa, Na)))
+    if pert is None:
+        b_det, b_ud, b_vd, b_td = tau * S_det, tau * S_ud, tau * S_vd, tau * S_td
+        b_sum = tau * (S_det + S_ud + S_vd)
+    else:  # absolute input errors eo, ed: first-order terms D_q beside the arithmetic band taub on the plain magnitudes
+        eo, ed, aonat, taub, comb = pert
+        Dn = fa(d)
+        DAOn = _cross_abs(aonat, Dn)
+        DAOe = [x + y for x, y in zip(_cross_abs(eo, Dn), _cross_abs(fa(ao), ed))]
+        sm = lambda p, q: sum(x * y for x, y in zip(p, q))  # noqa: E731
+        n_det, n_ud, n_vd, n_td = sm(Dn, Na), sm(E2a, DAOn), sm(E1a, DAOn), sm(aonat, Na)
+        D_det, D_ud, D_vd, D_td = sm(ed, Na), sm(E2a, DAOe), sm(E1a, DAOe), sm(eo, Na)
+        b_det = comb(tau * S_det, taub * n_det + 2 * D_det)
+        b_ud = comb(tau * S_ud, taub * n_ud + 2 * D_ud)
+        b_vd = comb(tau * S_vd, taub * n_vd + 2 * D_vd)
+        b_td = comb(tau * S_td, taub * n_td + 2 * D_td)
+        b_sum = b_det + b_ud + b_vd
     dd = _dot(d, d)
     if unit_cut:  # det >= 1e-6 |d|
         ok_cut = det >= 0 and det * det >= _FCUT * _FCUT * dd
-        hi, lo = det - Fr(tau * S_det), det + Fr(tau * S_det)  # decided: det -+ band both on one side of 1e-6 |d|
+        hi, lo = det - Fr(b_det), det + Fr(b_det)  # decided: det -+ band both on one side of 1e-6 |d|
         above = hi > 0 and hi * hi > _FCUT * _FCUT * dd
         below = lo < 0 or lo * lo < _FCUT * _FCUT * dd
         dec_cut = above or below
     else:
         ok_cut = det >= _FCUT
-        dec_cut = _gt(det - _FCUT, tau * S_det)
+        dec_cut = _gt(det - _FCUT, b_det)
     if not ok_cut and dec_cut:
         return None
     if det <= 0:  # (the cut is undecided and the forms below mean nothing: any outcome)
         return Cand(-1, UND, False, None, math.inf, 1, [(math.nan, math.inf, 1)])
     t = td / det
     at = abs(float(t))
-    S_t = S_td + at * S_det
-    E = tau * S_t / float(det) + U * at
-    decs = [(ud >= 0, _gt(ud, tau * S_ud)), (vd >= 0, _gt(vd, tau * S_vd)),
-            (det - ud - vd >= 0, _gt(det - ud - vd, tau * (S_det + S_ud + S_vd))),
+    if pert is None:
+        S_t = S_td + at * S_det
+        E = tau * S_t / float(det) + u * at
+    else:
+        E = (b_td + at * b_det) / float(det) + u * at
+    decs = [(ud >= 0, _gt(ud, b_ud)), (vd >= 0, _gt(vd, b_vd)),
+            (det - ud - vd >= 0, _gt(det - ud - vd, b_sum)),
             (t >= _FTMIN, _gt(t - _FTMIN, E))]
     if math.isfinite(tmax):
         decs.append((t <= Fr(tmax), _gt(Fr(tmax) - t, E)))
@@ -202,8 +258,9 @@ def exact_triangle(o, d, tmax, A, B, C, tau, unit_cut=False):
     return Cand(-1, UND, hit, float(t) if hit else None, E, 1, [(float(t), E, 1)], tex=t)
 
 
-def exact_sphere(o, d, tmax, c, r, omag, tau):
-    """c: the exact centre (Fractions); omag[i]: the |o_i - c_i| (strict) or |o_i| + |c_i| (fast) of S, per axis."""
+def exact_sphere(o, d, tmax, c, r, omag, tau, u=U, dmag=None, pert=None):
+    """c: the exact centre (Fractions); omag[i]: the |o_i - c_i| (strict) or |o_i| + |c_i| (fast) of S, per axis; dmag:
+    the magnitudes that stand for |d_i| in S (default |d_i|)."""
     o, d = _f3(o), _f3(d)
     r = Fr(float(r))
     oc = [o[k] - c[k] for k in range(3)]
@@ -213,16 +270,42 @@ def exact_sphere(o, d, tmax, c, r, omag, tau):
     disc = h * h - a * cc
     Da = [abs(float(x)) for x in d]
     fa = float(a)
+    faS = fa
+    if dmag is not None:
+        Da = [float(x) for x in dmag]
+        faS = sum(x * x for x in Da)
     S_h = sum(m * x for m, x in zip(omag, Da))
     S_c = sum(m * m for m in omag) + float(r) ** 2
-    S_d = S_h * S_h + fa * S_c
-    dec_disc = _gt(disc, tau * S_d)
+    S_d = S_h * S_h + faS * S_c
+    if pert is None:
+        b_h, b_d = tau * S_h, tau * S_d
+    else:  # (eo, ed, plain omag, arithmetic band, large: tested in binary64) — see Reference
+        eo, ed, onat, taub, lg, comb = pert
+        Dn = [abs(float(x)) for x in d]
+        ocn = [abs(float(x)) for x in oc]
+        sm = lambda p, q: sum(x * y for x, y in zip(p, q))  # noqa: E731
+        n_h = sm(onat, Dn)
+        n_d = n_h * n_h + fa * (sm(onat, onat) + float(r) ** 2)
+        D_h = sm(eo, Dn) + sm(ocn, ed)
+        D_a = 2 * sm(Dn, ed)
+        # disc = a (r^2 - b^2), b the distance of the centre from the line: the line moves by |eo + |s| ed| at its
+        # closest point o + s d, s = -h / a (termwise bounds of h^2 and a c' would not see that the two cancel)
+        fs = abs(float(h)) / fa
+        fb = math.sqrt(max(float(_dot(oc, oc)) - float(h) ** 2 / fa, 0.0))
+        mv = math.sqrt(sum((eo[k] + fs * ed[k]) ** 2 for k in range(3)))
+        D_d = 2 * fa * max(abs(float(r)), fb) * mv + D_a * abs(float(disc)) / fa
+        a_h, a_d, a_a = taub * n_h + 2 * D_h, taub * n_d + 2 * D_d, taub * fa + 2 * D_a
+        b_h, b_d, b_a = (a_h, a_d, a_a) if lg else (comb(tau * S_h, a_h), comb(tau * S_d, a_d), comb(tau * faS, a_a))
+    dec_disc = _gt(disc, b_d)
     inward = r < 0
     if disc < 0:
         if dec_disc:
             return None
         t0 = float(-h / a)
-        E0 = (tau * S_h + math.sqrt(tau * S_d) + tau * abs(t0) * fa) / fa + U * abs(t0)
+        if pert is None:
+            E0 = (tau * S_h + math.sqrt(tau * S_d) + tau * abs(t0) * faS) / fa + u * abs(t0)
+        else:
+            E0 = (b_h + math.sqrt(b_d) + abs(t0) * b_a) / fa + u * abs(t0)
         return Cand(-1, UND, False, None, E0, int(inward), [(t0, E0, 0), (t0, E0, 1)])
     sq = _sqrt(disc)
     fsq = float(sq)
@@ -230,8 +313,20 @@ def exact_sphere(o, d, tmax, c, r, omag, tau):
 
     def E(t):
         at = abs(float(t))
+        if pert is not None:
+            # the arithmetic alone on the strict form, and the input errors through dt = -(p - c).(do + t dd) /
+            # ((p - c).d), (p - c).d = -+sqrt(disc): the termwise forms above do not see that h^2 and a c' cancel
+            an_d = taub * n_d
+            s = math.sqrt(an_d) if fsq == 0 else min(math.sqrt(an_d), an_d / fsq)
+            pc = [abs(float(oc[k] + t * d[k])) for k in range(3)]
+            ein = math.inf if fsq == 0 else 2 * sum(pc[k] * (eo[k] + at * ed[k]) for k in range(3)) / fsq
+            new = (taub * n_h + s + taub * fsq + taub * at * fa) / fa + ein + u * at
+            if lg:
+                return new
+            s = math.sqrt(tau * S_d) if fsq == 0 else min(math.sqrt(tau * S_d), tau * S_d / fsq)
+            return comb((tau * S_h + s + tau * fsq + tau * at * faS) / fa + u * at, new)
         s = math.sqrt(tau * S_d) if fsq == 0 else min(math.sqrt(tau * S_d), tau * S_d / fsq)
-        return (tau * S_h + s + tau * fsq + tau * at * fa) / fa + U * at
+        return (tau * S_h + s + tau * fsq + tau * at * faS) / fa + u * at
 
     E1, E2 = E(t1), E(t2)
     tmx = Fr(tmax) if math.isfinite(tmax) else None
@@ -258,7 +353,15 @@ def exact_sphere(o, d, tmax, c, r, omag, tau):
     else:
         hit, t, Et, front = n2 and x2, t2, E2, f_far
         dec = dn1 and dn2 and dx2
-    dec_front = fsq > fa * max(E1, E2) + tau * S_ff(t)  # (d.(p - c) = -+sqrt(disc) + a (t_computed - t))
+    if pert is None:
+        b_ff = tau * S_ff(t)
+    else:
+        aft = abs(float(t))
+        n_ff = sum(Dn[k] * (onat[k] + aft * Dn[k]) for k in range(3))
+        D_ff = sum(ed[k] * (ocn[k] + aft * Dn[k]) + Dn[k] * (eo[k] + aft * ed[k]) for k in range(3))
+        a_ff = taub * n_ff + 2 * D_ff
+        b_ff = a_ff if lg else comb(tau * S_ff(t), a_ff)
+    dec_front = fsq > fa * max(E1, E2) + b_ff  # (d.(p - c) = -+sqrt(disc) + a (t_computed - t))
     outs = []
     if (n1 or not dn1) and (x1 or not dx1):
         outs.append((float(t1), E1, f_near))
@@ -280,7 +383,12 @@ def exact_sphere(o, d, tmax, c, r, omag, tau):
 
 
 # ---- the binary64 filter over pairs ----------------------------------------------------------------------------------
-def _tri_filter(o, d, tmax, A, e1, e2, tau, unit_cut):
+def _cross_abs_v(x, y):
+    return np.stack([x[:, 1] * y[:, 2] + y[:, 1] * x[:, 2], x[:, 2] * y[:, 0] + y[:, 2] * x[:, 0],
+                     x[:, 0] * y[:, 1] + y[:, 0] * x[:, 1]], axis=1)
+
+
+def _tri_filter(o, d, tmax, A, e1, e2, tau, unit_cut, u=U, aomag=None, dmag=None, pert=None):
     """Pairs [m]: status (0 miss, 1 hit, 2 exact path), t, E."""
     n = np.stack([e1[:, 1] * e2[:, 2] - e2[:, 1] * e1[:, 2], e1[:, 2] * e2[:, 0] - e2[:, 2] * e1[:, 0],
                   e1[:, 0] * e2[:, 1] - e2[:, 0] * e1[:, 1]], axis=1)
@@ -291,7 +399,7 @@ def _tri_filter(o, d, tmax, A, e1, e2, tau, unit_cut):
     ao = o - A
     dao = np.stack([ao[:, 1] * d[:, 2] - d[:, 1] * ao[:, 2], ao[:, 2] * d[:, 0] - d[:, 2] * ao[:, 0],
                     ao[:, 0] * d[:, 1] - d[:, 0] * ao[:, 1]], axis=1)
-    AOa, Da = np.abs(ao), np.abs(d)
+    AOa, Da = np.abs(ao) if aomag is None else aomag, np.abs(d) if dmag is None else dmag
     DAOa = np.stack([AOa[:, 1] * Da[:, 2] + Da[:, 1] * AOa[:, 2], AOa[:, 2] * Da[:, 0] + Da[:, 2] * AOa[:, 0],
                      AOa[:, 0] * Da[:, 1] + Da[:, 0] * AOa[:, 1]], axis=1)
     ud = np.einsum("ij,ij->i", e2, dao)
@@ -305,12 +413,29 @@ def _tri_filter(o, d, tmax, A, e1, e2, tau, unit_cut):
     cut = CUT * np.sqrt(np.einsum("ij,ij->i", d, d)) if unit_cut else CUT
     S_cut = S_det + (CUT * np.sqrt(np.einsum("ij,ij->i", Da, Da)) * 4 * U if unit_cut else 0.0)
     q_cut = det - cut
+    if pert is not None:
+        eo, ed, aonat, taub, comb = pert
+        comb = np.minimum if comb is min else _second
+        kb = taub + GF
+        Dn, E1a, E2a = np.abs(d), np.abs(e1), np.abs(e2)
+        DAOn = _cross_abs_v(aonat, Dn)
+        DAOe = _cross_abs_v(eo, Dn) + _cross_abs_v(np.abs(ao), ed)
+        sm = lambda p, q: np.einsum("ij,ij->i", p, q)  # noqa: E731
+        b_det = comb(k * S_cut, kb * sm(Dn, Na) + 2 * sm(ed, Na))
+        b_ud = comb(k * S_ud, kb * sm(E2a, DAOn) + 2 * sm(E2a, DAOe))
+        b_vd = comb(k * S_vd, kb * sm(E1a, DAOn) + 2 * sm(E1a, DAOe))
+        b_td = comb(k * S_td, kb * sm(aonat, Na) + 2 * sm(eo, Na))
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         t = td / det
         at = np.abs(t)
-        E = k * (S_td + at * S_det) / det + 2 * U * at
-        decs = [(q_cut, k * S_cut), (ud, k * S_ud), (vd, k * S_vd), (det - ud - vd, k * (S_det + S_ud + S_vd)),
-                (t - TMIN, E), (tmax - t, np.where(np.isfinite(tmax), E, 0.0))]
+        if pert is None:
+            E = k * (S_td + at * S_det) / det + 2 * u * at
+            decs = [(q_cut, k * S_cut), (ud, k * S_ud), (vd, k * S_vd), (det - ud - vd, k * (S_det + S_ud + S_vd)),
+                    (t - TMIN, E), (tmax - t, np.where(np.isfinite(tmax), E, 0.0))]
+        else:
+            E = (b_td + at * b_det) / det + 2 * u * at
+            decs = [(q_cut, b_det), (ud, b_ud), (vd, b_vd), (det - ud - vd, b_det + b_ud + b_vd),
+                    (t - TMIN, E), (tmax - t, np.where(np.isfinite(tmax), E, 0.0))]
         fail = np.zeros(len(o), bool)
         sure = np.ones(len(o), bool)
         for q, b in decs:
@@ -320,19 +445,41 @@ def _tri_filter(o, d, tmax, A, e1, e2, tau, unit_cut):
     return st, t, E
 
 
-def _sph_filter(o, d, tmax, c, r, omag, tau):
+def _sph_filter(o, d, tmax, c, r, omag, tau, u=U, dmag=None, pert=None):
     oc = o - c
     a = np.einsum("ij,ij->i", d, d)
     h = np.einsum("ij,ij->i", oc, d)
     cc = np.einsum("ij,ij->i", oc, oc) - r * r
     disc = h * h - a * cc
-    Da = np.abs(d)
+    Da = np.abs(d) if dmag is None else dmag
+    aS = a if dmag is None else np.einsum("ij,ij->i", Da, Da)
     S_h = np.einsum("ij,ij->i", omag, Da)
-    S_d = S_h * S_h + a * (np.einsum("ij,ij->i", omag, omag) + r * r)
+    S_d = S_h * S_h + aS * (np.einsum("ij,ij->i", omag, omag) + r * r)
     k = tau + GF
     st = np.full(len(o), UND, np.int8)
-    st[disc < -k * S_d] = MISS
-    pos = disc > k * S_d
+    if pert is None:
+        b_d = k * S_d
+    else:
+        eo, ed, onat, taub, lg, comb = pert
+        comb = np.minimum if comb is min else _second
+        kb = taub + GF
+        Dn, ocn = np.abs(d), np.abs(oc)
+        sm = lambda p, q: np.einsum("ij,ij->i", p, q)  # noqa: E731
+        n_h = sm(onat, Dn)
+        n_d = n_h * n_h + a * (sm(onat, onat) + r * r)
+        D_h = sm(eo, Dn) + sm(ocn, ed)
+        D_a = 2 * sm(Dn, ed)
+        # disc = a (r^2 - b^2), b the distance of the centre from the line: the line moves by |eo + |s| ed| at its
+        # closest point o + s d, s = -h / a (termwise bounds of h^2 and a c' would not see that the two cancel)
+        bb = np.sqrt(np.maximum(sm(oc, oc) - h * h / a, 0.0))
+        mv = np.linalg.norm(eo + (np.abs(h) / a)[:, None] * ed, axis=1)
+        D_d = 2 * a * np.maximum(np.abs(r), bb) * mv + D_a * np.abs(disc) / a
+        a_h, a_d, a_a = kb * n_h + 2 * D_h, kb * n_d + 2 * D_d, kb * a + 2 * D_a
+        b_h = np.where(lg, a_h, comb(k * S_h, a_h))
+        b_d = np.where(lg, a_d, comb(k * S_d, a_d))
+        b_a = np.where(lg, a_a, comb(k * aS, a_a))
+    st[disc < -b_d] = MISS
+    pos = disc > b_d
     t = np.full(len(o), np.nan)
     E = np.full(len(o), np.inf)
     front = np.zeros(len(o), np.int32)
@@ -341,8 +488,17 @@ def _sph_filter(o, d, tmax, c, r, omag, tau):
         t1, t2 = (-h - sq) / a, (-h + sq) / a
 
         def Eof(tt):
+            if pert is not None:  # (see exact_sphere)
+                an_d = kb * n_d
+                s = np.minimum(np.sqrt(an_d), an_d / sq)
+                att = np.abs(tt)[:, None]
+                ein = 2 * sm(np.abs(oc + tt[:, None] * d), eo + att * ed) / sq
+                new = (kb * n_h + s + kb * sq + kb * np.abs(tt) * a) / a + ein + 2 * u * np.abs(tt)
+                s = np.minimum(np.sqrt(k * S_d), k * S_d / sq)
+                old = (k * S_h + s + k * sq + k * np.abs(tt) * aS) / a + 2 * u * np.abs(tt)
+                return np.where(lg, new, comb(old, new))
             s = np.minimum(np.sqrt(k * S_d), k * S_d / sq)
-            return (k * S_h + s + k * sq + k * np.abs(tt) * a) / a + 2 * U * np.abs(tt)
+            return (k * S_h + s + k * sq + k * np.abs(tt) * aS) / a + 2 * u * np.abs(tt)
 
         E1, E2 = Eof(t1), Eof(t2)
         fin = np.isfinite(tmax)
@@ -354,7 +510,13 @@ def _sph_filter(o, d, tmax, c, r, omag, tau):
         far_out = far & ((TMIN - t2 > E2) | (fin & (t2 - tmax > E2)))
         tt = np.where(near_in, t1, t2)
         S_ff = np.einsum("ij,ij->i", Da, omag + np.abs(tt)[:, None] * Da)
-        ff_ok = sq > k * S_ff + a * np.where(near_in, E1, E2)  # (d.(p - c) at the computed t)
+        if pert is None:
+            b_ff = k * S_ff
+        else:
+            att = np.abs(tt)[:, None]
+            a_ff = kb * sm(Dn, onat + att * Dn) + 2 * (sm(ed, ocn + att * Dn) + sm(Dn, eo + att * ed))
+            b_ff = np.where(lg, a_ff, comb(k * S_ff, a_ff))
+        ff_ok = sq > b_ff + a * np.where(near_in, E1, E2)  # (d.(p - c) at the computed t)
     inward = r < 0
     st[near_out | far_out] = MISS
     hit = (near_in | far_in) & ff_ok
@@ -367,12 +529,40 @@ def _sph_filter(o, d, tmax, c, r, omag, tau):
 
 # ---- the reference over a ray set -------------------------------------------------------------------------------------
 class Reference:
-    """Per ray of `rays` (RAY_DTYPE) against `scene` (Scene) under `build` (STRICT / FAST): the exact closest hit and
-    any-hit, decided or not, and the candidates (Cand) that explain an undecided ray's answers."""
+    """Per ray of `rays` (RAY_DTYPE) against `scene` (Scene) under `build` (STRICT / FAST / F32): the exact closest
+    hit and any-hit, decided or not, and the candidates (Cand) that explain an undecided ray's answers.
 
-    def __init__(self, scene, rays, build, unit_cut=False, chunk=1 << 20):
+    tau: the band, default TAU[build].  omag, dmag [n, 3]: the magnitudes that stand for |o_i| and |d_i| in every S_q
+    (the world-coordinate forms only: FAST and F32) — for a ray that the build computes itself, the sum of the
+    magnitudes of the terms of its expression.  exclude [n, 2]: per ray a (class, class index) that is no candidate
+    (the primitive a scattered ray leaves), class -1 for none.
+
+    operr, derr [n, 3] (F32 only): ABSOLUTE bounds on the error of the origin and direction the build traces against
+    the ray given.  Beside tau S_q every decision then has the first-order band TAU_ARITH S_q' + 2 D_q: S_q' on the
+    magnitudes of the strict form (|o_i - c_i|, |o_i - A_i|), D_q the effect of the input errors on q (|dq/do| (operr
+    + the record's rounding) + |dq/dd| derr, term by term; the header's factor 2).  Both are bounds where tau S_q
+    counts the same input errors (omag, dmag): the band is the smaller one; `first_order`: tau S_q does not cover
+    operr / derr (the scattered rays of f32_audit), the band is the first-order one.  large: the (class, class index) pairs of the spheres that the kernel tests in
+    binary64 on the widened ray — their band is the input error alone, TAU[FAST] S_q' + 2 D_q."""
+
+    def __init__(self, scene, rays, build, unit_cut=False, chunk=1 << 20, tau=None, omag=None, dmag=None,
+                 exclude=None, operr=None, derr=None, large=None, first_order=False):
         self.scene, self.rays, self.build, self.unit_cut = scene, rays, build, unit_cut
-        self.tau = TAU[build]
+        self.tau = TAU[build] if tau is None else tau
+        self.u = U32 if build == F32 else U
+        self._world = build in (FAST, F32)
+        assert (omag is None and dmag is None) or self._world
+        self._oa = None if omag is None else np.ascontiguousarray(omag, np.float64)
+        self._da = None if dmag is None else np.ascontiguousarray(dmag, np.float64)
+        self._ex = None if exclude is None else np.asarray(exclude, np.int64).reshape(-1, 2)
+        assert (operr is None) == (derr is None) and (operr is None or build == F32)
+        self._eo = None if operr is None else np.ascontiguousarray(operr, np.float64)
+        self._ed = None if derr is None else np.ascontiguousarray(derr, np.float64)
+        self._large = {SPHERE: np.zeros(len(scene.sph), bool), MOVING: np.zeros(len(scene.mov), bool)}
+        for cls, ci in (large or ()):
+            self._large[int(cls)][int(ci)] = True
+        assert not (large and operr is None)
+        self._comb = _second if first_order else min
         n = len(rays)
         self.cands = [[] for _ in range(n)]
         self._o = np.ascontiguousarray(rays["origin"], np.float64)
@@ -393,8 +583,17 @@ class Reference:
         dc = g[:, 3:6] - g[:, :3]
         return g[:, :3] + tm * dc, np.abs(g[:, :3]) + np.abs(tm * dc)
 
-    def _omag(self, o, c, extra):
-        return (np.abs(o) + np.abs(c) if self.build == FAST else np.abs(o - c)) + extra
+    def _omag(self, o, c, extra, oa=None):
+        return ((np.abs(o) if oa is None else oa) + np.abs(c) if self._world else np.abs(o - c)) + extra
+
+    def _mags(self, ri):
+        """(omag, dmag) of the rays ri: the caller's, or None."""
+        return (None if self._oa is None else self._oa[ri]), (None if self._da is None else self._da[ri])
+
+    def _excluded(self, ri, cls, ci):
+        if self._ex is None:
+            return np.zeros(len(ri), bool)
+        return (self._ex[ri, 0] == cls) & (self._ex[ri, 1] == ci)
 
     def _spheres(self, chunk):
         for cls, g in ((SPHERE, self.scene.sph), (MOVING, self.scene.mov)):
@@ -407,7 +606,16 @@ class Reference:
                 ci = np.tile(np.arange(len(g)), len(ri) // len(g))
                 c, extra = self._centres(ri, cls, ci)
                 o = self._o[ri]
-                st, t, E, fr = _sph_filter(o, self._d[ri], self._tmax[ri], c, r[ci], self._omag(o, c, extra), self.tau)
+                oa, da = self._mags(ri)
+                pert = None
+                if self._eo is not None:
+                    lg = self._large[cls][ci]
+                    ec = np.where(lg[:, None], 0.0, 3 * U32 * (np.abs(c) + extra))
+                    pert = (self._eo[ri] + ec, self._ed[ri], np.abs(o - c), np.where(lg, TAU[FAST], TAU_ARITH), lg,
+                            self._comb)
+                st, t, E, fr = _sph_filter(o, self._d[ri], self._tmax[ri], c, r[ci], self._omag(o, c, extra, oa),
+                                           self.tau, self.u, da, pert)
+                st[self._excluded(ri, cls, ci)] = MISS
                 for j in np.nonzero(st == HIT)[0]:
                     self._add(ri[j], cls, ci[j], Cand(-1, HIT, True, float(t[j]), float(E[j]), int(fr[j]),
                                                       [(float(t[j]), float(E[j]), int(fr[j]))]))
@@ -426,15 +634,29 @@ class Reference:
             c, r = [c0[k] + tm * (c1[k] - c0[k]) for k in range(3)], g[6]
             extra = np.abs(g[:3]) + np.abs(self._time[i] * (g[3:6] - g[:3]))
         cf = np.array([float(x) for x in c])
-        om = self._omag(o[None], cf[None], extra[None])[0]
-        return exact_sphere(o, d, float(self._tmax[i]), c, r, [float(x) for x in om], self.tau)
+        oa, da = self._mags(np.array([i]))
+        om = self._omag(o[None], cf[None], extra[None], oa)[0]
+        pert = None
+        if self._eo is not None:
+            lg = bool(self._large[cls][ci])
+            ec = np.zeros(3) if lg else 3 * U32 * (np.abs(cf) + extra)
+            pert = ([float(x) for x in self._eo[i] + ec], [float(x) for x in self._ed[i]],
+                    [float(x) for x in np.abs(o - cf)], TAU[FAST] if lg else TAU_ARITH, lg, self._comb)
+        return exact_sphere(o, d, float(self._tmax[i]), c, r, [float(x) for x in om], self.tau, self.u,
+                            None if da is None else da[0], pert)
 
     def _exact_pair(self, i, cls, ci):
         self.n_exact += 1
         if cls == TRIANGLE:
             g = self.scene.tri[ci]
+            am, da = self._tri_mags(np.array([i]), g[None, 0:3])
+            pert = None
+            if self._eo is not None:
+                pert = ([float(x) for x in self._eo[i] + U32 * np.abs(g[0:3])], [float(x) for x in self._ed[i]],
+                        [float(x) for x in np.abs(self._o[i] - g[0:3])], TAU_ARITH, self._comb)
             return exact_triangle(self._o[i], self._d[i], float(self._tmax[i]), g[0:3], g[3:6], g[6:9], self.tau,
-                                  self.unit_cut)
+                                  self.unit_cut, self.u, None if am is None else am[0], None if da is None else da[0],
+                                  pert)
         return self._exact_sphere_pair(i, cls, ci)
 
     def _exact(self, i, cls, ci):
@@ -473,6 +695,13 @@ class Reference:
             rr, cc = np.nonzero(~(tn > tf * (1 + 1e-9) + 1e-300))
             yield ids[rr], cc
 
+    def _tri_mags(self, ri, A):
+        """(|o - A| magnitudes, dmag) of the pairs: F32 tests ao = o - A on a rounded o and a rounded A."""
+        oa, da = self._mags(ri)
+        if self.build != F32:
+            return None, da
+        return (np.abs(self._o[ri]) if oa is None else oa) + np.abs(A), da
+
     def _triangles(self, chunk):
         if len(self.scene.tri) == 0:
             return
@@ -481,8 +710,13 @@ class Reference:
             if len(ri) == 0:
                 continue
             A = g[ci, 0:3]
+            am, da = self._tri_mags(ri, A)
+            pert = None
+            if self._eo is not None:
+                pert = (self._eo[ri] + U32 * np.abs(A), self._ed[ri], np.abs(self._o[ri] - A), TAU_ARITH, self._comb)
             st, t, E = _tri_filter(self._o[ri], self._d[ri], self._tmax[ri], A, g[ci, 3:6] - A, g[ci, 6:9] - A,
-                                   self.tau, self.unit_cut)
+                                   self.tau, self.unit_cut, self.u, am, da, pert)
+            st[self._excluded(ri, TRIANGLE, ci)] = MISS
             for j in np.nonzero(st == HIT)[0]:
                 self._add(ri[j], TRIANGLE, ci[j], Cand(-1, HIT, True, float(t[j]), float(E[j]), 1,
                                                        [(float(t[j]), float(E[j]), 1)]))

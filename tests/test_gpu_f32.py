@@ -16,6 +16,9 @@ far smaller, 3e-8 .. 6e-5, and the tests hold the build to a tenth of the survey
   T2c  no structured artefacts: 16x16-pixel block means differ by <= 2/255 everywhere
        (a flipped decision moves a dark pixel by up to sqrt(1/spp) = 0.09, a block by 3e-4;
        banding or acne on the ground would move whole blocks).
+
+These are statistics of whole frames at full depth.  The per-sample bar of this build is
+tests/test_gpu_f32_audit.py: every shallow sample against exact hits (tests/f32_audit.py).
 """
 import subprocess
 
