@@ -426,6 +426,7 @@ struct rtow_ctx {
   uint32_t gblob_bytes = 0;
   uint32_t grid_fat_stride = 0;  // bytes per fat cell-list entry of the resident grid image (0: plain id lists)
   int32_t grid_ny = 0;           // n[1] of the resident grid image's header (0: no grid); 1 selects the two-axis walk
+  GridWalkConsts grid_walk{};    // the walk's constants from that header (rtow_walk_consts.h): TraceParams::walk
   int64_t last_spec = -1;        // TraceParams::spec of the last trace launch (rtow_debug_last_spec; -1: none yet)
   bool have_grid = false;
   uint32_t blob_bytes = 0;
@@ -682,6 +683,7 @@ static int grid_device_build(rtow_ctx *c, const rtow_camera_t &cam, int ns, int 
       unsigned char header[64];
       const uint32_t off_large = (uint32_t)(gimg.off_ids + total_ids * 4);
       rtow::write_grid_header(header, hd, gimg.n_large, off_large, gimg.off_fat, gimg.fat_stride);
+      std::memcpy(gimg.header, header, 64);
       HIPCHK(hipMemsetAsync(gp, 0, gimg.total_bytes, nullptr));
       if ((rc = h2d_block(gp, header, 64))) return rc;  // (`header` is on the stack: never the source of an async copy)
       if (ns) HIPCHK(hipMemcpyAsync(gp + gimg.off_sph, c->sph.p, sph.size() * 8, hipMemcpyDeviceToDevice, nullptr));
@@ -697,6 +699,14 @@ static int grid_device_build(rtow_ctx *c, const rtow_camera_t &cam, int ns, int 
     }
   }
   return RTOW_OK;
+}
+
+// What the context remembers of the grid image that is resident NOW, taken from its 64-byte header: called wherever an
+// image becomes resident (every upload and refit, host- or device-built).  n[1] == 1 selects the two-axis walk; the
+// specialised trace kernels read the walk's constants from the block derived here instead of the header.
+static void grid_header_resident(rtow_ctx *c, const rtow::GridImage &gimg) {
+  c->grid_ny = gimg.ok ? gimg.n[1] : 0;
+  c->grid_walk = gimg.ok ? make_grid_walk_consts(gimg.header, gimg.off_ids, gimg.off_cells) : GridWalkConsts{};
 }
 
 static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need);
@@ -1018,7 +1028,7 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
   const double t_grid1 = now_ms();
   c->have_grid = gimg.ok;
   c->grid_fat_stride = (gimg.ok && gimg.off_fat) ? gimg.fat_stride : 0u;
-  c->grid_ny = gimg.ok ? gimg.n[1] : 0;
+  grid_header_resident(c, gimg);
   c->gblob_bytes = 0;
   if (gimg.ok) {
     if (!grid_on_device && (rc = upload(c->gblob, gimg.blob))) return rc;
@@ -1775,6 +1785,7 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
   P.seed_hi = (uint32_t)(cfg->seed >> 32);
   P.n_items = (uint32_t)n_items;
   P.n_lanes = (uint32_t)n_lanes;
+  P.npix_local = (uint32_t)npix;
   P.div_npix = make_fastdiv((uint32_t)npix);
   P.div_w = make_fastdiv((uint32_t)cfg->image_width);
   P.div_tile = make_fastdiv((uint32_t)cfg->tile_rows);
@@ -1823,6 +1834,7 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
     // the header of the image that is resident NOW (every upload and refit, host- or device-built, sets grid_ny)
     if (P.spec != rtow::kSpecGeneric && c->grid_ny == 1 && !c->knobs.no_flat) P.spec |= rtow::kSpecFlatY;
   }
+  P.walk = c->grid_walk;  // (read by the class kernels only; made with grid_ny, from the same header)
   P.b4_trips = c->knobs.bvh4_sm ? 0u : 1u;
   {
     const bool b4 = kernel == RTOW_KERNEL_BVH4;
@@ -2811,7 +2823,7 @@ static int impl_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
   if (c->built & kNeedGrid) {
     c->have_grid = gimg.ok;
     c->grid_fat_stride = (gimg.ok && gimg.off_fat) ? gimg.fat_stride : 0u;
-    c->grid_ny = gimg.ok ? gimg.n[1] : 0;
+    grid_header_resident(c, gimg);
     c->gblob_bytes = gimg.ok ? (uint32_t)gimg.total_bytes : 0u;
     ds.gblob = (const unsigned char *)c->gblob.p;
     ds.gblob_bytes = c->gblob_bytes;

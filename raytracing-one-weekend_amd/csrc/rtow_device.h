@@ -13,6 +13,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "rtow_walk_consts.h"
+
 namespace rtow {
 
 struct DevMaterial {       // 48 B
@@ -90,43 +92,58 @@ struct FastDiv {  // unsigned division by a per-launch constant (see fastdiv() i
   uint32_t magic, shift;
 };
 
-struct TraceParams {
+// The words of TraceParams that the trip kernels' fetch block reads (take_items, decode_item: rtow_trace_body.h), as two
+// aligned runs at the front of the kernel-argument segment.  The kernels keep none of them in SGPRs across a trip (they
+// ran out of SGPRs long ago): a fetch loads each run with wide scalar loads and waits once, where single words scattered
+// over TraceParams arrived one load and one wait at a time.  Base classes of TraceParams: the host fills the fields by
+// their names as before.
+struct alignas(64) FetchDecode {  // decode_item: queue position -> pixel and samples (19 words)
+  // pixel order inside this rank's rows: tiles of 2^tile_w_log2 x 2^tile_h_log2 = 64 pixels,
+  // tiles row-major (tile_h_log2 == 0 and tile_w_log2 == 0: plain row-major order)
+  uint32_t tile_w_log2, tile_h_log2;
+  // tiled order: queue position of a tile -> tile (row-major over this rank's tile rows), made by the host
+  // (rtow_capi.cpp, tile_queue_table): the tiles that see no primitive come last.  Read once per batch, with a scalar load.
+  const uint32_t *tile_table;
+  FastDiv div_ns;          // tiled order: (item / 64) -> (tile, stream)
+  FastDiv div_tpr;         // tiles per row = W >> tile_w_log2
+  uint32_t div_tpr_n;      // the divisor itself
+  // A LEVEL is a run of `spt` consecutive samples of every pixel, one work item per pixel.  Strict build: a level
+  // is one reference "thread" (stream): spt = spp / nstreams (src/render.cpp:151-166, 174).  Fast builds: the
+  // launch's sample range is cut into levels by the host (rtow_capi.cpp, level_plan) whatever nstreams is.
+  int32_t nstreams;        // levels traced by THIS launch
+  FastDiv div_tile;        // local row -> strip
+  int32_t rank, nranks, tile_rows;
+  uint32_t sample_base;    // sample index of the first sample of this launch's level 0 (level k starts at sample_base + k * spt)
+  int32_t spt;             // samples per level
+  int32_t spt_last;        // samples of the launch's LAST level (= spt unless the host's schedule ends on a longer one:
+                           // a sample count with no divisor near the aimed-at item length, rtow_capi.cpp level_plan)
+  uint32_t npix_local;     // local_rows * W: pixels of this rank (the stride of the partial-sum slots' levels)
+};
+struct alignas(32) FetchHead {  // take_items and the partial-sum store (8 words)
+  uint32_t n_items;        // local_rows * W * nstreams
+  uint32_t n_items_first;  // queue positions below this one belong to tiles that see something; the rest to empty tiles,
+  uint32_t empty_batch;    // ... whose items (one segment per sample) are bought this many at a time instead of 64
+  int32_t W;               // full image width
+  double *partials;        // [nstreams][local_rows*W][3]
+  unsigned long long *counters; // [0] next item, [1] segments, [2] prim tests, [3] node tests
+};
+static_assert(sizeof(FetchDecode) == 128 && sizeof(FetchHead) == 32, "aligned runs: one or two wide scalar loads each");
+
+struct TraceParams : FetchDecode, FetchHead {
   DevScene sc;
   const DevCamera *cam;    // in device memory: read with scalar loads where rays are generated
   const float *cam32;      // the same 21 values as binary32 (f32 build)
                            // (by value it pinned 42 SGPRs across the whole kernel)
-  int32_t W, H;            // full image
-  // A LEVEL is a run of `spt` consecutive samples of every pixel, one work item per pixel.  Strict build: a level
-  // is one reference "thread" (stream): spt = spp / nstreams (src/render.cpp:151-166, 174).  Fast builds: the
-  // launch's sample range is cut into levels by the host (rtow_capi.cpp, level_plan) whatever nstreams is.
-  int32_t spt;             // samples per level
-  int32_t nstreams;        // levels traced by THIS launch
-  int32_t stream_first;    // index of its first level (strict build: sample_base = stream_first * spt)
-  uint32_t sample_base;    // sample index of the first sample of this launch's level 0 (level k starts at sample_base + k * spt)
-  int32_t spt_last;        // samples of the launch's LAST level (= spt unless the host's schedule ends on a longer one:
-                           // a sample count with no divisor near the aimed-at item length, rtow_capi.cpp level_plan)
+  int32_t H;               // full image height
+  int32_t stream_first;    // index of the launch's first level (strict build: sample_base = stream_first * spt)
   uint32_t tail_bound;     // trips a wave may spend in the end-of-launch protocol before it gives up (structural bound)
   double inv_wm1, inv_hm1; // 1 / (W - 1), 1 / (H - 1): the fast builds multiply where the reference divides (src/render.cpp:158-159)
   int32_t max_child_rays;
-  int32_t rank, nranks, tile_rows;
   int32_t local_rows;
   uint32_t seed_lo, seed_hi;
-  uint32_t n_items;        // local_rows * W * nstreams
   uint32_t n_lanes;        // grid * block (stride of the path stack)
-  FastDiv div_npix, div_w, div_tile;  // item -> (stream, row, column, strip)
-  FastDiv div_ns;                     // tiled order: (item / 64) -> (tile, stream)
-  // pixel order inside this rank's rows: tiles of 2^tile_w_log2 x 2^tile_h_log2 = 64 pixels,
-  // tiles row-major (tile_h_log2 == 0 and tile_w_log2 == 0: plain row-major order)
-  uint32_t tile_w_log2, tile_h_log2;
-  FastDiv div_tpr;         // tiles per row = W >> tile_w_log2
-  uint32_t div_tpr_n;      // the divisor itself
+  FastDiv div_npix, div_w; // row-major order: item -> (stream, row, column)
   uint32_t n_tile_rows;    // tile rows of this rank
-  // tiled order: queue position of a tile -> tile (row-major over this rank's tile rows), made by the host
-  // (rtow_capi.cpp, tile_queue_table): the tiles that see no primitive come last.  Read once per batch, with a scalar load.
-  const uint32_t *tile_table;
-  uint32_t n_items_first;  // queue positions below this one belong to tiles that see something; the rest to empty tiles,
-  uint32_t empty_batch;    // ... whose items (one segment per sample) are bought this many at a time instead of 64
-  double *partials;        // [nstreams][local_rows*W][3]
   uint32_t *stack;         // [max_child_rays][n_lanes] material index per bounce
   uint32_t *spill;         // BVH4 kernel: traversal stack entries beyond the LDS part, [entry][n_lanes]
   uint32_t spec;           // GRID kernel: scene-class specialisation of the code (0 generic; 1 static spheres only with
@@ -137,10 +154,13 @@ struct TraceParams {
   uint32_t leaf_votes;               // GRID / BVH4 walks: lanes that must hold a queued cell / leaf before a leaf phase runs
   uint32_t walk_cap, walk_max_open;  // GRID / BVH4 walks: resumable walk (rtow_trace_grid.h); cap 0xffffffff = never stop
   uint32_t sm4_restart, sm4_scatter, sm4_leaf;  // state machine: lanes that must wait for a block before it runs
-  unsigned long long *counters; // [0] next item, [1] segments, [2] prim tests, [3] node tests
   unsigned long long *dropped;  // sticky (never reset by a launch): lanes that gave up samples at the tail bound; the
                                 // host turns a non-zero word into RTOW_EHIP at its next synchronising entry point
   unsigned long long *t_origin; // diagnostic build: earliest wave start (100 MHz clock)
+  // GRID kernel, specialised instantiations: the walk's per-scene constants (rtow_walk_consts.h), made by the host from
+  // the header of the resident grid image at every upload and refit; the generic instantiation and every other kernel
+  // read the header itself
+  GridWalkConsts walk;
 };
 
 // Scene-class specialisations of the GRID trace kernel (round 4).  The generic kernel carries the code of every

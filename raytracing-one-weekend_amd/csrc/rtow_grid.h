@@ -34,6 +34,7 @@ struct GridImage {
   size_t total_bytes = 0;
   uint32_t off_fat = 0;
   uint32_t fat_stride = 0;  // bytes per fat list entry: 48 (static spheres) or 80 (scenes with moving spheres)
+  unsigned char header[64] = {};  // the image's first 64 bytes as written (the device builder keeps no host copy of the rest)
   bool ok = false;  // false: scene not suited (e.g. lists too long) — use the BVH
 };
 
@@ -323,6 +324,7 @@ inline void build_grid_image(const std::vector<double> &sph, const std::vector<d
 
   unsigned char *h = img.blob.data();
   write_grid_header(h, hd, img.n_large, off_large, img.off_fat, img.fat_stride);
+  std::memcpy(img.header, h, 64);
   if (img.off_fat)
     for (size_t e = 0; e < n_cell_ids; ++e)
       write_fat_entry(h + img.off_fat + e * img.fat_stride, img.fat_stride, ids[e], sph, mov);

@@ -109,11 +109,28 @@ struct ItemPool {
   unsigned long long seen = 0ull;  // queue head as of this wave's last fetch
 };
 
+// The fetch block's launch parameters: the two aligned runs at the front of the kernel-argument segment (rtow_device.h),
+// each read where it is needed with adjacent scalar loads — the compiler merges them into wide ones — and waited for once.
+__device__ __forceinline__ FetchHead load_fetch_head(const RTOW_CONST FetchHead *p) {
+  FetchHead h;
+  h.n_items = p->n_items, h.n_items_first = p->n_items_first, h.empty_batch = p->empty_batch, h.W = p->W;
+  h.partials = p->partials, h.counters = p->counters;
+  return h;
+}
+__device__ __forceinline__ FetchDecode load_fetch_decode(const RTOW_CONST FetchDecode *p) {
+  FetchDecode d;
+  d.tile_w_log2 = p->tile_w_log2, d.tile_h_log2 = p->tile_h_log2, d.tile_table = p->tile_table;
+  d.div_ns = FastDiv{p->div_ns.magic, p->div_ns.shift}, d.div_tpr = FastDiv{p->div_tpr.magic, p->div_tpr.shift};
+  d.div_tpr_n = p->div_tpr_n, d.nstreams = p->nstreams, d.div_tile = FastDiv{p->div_tile.magic, p->div_tile.shift};
+  d.rank = p->rank, d.nranks = p->nranks, d.tile_rows = p->tile_rows;
+  d.sample_base = p->sample_base, d.spt = p->spt, d.spt_last = p->spt_last, d.npix_local = p->npix_local;
+  return d;
+}
+
 // Hands one queue position to every lane of `need_mask` (all lanes of the wave call this together).
-// Returns the lane's position, >= kp->n_items when the queue is exhausted.
+// Returns the lane's position, >= kp.n_items when the queue is exhausted.
 __device__ __forceinline__ unsigned long long take_items(ItemPool &pool, unsigned long long need_mask, unsigned lane,
-                                                         uint32_t n_waves, const RTOW_CONST TraceParams *kp,
-                                                         unsigned long long *counters) {
+                                                         uint32_t n_waves, const FetchHead &kp) {
   // Wave-local pool [next, end): one global atomic buys kItemBatch items, which the lanes then take by
   // ballot rank with no further traffic (a single hot counter word saturates near 90 dequeues/us on this
   // chip — one atomic per wave trip was the bottleneck).  All of this is wave-uniform except `mine`.
@@ -126,7 +143,7 @@ __device__ __forceinline__ unsigned long long take_items(ItemPool &pool, unsigne
     // exactly what this wave needs now as it drains (a wave that hoards items at the end
     // of the queue keeps the whole launch waiting: measured ~4 item durations per launch)
     const unsigned long long left =
-        (unsigned long long)kp->n_items > pool.seen ? (unsigned long long)kp->n_items - pool.seen : 0ull;
+        (unsigned long long)kp.n_items > pool.seen ? (unsigned long long)kp.n_items - pool.seen : 0ull;
 #ifdef RTOW_NO_SHRINK  // (experiment: a batch is always one tile)
     uint32_t batch = kItemBatch;
     (void)left;
@@ -134,8 +151,8 @@ __device__ __forceinline__ unsigned long long take_items(ItemPool &pool, unsigne
     // (the tail of the queue holds the tiles that see nothing, decode_item: an item there is one segment per sample
     // against the launch's average of several, so a wave buys several levels of a tile at once — a batch that lasts
     // about as long as one of the first segment, and the one counter word sees no more requests than before)
-    const bool sky = pool.seen >= (unsigned long long)kp->n_items_first;
-    const uint32_t batch_max = sky ? kp->empty_batch : kItemBatch;
+    const bool sky = pool.seen >= (unsigned long long)kp.n_items_first;
+    const uint32_t batch_max = sky ? kp.empty_batch : kItemBatch;
     uint32_t batch = (uint32_t)((sky ? left * (unsigned long long)(batch_max >> 6) : left) / ((unsigned long long)n_waves * 4ull));
     batch = batch > batch_max ? batch_max : batch;
     batch = batch < want - avail ? want - avail : batch;
@@ -145,14 +162,14 @@ __device__ __forceinline__ unsigned long long take_items(ItemPool &pool, unsigne
     // a wave that has seen the end of the queue stops polling it: at the end of a launch every
     // wave asks every trip, and the one counter word serves ~100 requests/us (measured: the
     // last trips of a launch took 34 us instead of 13)
-    if (pool.seen < (unsigned long long)kp->n_items) {
-      if ((int)lane == leader) base = atomicAdd(&counters[0], (unsigned long long)batch);
+    if (pool.seen < (unsigned long long)kp.n_items) {
+      if ((int)lane == leader) base = atomicAdd(&kp.counters[0], (unsigned long long)batch);
       base = __shfl(base, leader);
     }
     pool.seen = base + batch;  // how far the queue had advanced when this wave last looked
     if (rank >= avail) mine = base + (rank - avail);
     const unsigned long long nn = base + (want - avail), ne = base + batch;
-    const unsigned long long cap = (unsigned long long)kp->n_items;
+    const unsigned long long cap = (unsigned long long)kp.n_items;
     pool.next = (uint32_t)(nn < cap ? nn : cap);
     pool.end = (uint32_t)(ne < cap ? ne : cap);
   } else {
@@ -175,47 +192,49 @@ struct ItemPos {
   uint32_t item, j, gi, sample0;
   int32_t count;  // samples of the item (the launch's last level may be longer than the others)
 };
-__device__ __forceinline__ ItemPos decode_item(const RTOW_CONST TraceParams *kp, uint32_t mine, uint32_t npix_local) {
+__device__ __forceinline__ ItemPos decode_item(const RTOW_CONST TraceParams *kp, const FetchHead &fh, uint32_t mine) {
   ItemPos ip;
-  const uint32_t qi = kp->n_items - 1u - mine;
-  if (kp->tile_h_log2 == 0u) {  // row-major, stream-major
+  const FetchDecode kd = load_fetch_decode(kp);  // (one wait for the whole run: nothing below loads a launch parameter)
+  const uint32_t npix_local = kd.npix_local;
+  const uint32_t qi = fh.n_items - 1u - mine;
+  if (kd.tile_h_log2 == 0u) {  // row-major, stream-major
     const uint32_t k = fastdiv(qi, FastDiv{kp->div_npix.magic, kp->div_npix.shift});
     const uint32_t lp = qi - k * npix_local;
     const uint32_t lr = fastdiv(lp, FastDiv{kp->div_w.magic, kp->div_w.shift});
-    ip.j = lp - lr * (uint32_t)kp->W;
+    ip.j = lp - lr * (uint32_t)fh.W;
     ip.item = k * npix_local + lp;  // partial-sum slot
     // local row -> global row: this rank's q-th strip is global strip q*nranks+rank
-    const uint32_t q = fastdiv(lr, FastDiv{kp->div_tile.magic, kp->div_tile.shift});
-    const uint32_t rr = lr - q * (uint32_t)kp->tile_rows;
-    ip.gi = (q * (uint32_t)kp->nranks + (uint32_t)kp->rank) * (uint32_t)kp->tile_rows + rr;
-    ip.sample0 = kp->sample_base + k * (uint32_t)kp->spt;  // first sample index of this level
-    ip.count = k + 1u == (uint32_t)kp->nstreams ? kp->spt_last : kp->spt;
+    const uint32_t q = fastdiv(lr, FastDiv{kd.div_tile.magic, kd.div_tile.shift});
+    const uint32_t rr = lr - q * (uint32_t)kd.tile_rows;
+    ip.gi = (q * (uint32_t)kd.nranks + (uint32_t)kd.rank) * (uint32_t)kd.tile_rows + rr;
+    ip.sample0 = kd.sample_base + k * (uint32_t)kd.spt;  // first sample index of this level
+    ip.count = k + 1u == (uint32_t)kd.nstreams ? kd.spt_last : kd.spt;
     return ip;
   }
   // 64-pixel tiles: the lanes of one (tile, level) group at a time, the group of the first lane still waiting
   const uint32_t g64 = qi >> 6, w = qi & 63u;
-  const RTOW_CONST uint32_t *table = (const RTOW_CONST uint32_t *)kp->tile_table;
+  const RTOW_CONST uint32_t *table = (const RTOW_CONST uint32_t *)kd.tile_table;
   ip.item = ip.j = ip.gi = ip.sample0 = 0u;
   ip.count = 0;
   for (;;) {
     const uint32_t ug = (uint32_t)__builtin_amdgcn_readfirstlane((int)g64);  // wave-uniform from here to the select
-    const uint32_t t = fastdiv(ug, FastDiv{kp->div_ns.magic, kp->div_ns.shift});
-    const uint32_t k = ug - t * (uint32_t)kp->nstreams;
+    const uint32_t t = fastdiv(ug, FastDiv{kd.div_ns.magic, kd.div_ns.shift});
+    const uint32_t k = ug - t * (uint32_t)kd.nstreams;
     const uint32_t tile = table[t];
-    const uint32_t tr = fastdiv(tile, FastDiv{kp->div_tpr.magic, kp->div_tpr.shift});
-    const uint32_t tc = tile - tr * kp->div_tpr_n;
+    const uint32_t tr = fastdiv(tile, FastDiv{kd.div_tpr.magic, kd.div_tpr.shift});
+    const uint32_t tc = tile - tr * kd.div_tpr_n;
     // first local row of the tile -> global row (a tile never straddles two strips: its rows are consecutive)
-    const uint32_t lr0 = tr << kp->tile_h_log2;
-    const uint32_t q = fastdiv(lr0, FastDiv{kp->div_tile.magic, kp->div_tile.shift});
-    const uint32_t gi0 = (q * (uint32_t)kp->nranks + (uint32_t)kp->rank) * (uint32_t)kp->tile_rows + (lr0 - q * (uint32_t)kp->tile_rows);
+    const uint32_t lr0 = tr << kd.tile_h_log2;
+    const uint32_t q = fastdiv(lr0, FastDiv{kd.div_tile.magic, kd.div_tile.shift});
+    const uint32_t gi0 = (q * (uint32_t)kd.nranks + (uint32_t)kd.rank) * (uint32_t)kd.tile_rows + (lr0 - q * (uint32_t)kd.tile_rows);
     const uint32_t item0 = k * npix_local + (tile << 6);
-    const uint32_t j0 = tc << kp->tile_w_log2;
-    const uint32_t s0 = kp->sample_base + k * (uint32_t)kp->spt;
-    const int32_t cnt = k + 1u == (uint32_t)kp->nstreams ? kp->spt_last : kp->spt;
+    const uint32_t j0 = tc << kd.tile_w_log2;
+    const uint32_t s0 = kd.sample_base + k * (uint32_t)kd.spt;
+    const int32_t cnt = k + 1u == (uint32_t)kd.nstreams ? kd.spt_last : kd.spt;
     if (g64 == ug) {
       ip.item = item0 + w;  // partial-sum slot
-      ip.j = j0 + (w & ((1u << kp->tile_w_log2) - 1u));
-      ip.gi = gi0 + (w >> kp->tile_w_log2);
+      ip.j = j0 + (w & ((1u << kd.tile_w_log2) - 1u));
+      ip.gi = gi0 + (w >> kd.tile_w_log2);
       ip.sample0 = s0;
       ip.count = cnt;
       break;
@@ -306,7 +325,6 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
   const uint32_t k0 = P.seed_lo, k1 = P.seed_hi;
   const unsigned lane = lane_id();
   [[maybe_unused]] const uint32_t lane_g = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t npix_local = (uint32_t)P.local_rows * (uint32_t)P.W;
 
   Image<LDS> im;
   [[maybe_unused]] Bvh4Reader<LDS> im4;  // LDS: the whole image is staged; otherwise the top of the tree
@@ -390,16 +408,17 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       // of SGPRs, so every one of them cost a v_readlane (VALU) per use.
       const RTOW_CONST TraceParams *kp = (const RTOW_CONST TraceParams *)__builtin_amdgcn_kernarg_segment_ptr();
       asm volatile("" : "+s"(kp));  // opaque per trip: keeps the loads from being hoisted out of the loop
+      const FetchHead fh = load_fetch_head(kp);
       if (need_item && item != 0xffffffffu) {  // the finished item goes to its partial-sum slot
-        double *dst = P.partials + (size_t)item * 3;
+        double *dst = fh.partials + (size_t)item * 3;
         dst[0] = acc.x;
         dst[1] = acc.y;
         dst[2] = acc.z;
         item = 0xffffffffu;
       }
-      const unsigned long long mine = take_items(pool, need_mask, lane, n_waves, kp, P.counters);
+      const unsigned long long mine = take_items(pool, need_mask, lane, n_waves, fh);
       if (need_item) {
-        if (mine >= (unsigned long long)kp->n_items) {
+        if (mine >= (unsigned long long)fh.n_items) {
           done = true;
 #ifdef RTOW_TAILSTAT
           if (ts_empty == 0ull) ts_empty = 1ull;  // marked; the wave-level snapshot is taken below
@@ -408,11 +427,11 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
             if (t_empty == 0ull) t_empty = __builtin_amdgcn_s_memrealtime();
           }
         } else {
-          const ItemPos ip = decode_item(kp, (uint32_t)mine, npix_local);
+          const ItemPos ip = decode_item(kp, fh, (uint32_t)mine);
           item = ip.item;
           j = ip.j;
           gi = ip.gi;
-          g.pixel = gi * (uint32_t)kp->W + j;
+          g.pixel = gi * (uint32_t)fh.W + j;
           g.sample = ip.sample0;
           s_left = ip.count;
           acc = {0.0, 0.0, 0.0};
@@ -613,7 +632,10 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
         const uint32_t o_mats = KERNEL == 3 ? sc.g_off_mats : sc.off_mats;
         if constexpr ((SPEC & 3) == 1) __builtin_assume(pid < sc.n_sph);
         if constexpr ((SPEC & 3) == 2) __builtin_assume(pid < sc.n_sph + sc.n_mov);
-        if (pid < sc.n_sph + sc.n_mov) {
+        // (the class kernels run on scenes without triangles: their triangle branch is not compiled at all — the
+        // assumptions above do not remove it for class 1, where n_mov >= 0 is not known to the compiler, and the
+        // section offset it reads cost a spilled SGPR)
+        if ((SPEC & 3) != 0 || pid < sc.n_sph + sc.n_mov) {
           V3 center;
           bool inward;  // negative radius: only the sign of the signed r*r is used here
           if (pid < sc.n_sph) {
@@ -846,8 +868,13 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
                                            P.walk_cap, P.walk_max_open);
     } else if constexpr (KERNEL == 3) {
       if constexpr (STAMPS) stamps.primary = __ballot(tracing && depth == P.max_child_rays);
+      // (the specialised walks read their per-scene constants from TraceParams::walk, at the walk's entry: the pointer is
+      // opaque per trip, so the block is neither held in SGPRs across the new-ray stage nor loaded word by word)
+      const RTOW_CONST TraceParams *kw = (const RTOW_CONST TraceParams *)__builtin_amdgcn_kernarg_segment_ptr();
+      if constexpr ((SPEC & 3) != 0) asm volatile("" : "+s"(kw));
       best = closest_hit_grid<LDS, STAMPS, (SPEC & 3), (SPEC & (int)kSpecFlatY) != 0>(
-          im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps, best, t_resume, P.walk_cap, P.walk_max_open, P.leaf_votes);
+          im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps, best, t_resume, P.walk_cap, P.walk_max_open, P.leaf_votes,
+          &kw->walk);
     } else if constexpr (KERNEL == 2) {
       // the walk uses wave votes, so every lane of the wave enters it
       best = closest_hit_bvh<LDS, STAMPS>(im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps);

@@ -23,12 +23,19 @@
 //
 // FLAT (kSpecFlatY, rtow_device.h): the resident grid has ONE layer of cells in y.  The set-up and the step are the
 // two-axis forms of rtow_dda_step.h: same cells in the same order, same t_entry; everything else is untouched.
+//
+// Per-scene constants.  The generic instantiation (SPEC == 0: the query, occlusion, radiance and guide kernels, and the
+// trace kernels under RTOW_NO_SPEC) reads the 64-byte header of the image and derives the far planes, the clamps and the
+// strides from it.  The specialised instantiations take all of that ready-made from `wk`, the block the host derived
+// from the same header (rtow_walk_consts.h, TraceParams::walk): adjacent words of the kernel-argument segment in the
+// order the walk consumes them, read with wide scalar loads at the walk's entry and waited for once.  Same values bit for
+// bit, so same cells, same counters, same image; the arithmetic behind the constants is the same code for both.
 template <bool LDS, bool ST, int SPEC = 0, bool FLAT = false>
 __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const DevScene &sc, V3 o,
                                                     V3 d, real time, bool active, uint32_t &nnode,
                                                     uint32_t &nprim, Stamps<ST> &stamps, Closest best,
                                                     float &t_resume, uint32_t cap, uint32_t max_open,
-                                                    uint32_t leaf_votes) {
+                                                    uint32_t leaf_votes, const RTOW_CONST GridWalkConsts *wk = nullptr) {
   const bool resumed = t_resume > 0.0f;
   const float t_in = t_resume;
   if (!resumed) {
@@ -52,22 +59,41 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
 #endif
   ImgOffsets off = {sc.g_off_ids, sc.g_off_sph, sc.g_off_mov, sc.g_off_tri, 0u, 0u, sc.g_off_sph32, sc.g_off_mov32};
   int last_id = -1;
-  // header: wave-uniform scalar loads from the global copy of the image
-  const RTOW_CONST float *hf = (const RTOW_CONST float *)sc.gblob;
-  const RTOW_CONST int32_t *hi = (const RTOW_CONST int32_t *)sc.gblob;
-  const float gx = hf[0], gy = hf[1], gz = hf[2];
-  const float cx = hf[3], cy = hf[4], cz = hf[5];
-  const float icx = hf[6], icy = hf[7], icz = hf[8];
-  const int nx = hi[9], ny = hi[10], nz = hi[11];
-  const uint32_t n_large = (uint32_t)hi[12], off_large = (uint32_t)hi[13];
-  off.fat = (uint32_t)hi[14];
-  off.fat_stride = (uint32_t)hi[15];
+  float gx, gy, gz, hx, hy, hz, cx, cy, cz, icx, icy, icz;
+  int nx, ny, nxm1, nym1, nzm1, neg_nx, nxny, neg_nxny;
+  [[maybe_unused]] int nz = 0;  // (the generic walk derives the far planes below, where it always did)
+  uint32_t n_large, lf, cells;
+  if constexpr (SPEC != 0) {
+    // the host's block: wave-uniform scalar loads from the kernel-argument segment (the 3D walk's five words — cy, icy,
+    // ny - 1 and the z strides — are dead in the two-axis walk and not loaded there)
+    gx = wk->gx, gy = wk->gy, gz = wk->gz, hx = wk->hx, hy = wk->hy, hz = wk->hz;
+    cx = wk->cx, cy = wk->cy, cz = wk->cz, icx = wk->icx, icy = wk->icy, icz = wk->icz;
+    nx = wk->nx, ny = wk->ny, nxm1 = wk->nxm1, nym1 = wk->nym1, nzm1 = wk->nzm1;
+    neg_nx = wk->neg_nx, nxny = wk->nxny, neg_nxny = wk->neg_nxny;
+    n_large = wk->n_large, lf = wk->large_first, cells = wk->cells;
+    off.fat = wk->fat;
+    off.fat_stride = wk->fat_stride;
+  } else {
+    // header: wave-uniform scalar loads from the global copy of the image
+    const RTOW_CONST float *hf = (const RTOW_CONST float *)sc.gblob;
+    const RTOW_CONST int32_t *hi = (const RTOW_CONST int32_t *)sc.gblob;
+    gx = hf[0], gy = hf[1], gz = hf[2];
+    cx = hf[3], cy = hf[4], cz = hf[5];
+    icx = hf[6], icy = hf[7], icz = hf[8];
+    nx = hi[9], ny = hi[10], nz = hi[11];
+    nxm1 = nx - 1, nym1 = ny - 1, nzm1 = nz - 1;
+    neg_nx = -nx, nxny = nx * ny, neg_nxny = -(nx * ny);
+    n_large = (uint32_t)hi[12];
+    lf = ((uint32_t)hi[13] - off.ids) >> 2;  // (off_large: the list's byte offset in the image)
+    cells = sc.g_off_cells;
+    off.fat = (uint32_t)hi[14];
+    off.fat_stride = (uint32_t)hi[15];
+  }
 
   // the large primitives, for every ray.  Static spheres are taken four (then two) at a time:
   // all records are loaded and all discriminants computed before any hit branch, so LDS
   // latency and the f64 dependency chains of one test overlap the others.
   if (active && !resumed && n_large != 0u) {
-    const uint32_t lf = (off_large - off.ids) >> 2;
     uint32_t k = 0;
     for (; k + 3 < n_large; k += 4) {
       int id[4];
@@ -118,7 +144,7 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
   const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
   const float ix = safe_inv(dx), iy = safe_inv(dy), iz = safe_inv(dz);
   const float oix = ox * ix, oiy = oy * iy, oiz = oz * iz;
-  const float hx = fmaf((float)nx, cx, gx), hy = fmaf((float)ny, cy, gy), hz = fmaf((float)nz, cz, gz);
+  if constexpr (SPEC == 0) hx = fmaf((float)nx, cx, gx), hy = fmaf((float)ny, cy, gy), hz = fmaf((float)nz, cz, gz);
   const float ax = fmaf(gx, ix, -oix), bx = fmaf(hx, ix, -oix);
   const float ay = fmaf(gy, iy, -oiy), by = fmaf(hy, iy, -oiy);
   const float az = fmaf(gz, iz, -oiz), bz = fmaf(hz, iz, -oiz);
@@ -131,28 +157,28 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
   const float tdx = fabsf(cx * ix), tdz = fabsf(cz * iz);
   const float px = fmaf(t0, dx, ox), pz = fmaf(t0, dz, oz);
   int c0 = (int)floorf((px - gx) * icx), c2 = (int)floorf((pz - gz) * icz);
-  c0 = min(max(c0, 0), nx - 1);
-  c2 = min(max(c2, 0), nz - 1);
+  c0 = min(max(c0, 0), nxm1);
+  c2 = min(max(c2, 0), nzm1);
   typename DdaWalkOf<FLAT>::type w;
   w.tmx = fmaf(fmaf((float)(c0 + (fx ? 1 : 0)), cx, gx), ix, -oix);
   w.tmz = fmaf(fmaf((float)(c2 + (fz ? 1 : 0)), cz, gz), iz, -oiz);
   w.tdx = tdx, w.tdz = tdz;
-  w.remx = fx ? nx - 1 - c0 : c0, w.remz = fz ? nz - 1 - c2 : c2;
+  w.remx = fx ? nxm1 - c0 : c0, w.remz = fz ? nzm1 - c2 : c2;
   w.incx = fx ? 1 : -1;
   if constexpr (FLAT) {
     // one layer in y (the host checked the header: ny == 1): the y cell is 0, its far wall is the slab's exit plane —
     // the generic tmy, fmaf(fmaf((float)(fy ? 1 : 0), cy, gy), iy, -oiy), is `by` or `ay` of the clip above
     w.ty_exit = fy ? by : ay;
-    w.incz = fz ? nx : -nx;
+    w.incz = fz ? nx : neg_nx;
     w.idx = c2 * nx + c0;
   } else {
     const float py = fmaf(t0, dy, oy);
     int c1 = (int)floorf((py - gy) * icy);
-    c1 = min(max(c1, 0), ny - 1);
+    c1 = min(max(c1, 0), nym1);
     w.tmy = fmaf(fmaf((float)(c1 + (fy ? 1 : 0)), cy, gy), iy, -oiy);
     w.tdy = fabsf(cy * iy);
-    w.remy = fy ? ny - 1 - c1 : c1;
-    w.incy = fy ? nx : -nx, w.incz = fz ? nx * ny : -(nx * ny);
+    w.remy = fy ? nym1 - c1 : c1;
+    w.incy = fy ? nx : neg_nx, w.incz = fz ? nxny : neg_nxny;
     w.idx = (c2 * ny + c1) * nx + c0;
   }
 
@@ -168,7 +194,7 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
       if (m_step != 0ull && (m_step & ~stamps.primary) == 0ull) stamps.iters_cam += 1;
     }
     if (walking && q1 == 0u) {  // (a lane with two cells queued waits for the next leaf phase)
-      const uint32_t cw = im.u32(sc.g_off_cells + 4u * (uint32_t)w.idx);
+      const uint32_t cw = im.u32(cells + 4u * (uint32_t)w.idx);
       ++nnode;
       if (cw != 0u) {
         if (q0 == 0u)

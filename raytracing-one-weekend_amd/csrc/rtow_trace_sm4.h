@@ -32,7 +32,6 @@ __global__ void __launch_bounds__(1024) RTOW_CAT(rtow_trace4_, RTOW_SUFFIX)(cons
   const uint32_t k0 = P.seed_lo, k1 = P.seed_hi;
   const unsigned lane = lane_id();
   const uint32_t lane_g = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t npix_local = (uint32_t)P.local_rows * (uint32_t)P.W;
   const uint32_t kRestartVotes = P.sm4_restart, kScatterVotes = P.sm4_scatter, kLeafVotes = P.sm4_leaf;  // (wave-uniform)
 
   Bvh4Reader<FULL> im;
@@ -106,23 +105,24 @@ __global__ void __launch_bounds__(1024) RTOW_CAT(rtow_trace4_, RTOW_SUFFIX)(cons
         if (need_mask != 0ull) {
           const RTOW_CONST TraceParams *kp = (const RTOW_CONST TraceParams *)__builtin_amdgcn_kernarg_segment_ptr();
           asm volatile("" : "+s"(kp));  // opaque per trip: keeps the loads from being hoisted out of the loop
+          const FetchHead fh = load_fetch_head(kp);
           if (need_item && item != 0xffffffffu) {
-            double *dst = P.partials + (size_t)item * 3;
+            double *dst = fh.partials + (size_t)item * 3;
             dst[0] = acc.x;
             dst[1] = acc.y;
             dst[2] = acc.z;
           }
-          const unsigned long long mine = take_items(pool, need_mask, lane, n_waves, kp, P.counters);
+          const unsigned long long mine = take_items(pool, need_mask, lane, n_waves, fh);
           if (need_item) {
-            if (mine >= (unsigned long long)kp->n_items) {
+            if (mine >= (unsigned long long)fh.n_items) {
               phase = PH_DEAD;
               item = 0xffffffffu;
             } else {
-              const ItemPos ip = decode_item(kp, (uint32_t)mine, npix_local);
+              const ItemPos ip = decode_item(kp, fh, (uint32_t)mine);
               item = ip.item;
               j = ip.j;
               gi = ip.gi;
-              g.pixel = gi * (uint32_t)kp->W + j;
+              g.pixel = gi * (uint32_t)fh.W + j;
               g.sample = ip.sample0;
               s_left = ip.count;
               acc = {0.0, 0.0, 0.0};
