@@ -380,7 +380,8 @@ typedef struct rtow_hit_t {   /* 72 B */
  *              RTOW_KERNEL_REFTREE is strict only (RTOW_EINVAL otherwise) and builds the reference's tree on first use.
  *   tmax       post-filter: the closest hit over [0.001, inf) is reported when its t <= tmax, else a miss (exact: the
  *              closest hit lies within tmax exactly when any hit does).  The walks are not seeded with tmax, so a
- *              short tmax prunes nothing.
+ *              short tmax prunes nothing.  (rtow_first_hits_device with max_hits == 1 is the closest hit with
+ *              tmax-seeded walks: the same record wherever the closest t is not an exact tie, for what lies within tmax.)
  *   time       results are independent of the kernel for time in [0, 1] only: the moving spheres' boxes cover that
  *              interval (the reference's BVH has the same property).
  * Errors: RTOW_EINVAL for a NULL ctx, NULL buffers with n_rays > 0, n_rays < 0 or > 2^31 - 64, misaligned buffers, an
@@ -422,6 +423,55 @@ int rtow_occluded_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const
 /* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
 int rtow_occluded(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
                   uint8_t *occluded, rtow_stats_t *stats);
+
+/* ---- first-k-hits (ordered multi-hit) ray queries -------------------------------------------------------------------
+ * "What are the first k things this ray passes through, in order?" — ordered transparency, thickness and layer counts,
+ * picking through glass, shadow rays that skip dielectrics, depth peeling — in one launch, without the epsilon a chain
+ * of rtow_intersect calls from each hit point needs, and exact where primitives tie.
+ *
+ *   hit set    For ray i, H is the set of primitives whose reference hit test (Sphere::hit, MovingSphere, Triangle::hit)
+ *              accepts a t in [0.001, ray.tmax], each with that t: ONE entry per primitive.  A sphere contributes the
+ *              root the reference picks — the near root if it is >= 0.001, else the far root; the exit of a sphere
+ *              entered at t is found by a follow-up ray from that hit.  Triangles are hit only where det >= 1e-6, as
+ *              everywhere else in the library.
+ *   order      H ascending by (t, insertion index) — the insertion index is rtow_hit_t::prim.  The tie rule is part of
+ *              the contract: it makes the answer independent of kernel, builder and scheduling, also when a tie
+ *              straddles slot max_hits.
+ *   output     counts[i] = min(|H|, max_hits); hits[i][j] for j < counts[i] is the full rtow_hit_t of the j-th entry —
+ *              exactly the fields rtow_intersect writes for that primitive and ray; slots j >= counts[i] hold the miss
+ *              record (t = +inf, zeros, -1, -1, -1, 0).  All max_hits slots of every ray are written; nothing is
+ *              written beyond n_rays * max_hits records or beyond n_rays counts.  d_counts may be NULL.
+ *   tmax       below 0.001, or NaN: count 0 without a walk.  The walks are seeded with tmax, and once max_hits entries
+ *              are kept they cull at the t of the last one (inclusive: every member of a tie is still visited).
+ *   max_hits   1 .. RTOW_MAX_HITS.  max_hits == 1 is the closest hit with tmax-seeded walks (see the tmax note of
+ *              rtow_intersect_device), ties resolved to the lowest insertion index.
+ *   precision  RTOW_F64_STRICT: bit-identical to the definition above under BRUTE, BVH, GRID and BVH4, with either
+ *                               builder, for time in [0, 1];
+ *              RTOW_F64_FAST:   the fast build's tests and walks.  On a ray all of whose decisions are clear of the
+ *                               rounding band of rtow_intersect_device — t against tmax and the gaps between consecutive
+ *                               hits up to the first one left out included — the sequence is the exact one; on any
+ *                               other ray it is one the band allows.  An exactly tangent ray misses that sphere; GRID's
+ *                               triangle cut is det >= 1e-6 |d|;
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ *   kernel     AUTO, fallbacks, residency rules (RTOW_ENOSCENE after a lean upload) and kernel_used as in
+ *              rtow_intersect_device.  RTOW_KERNEL_REFTREE: RTOW_EINVAL (the reference's tree misses hits by design and
+ *              has no multi-hit meaning; as in rtow_closest_point).
+ * d_rays: rtow_ray_t, DEVICE memory, 16-byte aligned; d_hits: n_rays * max_hits rtow_hit_t, 8-byte aligned; d_counts:
+ * n_rays int32_t, 4-byte aligned, or NULL.  Enqueued on hip_stream with the ordering rule of rtow_intersect_device (a
+ * non-blocking stream waits for the last upload or refit); returns without synchronising unless stats != NULL, which
+ * synchronises and fills segments = n_rays, prim_tests and node_tests (BRUTE counts the tests it ran), kernel_ms,
+ * total_ms, kernel_used; samples = local_rows = 0.
+ * Errors: those of rtow_intersect_device; max_hits outside [1, RTOW_MAX_HITS] is RTOW_EINVAL.  n_rays == 0 returns
+ * RTOW_OK and launches nothing.  One call in flight per context; the render path, the profile ring and the
+ * dropped-sample word are not involved: a render or an rtow_intersect after any number of these calls is bit-identical
+ * to one without them. */
+#define RTOW_MAX_HITS 8
+int rtow_first_hits_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays,
+                           int32_t max_hits, void *d_hits /* rtow_hit_t[n_rays][max_hits] */,
+                           void *d_counts /* int32_t[n_rays] or NULL */, void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
+int rtow_first_hits(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays,
+                    int32_t max_hits, rtow_hit_t *hits, int32_t *counts /* or NULL */, rtow_stats_t *stats);
 
 /* ---- closest-point (distance) queries -------------------------------------------------------------------------------
  * "What is the nearest surface to this point?" — for every query point p, the primitive of the resident scene nearest

@@ -256,6 +256,12 @@ QueryLaunchFn launch_query_strict, launch_query_fast, launch_occlude_strict, lau
     launch_pointq_fast;
 QueryOccupancyFn query_occupancy_strict, query_occupancy_fast, occlude_occupancy_strict, occlude_occupancy_fast,
     pointq_occupancy_strict, pointq_occupancy_fast;
+// csrc/rtow_first_hits_{strict,fast}.hip (rtow_first_hits.h): the first-k-hits query — max_hits records and one count per ray
+using FirstHitsLaunchFn = int(const TraceParams &p, const void *rays, void *hits, int32_t *counts, uint32_t n,
+                              int32_t max_hits, const int32_t *map, unsigned long long *counters, int kernel, int grid,
+                              int block, unsigned lds_bytes, void *stream);
+FirstHitsLaunchFn launch_first_hits_strict, launch_first_hits_fast;
+QueryOccupancyFn first_hits_occupancy_strict, first_hits_occupancy_fast;
 // csrc/rtow_radiance_{strict,fast}.hip (rtow_radiance.h): the radiance query; `p` carries the seed, max_child_rays and
 // the strict build's path stack beside the walks' fields
 using RadianceLaunchFn = int(const TraceParams &p, const void *rays, const void *ids, void *out, uint32_t n,
@@ -481,6 +487,7 @@ struct rtow_ctx {
   DevBuf q_counters, q_spill, q_rays, q_hits, q_occ, q_map[3];
   DevBuf q_stack, q_ids, q_rgb;  // rtow_radiance*: the strict build's path stack (sized per launch), the host form's staging
   DevBuf q_guides;               // rtow_guides: the host form's staging (rtow_camera_rays stages in q_rays / q_ids)
+  DevBuf q_khits, q_kcounts;     // rtow_first_hits: the host form's staging (its rays go through q_rays)
   bool q_map_ok[3] = {false, false, false};
   hipEvent_t q_ev[4] = {};
   unsigned long long *h_qcounters = nullptr;
@@ -560,7 +567,7 @@ void rtow_ctx_destroy(rtow_ctx *c) {
                     &c->blob32, &c->gblob32, &c->cam32_dev, &c->blob4,
                     &c->partials, &c->stack, &c->counters, &c->spill, &c->out, &c->out8, &c->rtree, &c->counters_init,
                     &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_occ, &c->q_map[0], &c->q_map[1],
-                    &c->q_map[2], &c->q_stack, &c->q_ids, &c->q_rgb, &c->q_guides,
+                    &c->q_map[2], &c->q_stack, &c->q_ids, &c->q_rgb, &c->q_guides, &c->q_khits, &c->q_kcounts,
                     &c->rf.map2, &c->rf.map4, &c->rf.par2, &c->rf.par4, &c->rf.need4, &c->rf.flags,
                     &c->rf.nbox2, &c->rf.nbox4, &c->rf.sbox4, &c->rf.pbox, &c->rf.partials, &c->rf.area, &c->rf.g_sph,
                     &c->rf.g_mov, &c->rf.g_tri, &c->tile_table})
@@ -2206,6 +2213,67 @@ static int query_host(rtow_ctx *c, const QueryKind &k, int32_t precision, int32_
   return RTOW_OK;
 }
 
+// The first-k-hits query (rtow_first_hits*, csrc/rtow_first_hits.h): the closest-hit query's checks, strategy, launch
+// shape, ordering, stats and id translation (query_begin / query_launch / query_map) around a kernel that writes max_hits
+// records and one count per ray.  REFTREE is refused (the reference's tree misses hits by design: no multi-hit meaning).
+// BRUTE uses no LDS (its walk reads the class-major arrays) and counts the tests it ran.
+static int first_hits_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_rays, int64_t n,
+                             int32_t max_hits, void *d_hits, void *d_counts, void *hip_stream, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
+  if (max_hits < 1 || max_hits > RTOW_MAX_HITS)
+    return fail(RTOW_EINVAL, "max_hits %d outside [1, %d]", max_hits, RTOW_MAX_HITS);
+  if (n > 0 && (!d_rays || !d_hits)) return fail(RTOW_EINVAL, "NULL ray or hit buffer");
+  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
+  if (((uintptr_t)d_hits & 7u) != 0u) return fail(RTOW_EINVAL, "hit buffer must be 8-byte aligned");
+  if (((uintptr_t)d_counts & 3u) != 0u) return fail(RTOW_EINVAL, "count buffer must be 4-byte aligned");
+  if (kernel_req == RTOW_KERNEL_REFTREE)
+    return fail(RTOW_EINVAL, "first-hits queries: RTOW_KERNEL_REFTREE has no multi-hit meaning");
+  QueryRun q;
+  int rc;
+  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
+  if (n == 0) return RTOW_OK;
+
+  const int kernel = q.kernel;
+  const int32_t *map = nullptr;
+  const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
+  if ((rc = query_map(c, which, &map))) return rc;
+  const int block = q.shape.block;
+  const unsigned lds = kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;
+  const int build = q.strict ? 0 : 1;
+  rtow::FirstHitsLaunchFn *const launch[2] = {rtow::launch_first_hits_strict, rtow::launch_first_hits_fast};
+  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::first_hits_occupancy_strict, rtow::first_hits_occupancy_fast};
+  const int occ = occupancy[build](kernel, block, lds, nullptr);
+  return query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
+    return launch[build](P, d_rays, d_hits, (int32_t *)d_counts, (uint32_t)n, max_hits, map, counters, kernel, grid, block,
+                         lds, hip_stream);
+  });
+}
+
+static int first_hits_host(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n,
+                           int32_t max_hits, rtow_hit_t *hits, int32_t *counts, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
+  if (max_hits < 1 || max_hits > RTOW_MAX_HITS)
+    return fail(RTOW_EINVAL, "max_hits %d outside [1, %d]", max_hits, RTOW_MAX_HITS);
+  if (n > 0 && (!rays || !hits)) return fail(RTOW_EINVAL, "NULL ray or hit array");
+  if (n == 0) return first_hits_device(c, precision, kernel, nullptr, 0, max_hits, nullptr, nullptr, nullptr, stats);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t hit_bytes = (size_t)n * (size_t)max_hits * sizeof(rtow_hit_t);
+  int rc;
+  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_ray_t))) || (rc = c->q_khits.ensure(hit_bytes)) ||
+      (counts && (rc = c->q_kcounts.ensure((size_t)n * sizeof(int32_t)))))
+    return rc;
+  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
+  if ((rc = first_hits_device(c, precision, kernel, c->q_rays.p, n, max_hits, c->q_khits.p, counts ? c->q_kcounts.p : nullptr,
+                              nullptr, stats)))
+    return rc;
+  HIPCHK(hipMemcpy(hits, c->q_khits.p, hit_bytes, hipMemcpyDeviceToHost));
+  if (counts) HIPCHK(hipMemcpy(counts, c->q_kcounts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return RTOW_OK;
+}
+
 // The radiance query (rtow_radiance*, csrc/rtow_radiance.h): the ray queries' strategy, launch shape, ordering and stats
 // (query_begin / query_launch) around a kernel that traces whole paths.  The launch fills what the paths need beyond the
 // walks' fields: the Philox key, the depth and — strict build — a path stack of its own, sized for this launch's lanes.
@@ -2969,6 +3037,17 @@ int rtow_closest_point_device(rtow_ctx *c, int32_t precision, int32_t kernel, co
 int rtow_closest_point(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
                        rtow_point_hit_t *hits, rtow_stats_t *stats) {
   return guarded("rtow_closest_point", [&] { return query_host(c, kClosestPoint, precision, kernel, queries, n, hits, stats); });
+}
+int rtow_first_hits_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays,
+                           int32_t max_hits, void *d_hits, void *d_counts, void *hip_stream, rtow_stats_t *stats) {
+  return guarded("rtow_first_hits_device", [&] {
+    return first_hits_device(c, precision, kernel, d_rays, n_rays, max_hits, d_hits, d_counts, hip_stream, stats);
+  });
+}
+int rtow_first_hits(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, int32_t max_hits,
+                    rtow_hit_t *hits, int32_t *counts, rtow_stats_t *stats) {
+  return guarded("rtow_first_hits",
+                 [&] { return first_hits_host(c, precision, kernel, rays, n_rays, max_hits, hits, counts, stats); });
 }
 int rtow_radiance_device(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params,
                          const void *d_rays, int64_t n_rays, const void *d_ids, void *d_rgb_sums, void *hip_stream,

@@ -3,8 +3,8 @@
 //
 // What it computes: for every caller ray, the reference's world hit over [0.001, +inf) (src/render.cpp:33-34,
 // BVHNode::hit) with the same walks the trace kernels run — closest_hit_stream / _bvh / _grid / _bvh4 / _reftree,
-// included read-only below exactly as rtow_trace_body.h includes them — then the winner's hit record rebuilt with the
-// trace kernel's shading expressions (rtow_trace_body.h, the `do_scat` block): Ray::at, the sphere normal faced
+// included read-only below exactly as rtow_trace_body.h includes them — then the winner's hit record (rtow_hit_record.h,
+// shared with the first-k-hits query) rebuilt with the trace kernel's shading expressions: Ray::at, the sphere normal faced
 // against the ray, the triangle's un-normalised e1 x e2, the material index from the scene image.  A hit beyond the
 // ray's tmax is then reported as a miss (post-filter: the closest hit in [0.001, inf) lies within tmax exactly when
 // any hit does; the walks are not seeded with tmax, so nothing is pruned by it).
@@ -44,8 +44,7 @@ namespace {
 #include "rtow_trace_reftree.h"
 #endif
 #include "rtow_kernel_frame.h"
-
-constexpr uint32_t kHitBytes = 72u;  // rtow_hit_t, include/rtow.h
+#include "rtow_hit_record.h"
 
 struct QueryParams {
   TraceParams P;               // the scene (P.sc) and the walks' launch fields: spill, n_lanes, leaf_votes, walk_max_open
@@ -125,87 +124,11 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       best = closest_hit_stream(sc, to_f64(ro), to_f64(rd), (double)rtime, active);
     }
 
-    // ---- the hit record of the winner (rtow_trace_body.h, `do_scat`: the same expressions) ----
+    // ---- the hit record of the winner (rtow_hit_record.h) ----
     const bool hit = active && best.prim >= 0 && best.t <= tmax;
-    if (active) {
-      double t = __builtin_huge_val();
-      V3 p = {0, 0, 0}, normal = {0, 0, 0};
-      int32_t prim = -1, kind = -1, mi = -1, front = 0;
-      if (hit) {
-        const int pid = best.prim;
-        t = best.t;
-        p = ro + rd * best.t;  // Ray::at (the trace kernel's scattered origin)
-        bool ff = true;        // triangles: front_facing is always true (src/common-model.cpp:121)
-        kind = pid < sc.n_sph ? 0 : (pid < sc.n_sph + sc.n_mov ? 1 : 2);
-        if constexpr (KERNEL == 4) {
-          const uint32_t r = sc.b4_off_tri + 96u * (uint32_t)pid;
-          const vd2 q4 = im4.t2(r + 64u), q5 = im4.t2(r + 80u);
-          normal = {(real)q4.y, (real)q5.x, (real)q5.y};
-          mi = (int)im4.u32(sc.b4_off_pmat + 4u * (uint32_t)pid);
-        } else if constexpr (KERNEL == 2 || KERNEL == 3) {
-          const uint32_t o_sph = KERNEL == 3 ? sc.g_off_sph : sc.off_sph;
-          const uint32_t o_mov = KERNEL == 3 ? sc.g_off_mov : sc.off_mov;
-          const uint32_t o_tri = KERNEL == 3 ? sc.g_off_tri : sc.off_tri;
-          const uint32_t o_pmat = KERNEL == 3 ? sc.g_off_pmat : sc.off_pmat;
-          if (pid < sc.n_sph + sc.n_mov) {
-            V3 center;
-            bool inward;
-            if (pid < sc.n_sph) {
-              const double2 p0 = im.d2(o_sph + 32u * (uint32_t)pid), p1 = im.d2(o_sph + 32u * (uint32_t)pid + 16u);
-              center = {(real)p0.x, (real)p0.y, (real)p1.x};
-              inward = p1.y < 0.0;
-            } else {
-              const uint32_t r = o_mov + 64u * (uint32_t)(pid - sc.n_sph);
-              const double2 p0 = im.d2(r), p1 = im.d2(r + 16u), p2 = im.d2(r + 32u), p3 = im.d2(r + 48u);
-              center = {p0.x + rtime * p1.y, p0.y + rtime * p2.x, p1.x + rtime * p2.y};
-              inward = p3.x < 0.0;
-            }
-            normal = normalize(p - center);
-            ff = (dot(rd, normal) < real(0.0)) ^ inward;
-            normal = ff ? normal : -normal;
-          } else {
-            const uint32_t r = o_tri + 96u * (uint32_t)(pid - sc.n_sph - sc.n_mov);
-            const double2 q4 = im.d2(r + 64u), q5 = im.d2(r + 80u);
-            normal = {q4.y, q5.x, q5.y};
-          }
-          mi = (int)im.u32(o_pmat + 4u * (uint32_t)pid);
-        } else {
-          if (pid < sc.n_sph + sc.n_mov) {
-            V3 center;
-            bool inward;
-            if (pid < sc.n_sph) {
-              const double *q = sc.sph + 4 * (size_t)pid;
-              center = {(real)q[0], (real)q[1], (real)q[2]};
-              inward = sc.sph_r[pid] < 0.0;
-            } else {
-              const double *q = sc.mov + 8 * (size_t)(pid - sc.n_sph);
-              center = {q[0] + rtime * q[3], q[1] + rtime * q[4], q[2] + rtime * q[5]};
-              inward = q[7] < 0.0;
-            }
-            normal = normalize(p - center);
-            ff = (dot(rd, normal) < real(0.0)) ^ inward;
-            normal = ff ? normal : -normal;
-          } else {
-            const double *q = sc.tri + 12 * (size_t)(pid - sc.n_sph - sc.n_mov);
-            normal = {(real)q[9], (real)q[10], (real)q[11]};
-          }
-          mi = sc.prim_mat[pid];
-        }
-        prim = Q.map[pid];
-        front = ff ? 1 : 0;
-      }
-      double *h = reinterpret_cast<double *>(Q.hits + (size_t)i * kHitBytes);
-      h[0] = t;
-      h[1] = p.x;
-      h[2] = p.y;
-      h[3] = p.z;
-      h[4] = normal.x;
-      h[5] = normal.y;
-      h[6] = normal.z;
-      int32_t *hi = reinterpret_cast<int32_t *>(h + 7);
-      reinterpret_cast<int2 *>(hi)[0] = make_int2(prim, kind);
-      reinterpret_cast<int2 *>(hi)[1] = make_int2(mi, front);
-    }
+    if (active)
+      write_hit_record<KERNEL, LDS>(im, im4, sc, Q.map, ro, rd, rtime, hit, best.prim, best.t,
+                                    Q.hits + (size_t)i * kHitBytes);
   }
 
   // statistics: one atomic per wave and counter

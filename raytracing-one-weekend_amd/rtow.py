@@ -25,6 +25,7 @@ MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2
 PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_TRIANGLE = 0, 1, 2
 F64_STRICT, F64_FAST, F32 = 0, 1, 2
 KERNEL_AUTO, KERNEL_BRUTE, KERNEL_BVH, KERNEL_GRID, KERNEL_BVH4, KERNEL_REFTREE = 0, 1, 2, 3, 4, 5
+MAX_HITS = 8  # RTOW_MAX_HITS: the most entries rtow_first_hits keeps per ray
 SPEC_GENERIC, SPEC_STATIC_SPHERES, SPEC_MOVING_SPHERES, SPEC_FLAT_Y = 0, 1, 2, 4  # Context.last_spec()
 MODEL_OO, MODEL_VARIANT, MODEL_WORLD = 0, 1, 2  # scene models of the host scene scripts (include/rtow.h)
 BUILDER_HOST_SAH, BUILDER_DEVICE_LBVH, BUILDER_AUTO = 0, 1, 2
@@ -198,7 +199,7 @@ EXPORTS = [
     "rtow_scene_refit", "rtow_refit_info", "rtow_closest_point_device", "rtow_closest_point",
     "rtow_debug_tile_order", "rtow_radiance_device", "rtow_radiance",
     "rtow_camera_rays_device", "rtow_camera_rays", "rtow_camera_ray_count", "rtow_guides_device", "rtow_guides",
-    "rtow_debug_last_spec",
+    "rtow_debug_last_spec", "rtow_first_hits_device", "rtow_first_hits",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -285,6 +286,11 @@ def lib():
                                            C.c_void_p, C.POINTER(Stats)]
         L.rtow_occluded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.POINTER(Stats)]
+    if hasattr(L, "rtow_first_hits"):
+        L.rtow_first_hits_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rtow_first_hits.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.POINTER(Stats)]
     if hasattr(L, "rtow_closest_point"):
         L.rtow_closest_point_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                                 C.c_void_p, C.POINTER(Stats)]
@@ -563,6 +569,31 @@ class Context:
         check(lib().rtow_occluded_device(self._h, precision, kernel, C.c_void_p(d_rays), n, C.c_void_p(d_occluded),
                                          C.c_void_p(stream), C.byref(st) if st is not None else None),
               "rtow_occluded_device")
+        return st
+
+    def first_hits(self, rays, max_hits, precision=F64_FAST, kernel=KERNEL_AUTO, want_stats=False):
+        """The first `max_hits` (1 .. MAX_HITS) primitives every ray (a RAY_DTYPE array, host memory) passes through
+        within [0.001, tmax], ordered by (t, insertion index): (hits, counts) — an [n, max_hits] HIT_DTYPE array whose
+        unused slots hold the miss record, and int32 [n] — plus Stats with `want_stats` (rtow_first_hits)."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        hits = np.empty((len(r), max(int(max_hits), 0)), dtype=HIT_DTYPE)
+        counts = np.empty(len(r), dtype=np.int32)
+        st = Stats() if want_stats else None
+        check(lib().rtow_first_hits(self._h, precision, kernel, r.ctypes.data_as(C.c_void_p), len(r), int(max_hits),
+                                    hits.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                    C.byref(st) if st is not None else None), "rtow_first_hits")
+        return (hits, counts, st) if want_stats else (hits, counts)
+
+    def first_hits_device(self, d_rays: int, n: int, max_hits: int, d_hits: int, d_counts: int = 0, precision=F64_FAST,
+                          kernel=KERNEL_AUTO, stream: int = 0, want_stats=False):
+        """The same on device buffers (raw pointers: n x 64-byte rays, n x max_hits x 72-byte hits, n int32 counts or 0
+        for none), enqueued on `stream` (rtow_first_hits_device); returns Stats with `want_stats` (then synchronised),
+        else None."""
+        st = Stats() if want_stats else None
+        check(lib().rtow_first_hits_device(self._h, precision, kernel, C.c_void_p(d_rays), n, int(max_hits),
+                                           C.c_void_p(d_hits), C.c_void_p(d_counts) if d_counts else None,
+                                           C.c_void_p(stream), C.byref(st) if st is not None else None),
+              "rtow_first_hits_device")
         return st
 
     def closest_point(self, queries, precision=F64_FAST, kernel=KERNEL_AUTO, want_stats=False):
