@@ -6,20 +6,13 @@
 // entry per primitive, with the root that test picks — ordered ascending by (t, insertion index) and cut at max_hits
 // (1 .. 8): max_hits full rtow_hit_t records per ray (the unused ones the miss record) and the count.
 //
-// The walks below are the any-hit walks of rtow_occlude.h (the render's walks seeded with tmax, without suspend /
-// resume) with two changes: a hit does not end a lane's walk, and the bound the boxes, cells and primitive tests cull
-// against is tmax while the lane's list holds fewer than max_hits entries and the t of entry max_hits - 1 after that.
-// The pieces they are built from (Image, the ray forms, leaf_test, the hit tests, the 4-wide step, leaf and stack) are
-// the render's, included read-only.
-//
-// Why the shrinking bound is exact: a primitive's test with upper bound b accepts exactly when its unbounded test
-// returns a t <= b (rtow_occlude.h: sphere_resolve picks its root by tmin alone, a triangle has one t), with the same
-// bits.  Once max_hits entries are kept, a primitive with t above the last of them cannot enter; one with t equal to it
-// still can (lower insertion index), and the bound is inclusive everywhere — the box and cell intervals are conservative
-// f32 supersets compared with <=, the primitive tests accept t <= bound — so every member of a tie at the bound is
-// visited.  The bound only shrinks, so a subtree, cell or primitive once rejected stays rejected.  Hence the kept list
-// equals "all of H, sorted, cut at max_hits", whatever order the walk met the primitives in: bit-determined in the
-// strict build, the same under every strategy, builder and schedule.
+// The BVH, GRID and BVH4 walks are the tmax-bounded walks of rtow_bounded_walks.h with the list sink below: a hit does
+// not end a lane's walk, and the bound is tmax while the lane's list holds fewer than max_hits entries and the t of
+// entry max_hits - 1 after that.  Once max_hits entries are kept, a primitive with t above the last of them cannot
+// enter; one with t equal to it still can (lower insertion index), and the walks visit every member of a tie at the
+// bound (that header: inclusive comparisons, a bound that only shrinks).  Hence the kept list equals "all of H, sorted,
+// cut at max_hits", whatever order the walk met the primitives in: bit-determined in the strict build, the same under
+// every strategy, builder and schedule.
 //
 // The list: 8 (t, walk id) pairs per lane in registers, sorted by (t, insertion index); insertion is a fully unrolled
 // compare-and-shift over eight named slots (no scratch: see HitList).  The insertion index (`map[id]`) is read only to break an
@@ -53,6 +46,7 @@ namespace {
 #include "rtow_trace_grid.h"
 #include "rtow_trace_bvh4.h"
 #include "rtow_kernel_frame.h"
+#include "rtow_bounded_walks.h"
 #include "rtow_hit_record.h"
 
 struct FirstHitsParams {
@@ -151,225 +145,78 @@ __device__ __forceinline__ Closest candidate(double bound) {
   return c;
 }
 
-// ---- BVH: the threaded walk of any_hit_bvh (rtow_occlude.h), bound from the list, no early exit ----
+// ---- the list sink of the bounded walks (rtow_bounded_walks.h) ----
+// One primitive per test: the hit tests overwrite one Closest, and every accepted primitive is a candidate.  The lane is
+// never done.  In the fast build's grid walk the list holds distances, and so does the bound (the kernel converts at
+// output, as closest_hit_grid does when its walk is complete).
+struct FirstHitsSink {
+  static constexpr bool kFold = false;  // the slack is multiplied per node, as in the state machine — six registers the list needs
+  HitList &L;
+  int max_hits;
+  const int32_t *map;
+  double bound;
+  int last_id;  // leaf_test's one-entry mailbox, kept across the grid's cells: a repeat was tested against a bound no smaller
+  __device__ __forceinline__ void seed(double tmax) {
+    list_clear(L, tmax);
+    bound = tmax;
+    last_id = -1;
+  }
+  __device__ __forceinline__ float bound32() const { return round_up_f32(bound); }
+  __device__ __forceinline__ bool done() const { return false; }
+  // CELL: a grid cell (a primitive is listed in every cell it overlaps: mailbox and DEDUP); else a BVH leaf
+  template <bool LDS, bool CELL>
+  __device__ __forceinline__ void list(const Image<LDS> &im, const DevScene &sc, const ImgOffsets &off, uint32_t first,
+                                       uint32_t count, const RayForms &ray, uint32_t &nprim) {
+    for (uint32_t k = 0; k < count; ++k) {
+      Closest c = candidate(bound);
+      int none = -1;
+      leaf_test<LDS, CELL>(im, sc, off, first + k, 1u, ray, c, nprim, CELL ? last_id : none);
+      list_take<CELL>(L, c, map, max_hits, bound);
+    }
+  }
+  template <bool LDS>
+  __device__ __forceinline__ void large(const Image<LDS> &im, const DevScene &sc, const ImgOffsets &off, uint32_t lf,
+                                        uint32_t n_large, const RayForms &ray, uint32_t &nprim) {
+    for (uint32_t k = 0; k < n_large; ++k) {
+      Closest c = candidate(bound);
+      int none = -1;
+      leaf_test<LDS, false, 0, true>(im, sc, off, lf + k, 1u, ray, c, nprim, none);
+      list_take<true>(L, c, map, max_hits, bound);
+    }
+  }
+  // the leaf's triangles as one-triangle leaves (leaf word: rtow_bvh4.h, [first : 18][count - 1 : 2])
+  template <bool FULL>
+  __device__ __forceinline__ void leaf4(const Bvh4Reader<FULL> &im, const DevScene &sc, uint32_t leaf, V3d o64, V3d d64,
+                                        uint32_t &nprim) {
+    const uint32_t first = (leaf & (kRefLeaf - 1u)) >> 2, count = (leaf & 3u) + 1u;
+    for (uint32_t k = 0; k < count; ++k) {
+      Closest c = candidate(bound);
+      bvh4_leaf<FULL>(im, sc, kRefLeaf | ((first + k) << 2), o64, d64, c, nprim);
+      list_take<false>(L, c, map, max_hits, bound);
+    }
+  }
+};
+
 template <bool LDS>
 __device__ __forceinline__ void first_hits_bvh(const Image<LDS> &im, const DevScene &sc, V3 o, V3 d, real time, double tmax,
                                                bool active, int max_hits, const int32_t *map, HitList &L,
                                                uint32_t &nnode, uint32_t &nprim) {
-  list_clear(L, tmax);
-  double bound = tmax;
-  const RayForms ray = make_ray_forms(o, d, time);
-  const float ix = safe_inv((float)d.x), iy = safe_inv((float)d.y), iz = safe_inv((float)d.z);
-  const float oix = (float)o.x * ix, oiy = (float)o.y * iy, oiz = (float)o.z * iz;
-  const float tmin32 = 0.0009f;  // < RTOW_TMIN
-  const float slack = 1.00002f;  // relative slack on the far side of the interval
-  float tmax32 = round_up_f32(bound);
-  const uint32_t END = (uint32_t)sc.n_nodes;
-  const ImgOffsets off = {sc.off_ids, sc.off_sph, sc.off_mov, sc.off_tri, 0u, 0u, sc.off_sph32, sc.off_mov32};
-  uint32_t node = active ? 0u : END;
-  uint32_t q0 = 0u, q1 = 0u, q2 = 0u, q3 = 0u;  // queued leaves (0 = empty), oldest first
-  for (;;) {
-    if (node < END) {
-      const float4 r0 = im.f4(node * 32u), r1 = im.f4(node * 32u + 16u);
-      ++nnode;
-      const float ax = fmaf(r0.x, ix, -oix), bx = fmaf(r0.w, ix, -oix);
-      const float ay = fmaf(r0.y, iy, -oiy), by = fmaf(r1.x, iy, -oiy);
-      const float az = fmaf(r0.z, iz, -oiz), bz = fmaf(r1.y, iz, -oiz);
-      const float tnear = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tmin32));
-      const float tfar = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tmax32));
-      const bool hit = tnear <= tfar * slack;
-      const uint32_t skip = __float_as_uint(r1.z), leaf = __float_as_uint(r1.w);
-      if (hit && leaf != 0u) {
-        if (q0 == 0u)
-          q0 = leaf;
-        else if (q1 == 0u)
-          q1 = leaf;
-        else if (q2 == 0u)
-          q2 = leaf;
-        else
-          q3 = leaf;
-      }
-      node = (hit && leaf == 0u) ? node + 1u : skip;
-    }
-    const bool any_walking = __any(node < END);
-    if (__any(q3 != 0u) || !any_walking) {
-      if (q0 != 0u) {
-        // one primitive per test: the hit tests overwrite one Closest, and every accepted primitive is a candidate
-        const uint32_t first = q0 >> 3, count = q0 & 7u;
-        for (uint32_t k = 0; k < count; ++k) {
-          Closest c = candidate(bound);
-          int last_id = -1;
-          leaf_test<LDS, false>(im, sc, off, first + k, 1u, ray, c, nprim, last_id);
-          list_take<false>(L, c, map, max_hits, bound);
-        }
-        tmax32 = round_up_f32(bound);
-      }
-      q0 = q1;
-      q1 = q2;
-      q2 = q3;
-      q3 = 0u;
-      if (!__any(node < END) && !__any(q0 != 0u)) break;
-    }
-  }
+  FirstHitsSink sink{L, max_hits, map};
+  bounded_walk_bvh<LDS>(im, sc, o, d, time, tmax, active, sink, nnode, nprim);
 }
-
-// ---- GRID: the 3D-DDA of any_hit_grid (rtow_occlude.h: step sign from the reciprocal), bound from the list ----
-// The fast build walks the unit direction: the list holds distances, and so does the bound (the kernel converts at
-// output, as closest_hit_grid does when its walk is complete).
 template <bool LDS>
 __device__ __forceinline__ void first_hits_grid(const Image<LDS> &im, const DevScene &sc, V3 o, V3 d, real time,
-                                                  double tmax, bool active, int max_hits, const int32_t *map, HitList &L,
-                                                  uint32_t &nnode, uint32_t &nprim, uint32_t leaf_votes) {
-#ifdef RTOW_UNIT_RAYS
-  const double a_ref = dot(d, d);
-  const double inv_len = fast_rsqrt(a_ref), len = a_ref * inv_len;
-  d = d * inv_len;
-  const RayForms ray = make_unit_ray_forms(o, d, time, len);
-  const float tmin32w = 0.0009f * (float)len;
-  const double tmaxw = tmax * len;
-#else
-  const RayForms ray = make_ray_forms(o, d, time);
-  const float tmin32w = 0.0009f;
-  const double tmaxw = tmax;
-#endif
-  list_clear(L, tmaxw);
-  double bound = tmaxw;
-  ImgOffsets off = {sc.g_off_ids, sc.g_off_sph, sc.g_off_mov, sc.g_off_tri, 0u, 0u, sc.g_off_sph32, sc.g_off_mov32};
-  const RTOW_CONST float *hf = (const RTOW_CONST float *)sc.gblob;
-  const RTOW_CONST int32_t *hi = (const RTOW_CONST int32_t *)sc.gblob;
-  const float gx = hf[0], gy = hf[1], gz = hf[2];
-  const float cx = hf[3], cy = hf[4], cz = hf[5];
-  const float icx = hf[6], icy = hf[7], icz = hf[8];
-  const int nx = hi[9], ny = hi[10], nz = hi[11];
-  const uint32_t n_large = (uint32_t)hi[12], off_large = (uint32_t)hi[13];
-  off.fat = (uint32_t)hi[14];
-  off.fat_stride = (uint32_t)hi[15];
-
-  // the large primitives (the ground sphere), for every ray, one at a time
-  if (active && n_large != 0u) {
-    const uint32_t lf = (off_large - off.ids) >> 2;
-    for (uint32_t k = 0; k < n_large; ++k) {
-      Closest c = candidate(bound);
-      int last_id = -1;
-      leaf_test<LDS, false, 0, true>(im, sc, off, lf + k, 1u, ray, c, nprim, last_id);
-      list_take<true>(L, c, map, max_hits, bound);
-    }
-  }
-  float tmax32 = round_up_f32(bound);
-  stage_prio<kPrioSetup>();  // (the issue priorities of any_hit_grid: set-up, cell walk, cell lists)
-
-  const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;
-  const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
-  const float ix = safe_inv(dx), iy = safe_inv(dy), iz = safe_inv(dz);
-  const float oix = ox * ix, oiy = oy * iy, oiz = oz * iz;
-  const float hx = fmaf((float)nx, cx, gx), hy = fmaf((float)ny, cy, gy), hz = fmaf((float)nz, cz, gz);
-  const float ax = fmaf(gx, ix, -oix), bx = fmaf(hx, ix, -oix);
-  const float ay = fmaf(gy, iy, -oiy), by = fmaf(hy, iy, -oiy);
-  const float az = fmaf(gz, iz, -oiz), bz = fmaf(hz, iz, -oiz);
-  const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tmin32w));
-  const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tmax32));
-  bool walking = active && t0 <= t1 * 1.00002f;
-
-  const float px = fmaf(t0, dx, ox), py = fmaf(t0, dy, oy), pz = fmaf(t0, dz, oz);
-  int c0 = (int)floorf((px - gx) * icx), c1 = (int)floorf((py - gy) * icy), c2 = (int)floorf((pz - gz) * icz);
-  c0 = min(max(c0, 0), nx - 1);
-  c1 = min(max(c1, 0), ny - 1);
-  c2 = min(max(c2, 0), nz - 1);
-  const bool fx = !(ix < 0.0f), fy = !(iy < 0.0f), fz = !(iz < 0.0f);  // the sign of the reciprocal: -0.0 steps down
-  float tmx = fmaf(fmaf((float)(c0 + (fx ? 1 : 0)), cx, gx), ix, -oix);
-  float tmy = fmaf(fmaf((float)(c1 + (fy ? 1 : 0)), cy, gy), iy, -oiy);
-  float tmz = fmaf(fmaf((float)(c2 + (fz ? 1 : 0)), cz, gz), iz, -oiz);
-  const float tdx = fabsf(cx * ix), tdy = fabsf(cy * iy), tdz = fabsf(cz * iz);
-  int remx = fx ? nx - 1 - c0 : c0, remy = fy ? ny - 1 - c1 : c1, remz = fz ? nz - 1 - c2 : c2;
-  const int incx = fx ? 1 : -1, incy = fy ? nx : -nx, incz = fz ? nx * ny : -(nx * ny);
-  int idx = (c2 * ny + c1) * nx + c0;
-
-  int last_id = -1;  // leaf_test's one-entry mailbox, kept across cells: a repeat was tested against a bound no smaller
-  stage_prio<kPrioStage>();
-  uint32_t q0 = 0u, q1 = 0u;
-  for (;;) {
-    if (walking && q1 == 0u) {  // (a lane with two cells queued waits for the next leaf phase)
-      const uint32_t cw = im.u32(sc.g_off_cells + 4u * (uint32_t)idx);
-      ++nnode;
-      if (cw != 0u) {
-        if (q0 == 0u)
-          q0 = cw;
-        else
-          q1 = cw;
-      }
-      const float tnext = fminf(fminf(tmx, tmy), tmz);
-      const bool sx = tmx == tnext;
-      const bool sy = !sx && tmy == tnext;
-      const int rem = sx ? remx : (sy ? remy : remz);
-      walking = rem > 0 && !(tnext > tmax32);
-      idx += sx ? incx : (sy ? incy : incz);
-      tmx += sx ? tdx : 0.0f;
-      tmy += sy ? tdy : 0.0f;
-      tmz += (!sx && !sy) ? tdz : 0.0f;
-      remx -= sx ? 1 : 0;
-      remy -= sy ? 1 : 0;
-      remz -= (!sx && !sy) ? 1 : 0;
-    }
-    const bool any_walking = __any(walking);
-    const unsigned long long m_pending = __ballot(q0 != 0u);
-    if ((m_pending != 0ull && ((uint32_t)__popcll(m_pending) >= leaf_votes || __ballot(walking && q1 == 0u) == 0ull)) ||
-        !any_walking) {
-      stage_prio<kPrioLeaf>();
-      if (q0 != 0u) {
-        const uint32_t first = q0 >> 8, count = q0 & 255u;
-        for (uint32_t k = 0; k < count; ++k) {
-          Closest c = candidate(bound);
-          leaf_test<LDS, true>(im, sc, off, first + k, 1u, ray, c, nprim, last_id);
-          list_take<true>(L, c, map, max_hits, bound);
-        }
-        tmax32 = round_up_f32(bound);
-      }
-      q0 = q1;
-      q1 = 0u;
-      stage_prio<kPrioStage>();
-      if (!__any(walking) && !__any(q0 != 0u)) break;
-    }
-  }
+                                                double tmax, bool active, int max_hits, const int32_t *map, HitList &L,
+                                                uint32_t &nnode, uint32_t &nprim, uint32_t leaf_votes) {
+  FirstHitsSink sink{L, max_hits, map};
+  bounded_walk_grid<LDS>(im, sc, o, d, time, tmax, active, sink, nnode, nprim, leaf_votes);
 }
-
-// ---- BVH4: the trip loop of any_hit_bvh4 (rtow_occlude.h), bound from the list, no early exit ----
 template <bool FULL>
 __device__ __forceinline__ void first_hits_bvh4(const Bvh4Reader<FULL> &im, const DevScene &sc, const TraceParams &P, V3 o,
                                                 V3 d, double tmax, bool active, uint32_t lane_g, int max_hits,
                                                 const int32_t *map, HitList &L, uint32_t &nnode, uint32_t &nprim) {
-  list_clear(L, tmax);
-  double bound = tmax;
-  const V3d o64 = to_f64(o), d64 = to_f64(d);
-  const Bvh4Ray ray = bvh4_ray<FULL>(sc, o, d);
-  const Bvh4Stack st = bvh4_stack(sc);
-  float tmax32 = round_up_f32(bound);
-  uint32_t sa = st.lds;
-  uint32_t cur = active ? 0u : kRefNone;  // node 0 = root
-  uint32_t q0 = kRefNone, q1 = kRefNone;  // queued leaves, oldest first
-  if constexpr (FULL) stage_prio<kPrioLeaf>();
-  for (;;) {
-    // (FOLD = false: the slack is multiplied per node, as in the state machine — six registers the list needs)
-    bvh4_step<FULL, false>(im, P, ray, tmax32, st, lane_g, cur, sa, q0, q1, nnode);
-    const bool any_walking = __any(cur != kRefNone);
-    const unsigned long long m_pending = __ballot(q0 != kRefNone);
-    if ((m_pending != 0ull && ((uint32_t)__popcll(m_pending) >= P.leaf_votes || __ballot(bvh4_busy(cur, q1)) == 0ull)) ||
-        !any_walking) {
-      if (q0 != kRefNone) {
-        // the leaf's triangles as one-triangle leaves (leaf word: rtow_bvh4.h, [first : 18][count - 1 : 2])
-        const uint32_t first = (q0 & (kRefLeaf - 1u)) >> 2, count = (q0 & 3u) + 1u;
-        for (uint32_t k = 0; k < count; ++k) {
-          Closest c = candidate(bound);
-          bvh4_leaf<FULL>(im, sc, kRefLeaf | ((first + k) << 2), o64, d64, c, nprim);
-          list_take<false>(L, c, map, max_hits, bound);
-        }
-        tmax32 = round_up_f32(bound);
-      }
-      q0 = q1;
-      q1 = kRefNone;
-      if (!__any(cur != kRefNone) && !__any(q0 != kRefNone)) break;
-    }
-  }
-  if constexpr (FULL) stage_prio<kPrioStage>();
+  FirstHitsSink sink{L, max_hits, map};
+  bounded_walk_bvh4<FULL>(im, sc, P, o, d, tmax, active, lane_g, sink, nnode, nprim);
 }
 
 // ---- STREAM: every primitive, in class order, from the class-major arrays (scalar loads: the index is wave-uniform) ----
@@ -440,14 +287,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     V3 wo = {0, 0, 0}, wd = {0, 0, 1};
     real wtime = 0;
     double tmax = 0.0;
-    if (in) {
-      const vd2 *r = reinterpret_cast<const vd2 *>(Q.rays + (size_t)i * kRayBytes);
-      const vd2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];  // {ox, oy} {oz, time} {dx, dy} {dz, tmax}
-      wo = {r0.x, r0.y, r1.x};
-      wtime = r1.y;
-      wd = {r2.x, r2.y, r3.x};
-      tmax = r3.y;
-    }
+    if (in) load_ray(Q.rays, i, wo, wd, wtime, tmax);
     // a ray whose interval [0.001, tmax] is empty (tmax NaN included) hits nothing: it skips the walk
     const bool active = in && tmax >= RTOW_TMIN;
 
@@ -465,10 +305,10 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     // ---- the records, in list order ----
     if (in) {
       // (the ray is read again rather than kept across the walk: the walk's registers go to the list)
-      const vd2 *r = reinterpret_cast<const vd2 *>(Q.rays + (size_t)i * kRayBytes);
-      const vd2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
-      const V3 ro = {r0.x, r0.y, r1.x}, rd = {r2.x, r2.y, r3.x};
-      const real rtime = r1.y;
+      V3 ro, rd;
+      real rtime;
+      [[maybe_unused]] double tmax_again;  // (not read: the walk is over)
+      load_ray(Q.rays, i, ro, rd, rtime, tmax_again);
       int32_t count = 0;
       unsigned char *dst = Q.hits + (size_t)i * (size_t)max_hits * kHitBytes;
       for (int j = 0; j < max_hits; ++j) {
@@ -487,12 +327,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     }
   }
 
-  // statistics: one atomic per wave and counter
-  const unsigned long long c0 = wave_sum(nprim), c1 = wave_sum(nnode);
-  if (lane == 0) {
-    atomicAdd(&Q.counters[0], c0);
-    atomicAdd(&Q.counters[1], c1);
-  }
+  flush_counters(Q.counters, nprim, nnode);
 }
 
 }  // namespace

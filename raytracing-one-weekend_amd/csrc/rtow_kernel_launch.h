@@ -1,6 +1,7 @@
 // rtow_kernel_launch.h — the host side of the kernel frame (rtow_kernel_frame.h): how one instantiation of a render or
 // query kernel is launched, and how many of its workgroups stay resident per CU.  Included inside `namespace rtow {`,
-// after the kernels' anonymous namespace, by rtow_trace_body.h, rtow_query.h, rtow_occlude.h and rtow_pointq.h.
+// after the kernels' anonymous namespace, by rtow_trace_body.h, rtow_query.h, rtow_occlude.h, rtow_first_hits.h,
+// rtow_pointq.h, rtow_radiance.h and rtow_guides.h.
 #pragma once
 
 // The kernels address the dynamic LDS block from 0 (lds_read / lds_write, rtow_trace_math.h): an instantiation that had

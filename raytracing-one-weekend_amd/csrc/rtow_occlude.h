@@ -2,18 +2,10 @@
 // included by rtow_occlude_strict.hip and rtow_occlude_fast.hip, which differ only in -ffp-contract and in RTOW_SUFFIX.
 //
 // What it computes: for every caller ray, 1 if some primitive's hit test accepts a t in [0.001, tmax], else 0 — the
-// shadow / visibility question.  The walks below are any-hit versions of the render's walks (rtow_trace_bvh.h,
-// rtow_trace_grid.h, rtow_trace_bvh4.h, rtow_trace_hit.h): the closest-so-far value starts at the ray's tmax instead of
-// +inf, so box and cell culling prune at tmax from the first node, and a lane stops at the end of the first leaf phase
-// in which it accepts a hit.  The pieces they are built from (Image, the ray forms, leaf_test, the hit tests, the
-// 4-wide step, leaf and stack) are the render's, included read-only; the benchmarked walks themselves are not touched.
-//
-// Why seeding is exact: a primitive's hit test with upper bound tmax accepts exactly when its unbounded test returns a
-// t <= tmax (sphere_resolve picks its root by tmin alone: root1 <= root2, so a near root beyond tmax rules out the far
-// one; a triangle has one t), and the f32 box / cell intervals are conservative as they are for the closest-hit walks.
-// So the answer equals `closest hit over [0.001, inf) <= tmax` — bit-determined in the strict build, the same under
-// every strategy.  (The fast build's grid walk compares in distance units, tmax * |d|, and its triangle test compares
-// t * det: the answer can differ from the fast closest hit's `t <= tmax` only when t is within rounding of tmax.)
+// shadow / visibility question.  The BVH, GRID and BVH4 walks are the tmax-bounded walks of rtow_bounded_walks.h with
+// the any-hit sink below: one closest-so-far value seeded with tmax, and a lane that stops at the end of the first leaf
+// phase in which it accepts a hit.  By the argument in that header the answer equals `closest hit over [0.001, inf) <=
+// tmax`: bit-determined in the strict build, the same under every strategy.
 //
 // Execution model: that of the closest-hit query (rtow_query.h): persistent waves of 64 consecutive rays, the scene
 // image staged in LDS per workgroup exactly as the render stages it, lanes past n_rays (and rays whose tmax is below
@@ -42,6 +34,7 @@ namespace {
 #include "rtow_trace_reftree.h"
 #endif
 #include "rtow_kernel_frame.h"
+#include "rtow_bounded_walks.h"
 
 struct OccludeParams {
   TraceParams P;               // the scene (P.sc) and the walks' launch fields: spill, n_lanes, leaf_votes
@@ -59,100 +52,32 @@ __device__ __forceinline__ Closest seeded(double tmax) {
   return best;
 }
 
-// ---- BVH: the threaded walk of closest_hit_bvh (rtow_trace_bvh.h), seeded, with early exit ----
-template <bool LDS>
-__device__ __forceinline__ bool any_hit_bvh(const Image<LDS> &im, const DevScene &sc, V3 o, V3 d, real time, double tmax,
-                                            bool active, uint32_t &nnode, uint32_t &nprim) {
-  Closest best = seeded(tmax);
-  const RayForms ray = make_ray_forms(o, d, time);
-  const float ix = safe_inv((float)d.x), iy = safe_inv((float)d.y), iz = safe_inv((float)d.z);
-  const float oix = (float)o.x * ix, oiy = (float)o.y * iy, oiz = (float)o.z * iz;
-  const float tmin32 = 0.0009f;  // < RTOW_TMIN
-  const float slack = 1.00002f;  // relative slack on the far side of the interval
-  const float tmax32 = round_up_f32(best.t);  // the bound: fixed, the walk ends at the first hit
-  const uint32_t END = (uint32_t)sc.n_nodes;
-  const ImgOffsets off = {sc.off_ids, sc.off_sph, sc.off_mov, sc.off_tri, 0u, 0u, sc.off_sph32, sc.off_mov32};
-  int last_id = -1;
-  uint32_t node = active ? 0u : END;
-  uint32_t q0 = 0u, q1 = 0u, q2 = 0u, q3 = 0u;  // queued leaves (0 = empty), oldest first
-  for (;;) {
-    if (node < END) {
-      const float4 r0 = im.f4(node * 32u), r1 = im.f4(node * 32u + 16u);
-      ++nnode;
-      const float ax = fmaf(r0.x, ix, -oix), bx = fmaf(r0.w, ix, -oix);
-      const float ay = fmaf(r0.y, iy, -oiy), by = fmaf(r1.x, iy, -oiy);
-      const float az = fmaf(r0.z, iz, -oiz), bz = fmaf(r1.y, iz, -oiz);
-      const float tnear = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tmin32));
-      const float tfar = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tmax32));
-      const bool hit = tnear <= tfar * slack;
-      const uint32_t skip = __float_as_uint(r1.z), leaf = __float_as_uint(r1.w);
-      if (hit && leaf != 0u) {
-        if (q0 == 0u)
-          q0 = leaf;
-        else if (q1 == 0u)
-          q1 = leaf;
-        else if (q2 == 0u)
-          q2 = leaf;
-        else
-          q3 = leaf;
-      }
-      node = (hit && leaf == 0u) ? node + 1u : skip;
-    }
-    const bool any_walking = __any(node < END);
-    if (__any(q3 != 0u) || !any_walking) {
-      if (q0 != 0u) leaf_test<LDS, false>(im, sc, off, q0 >> 3, q0 & 7u, ray, best, nprim, last_id);
-      q0 = q1;
-      q1 = q2;
-      q2 = q3;
-      q3 = 0u;
-      if (best.prim >= 0) {  // occluded: this lane is finished (the wave keeps voting)
-        node = END;
-        q0 = q1 = q2 = 0u;
-      }
-      if (!__any(node < END) && !__any(q0 != 0u)) break;
-    }
+// ---- the any-hit sink of the bounded walks (rtow_bounded_walks.h) ----
+// A whole leaf, cell or list per call, against one Closest seeded with tmax.  The culling bound stays tmax: the walk ends
+// at the lane's first hit, so a smaller one could never be observed.  One mailbox for the whole walk.
+struct AnyHitSink {
+  static constexpr bool kFold = true;
+  Closest best;
+  float tmax32;
+  int last_id;
+  __device__ __forceinline__ void seed(double tmax) {
+    best = seeded(tmax);
+    tmax32 = round_up_f32(best.t);
+    last_id = -1;
   }
-  return best.prim >= 0;
-}
-
-// ---- GRID: the 3D-DDA of closest_hit_grid (rtow_trace_grid.h) without its suspend / resume, seeded, early exit ----
-// The DDA's step direction is taken from the sign of the reciprocal it steps with (1 / -0.0 is negative), not from
-// `d >= 0` as the render's walk does: the two disagree for a -0.0 component, which made that walk step the wrong way
-// (rtow_query.h hands it +0.0 instead; here the walk is consistent by construction and takes the caller's direction).
-template <bool LDS>
-__device__ __forceinline__ bool any_hit_grid(const Image<LDS> &im, const DevScene &sc, V3 o, V3 d, real time,
-                                             double tmax, bool active, uint32_t &nnode, uint32_t &nprim,
-                                             uint32_t leaf_votes) {
-#ifdef RTOW_UNIT_RAYS
-  // the fast build walks the unit direction (rtow_trace_bvh.h, RTOW_UNIT_RAYS): its ray parameter is a distance, and so
-  // is the bound it starts from
-  const double a_ref = dot(d, d);
-  const double inv_len = fast_rsqrt(a_ref), len = a_ref * inv_len;
-  d = d * inv_len;
-  const RayForms ray = make_unit_ray_forms(o, d, time, len);
-  const float tmin32w = 0.0009f * (float)len;
-  Closest best = seeded(tmax * len);
-#else
-  const RayForms ray = make_ray_forms(o, d, time);
-  const float tmin32w = 0.0009f;
-  Closest best = seeded(tmax);
-#endif
-  ImgOffsets off = {sc.g_off_ids, sc.g_off_sph, sc.g_off_mov, sc.g_off_tri, 0u, 0u, sc.g_off_sph32, sc.g_off_mov32};
-  int last_id = -1;
-  const RTOW_CONST float *hf = (const RTOW_CONST float *)sc.gblob;
-  const RTOW_CONST int32_t *hi = (const RTOW_CONST int32_t *)sc.gblob;
-  const float gx = hf[0], gy = hf[1], gz = hf[2];
-  const float cx = hf[3], cy = hf[4], cz = hf[5];
-  const float icx = hf[6], icy = hf[7], icz = hf[8];
-  const int nx = hi[9], ny = hi[10], nz = hi[11];
-  const uint32_t n_large = (uint32_t)hi[12], off_large = (uint32_t)hi[13];
-  off.fat = (uint32_t)hi[14];
-  off.fat_stride = (uint32_t)hi[15];
-
-  // the large primitives (the ground sphere), for every ray, as closest_hit_grid tests them (static spheres four, then
-  // two at a time); a hit among them ends the lane before the DDA
-  if (active && n_large != 0u) {
-    const uint32_t lf = (off_large - off.ids) >> 2;
+  __device__ __forceinline__ float bound32() const { return tmax32; }
+  __device__ __forceinline__ bool done() const { return best.prim >= 0; }  // occluded: this lane is finished
+  template <bool LDS, bool CELL>
+  __device__ __forceinline__ void list(const Image<LDS> &im, const DevScene &sc, const ImgOffsets &off, uint32_t first,
+                                       uint32_t count, const RayForms &ray, uint32_t &nprim) {
+    leaf_test<LDS, CELL>(im, sc, off, first, count, ray, best, nprim, last_id);
+  }
+  // as closest_hit_grid tests them (static spheres four, then two at a time: all records loaded and all discriminants
+  // computed before any hit branch).  A copy of that walk's block: lifting it into a function both call changed the
+  // render kernels' code objects, and those stay as they are.
+  template <bool LDS>
+  __device__ __forceinline__ void large(const Image<LDS> &im, const DevScene &sc, const ImgOffsets &off, uint32_t lf,
+                                        uint32_t n_large, const RayForms &ray, uint32_t &nprim) {
     uint32_t k = 0;
     for (; k + 3 < n_large; k += 4) {
       int id[4];
@@ -192,112 +117,35 @@ __device__ __forceinline__ bool any_hit_grid(const Image<LDS> &im, const DevScen
     }
     if (k < n_large) leaf_test<LDS, false, 0, true>(im, sc, off, lf + k, n_large - k, ray, best, nprim, last_id);
   }
-  const float tmax32 = round_up_f32(best.t);
-  stage_prio<kPrioSetup>();
-
-  const float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;
-  const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
-  const float ix = safe_inv(dx), iy = safe_inv(dy), iz = safe_inv(dz);
-  const float oix = ox * ix, oiy = oy * iy, oiz = oz * iz;
-  const float hx = fmaf((float)nx, cx, gx), hy = fmaf((float)ny, cy, gy), hz = fmaf((float)nz, cz, gz);
-  const float ax = fmaf(gx, ix, -oix), bx = fmaf(hx, ix, -oix);
-  const float ay = fmaf(gy, iy, -oiy), by = fmaf(hy, iy, -oiy);
-  const float az = fmaf(gz, iz, -oiz), bz = fmaf(hz, iz, -oiz);
-  const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tmin32w));
-  const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tmax32));
-  bool walking = active && best.prim < 0 && t0 <= t1 * 1.00002f;
-
-  const float px = fmaf(t0, dx, ox), py = fmaf(t0, dy, oy), pz = fmaf(t0, dz, oz);
-  int c0 = (int)floorf((px - gx) * icx), c1 = (int)floorf((py - gy) * icy), c2 = (int)floorf((pz - gz) * icz);
-  c0 = min(max(c0, 0), nx - 1);
-  c1 = min(max(c1, 0), ny - 1);
-  c2 = min(max(c2, 0), nz - 1);
-  const bool fx = !(ix < 0.0f), fy = !(iy < 0.0f), fz = !(iz < 0.0f);  // (see above: the sign of the reciprocal)
-  float tmx = fmaf(fmaf((float)(c0 + (fx ? 1 : 0)), cx, gx), ix, -oix);
-  float tmy = fmaf(fmaf((float)(c1 + (fy ? 1 : 0)), cy, gy), iy, -oiy);
-  float tmz = fmaf(fmaf((float)(c2 + (fz ? 1 : 0)), cz, gz), iz, -oiz);
-  const float tdx = fabsf(cx * ix), tdy = fabsf(cy * iy), tdz = fabsf(cz * iz);
-  int remx = fx ? nx - 1 - c0 : c0, remy = fy ? ny - 1 - c1 : c1, remz = fz ? nz - 1 - c2 : c2;
-  const int incx = fx ? 1 : -1, incy = fy ? nx : -nx, incz = fz ? nx * ny : -(nx * ny);
-  int idx = (c2 * ny + c1) * nx + c0;
-
-  stage_prio<kPrioStage>();
-  uint32_t q0 = 0u, q1 = 0u;
-  for (;;) {
-    if (walking && q1 == 0u) {  // (a lane with two cells queued waits for the next leaf phase)
-      const uint32_t cw = im.u32(sc.g_off_cells + 4u * (uint32_t)idx);
-      ++nnode;
-      if (cw != 0u) {
-        if (q0 == 0u)
-          q0 = cw;
-        else
-          q1 = cw;
-      }
-      const float tnext = fminf(fminf(tmx, tmy), tmz);
-      const bool sx = tmx == tnext;
-      const bool sy = !sx && tmy == tnext;
-      const int rem = sx ? remx : (sy ? remy : remz);
-      walking = rem > 0 && !(tnext > tmax32);
-      idx += sx ? incx : (sy ? incy : incz);
-      tmx += sx ? tdx : 0.0f;
-      tmy += sy ? tdy : 0.0f;
-      tmz += (!sx && !sy) ? tdz : 0.0f;
-      remx -= sx ? 1 : 0;
-      remy -= sy ? 1 : 0;
-      remz -= (!sx && !sy) ? 1 : 0;
-    }
-    const bool any_walking = __any(walking);
-    const unsigned long long m_pending = __ballot(q0 != 0u);
-    if ((m_pending != 0ull && ((uint32_t)__popcll(m_pending) >= leaf_votes || __ballot(walking && q1 == 0u) == 0ull)) ||
-        !any_walking) {
-      stage_prio<kPrioLeaf>();
-      if (q0 != 0u) leaf_test<LDS, true>(im, sc, off, q0 >> 8, q0 & 255u, ray, best, nprim, last_id);
-      q0 = q1;
-      q1 = 0u;
-      if (best.prim >= 0) {  // occluded: the lane's DDA stops here
-        walking = false;
-        q0 = 0u;
-      }
-      stage_prio<kPrioStage>();
-      if (!__any(walking) && !__any(q0 != 0u)) break;
-    }
+  template <bool FULL>
+  __device__ __forceinline__ void leaf4(const Bvh4Reader<FULL> &im, const DevScene &sc, uint32_t leaf, V3d o64, V3d d64,
+                                        uint32_t &nprim) {
+    bvh4_leaf<FULL>(im, sc, leaf, o64, d64, best, nprim);
   }
-  return best.prim >= 0;
-}
+};
 
-// ---- BVH4: the trip loop of closest_hit_bvh4 (rtow_trace_bvh4.h) without its suspend / resume, seeded, early exit ----
+template <bool LDS>
+__device__ __forceinline__ bool any_hit_bvh(const Image<LDS> &im, const DevScene &sc, V3 o, V3 d, real time, double tmax,
+                                            bool active, uint32_t &nnode, uint32_t &nprim) {
+  AnyHitSink sink;
+  bounded_walk_bvh<LDS>(im, sc, o, d, time, tmax, active, sink, nnode, nprim);
+  return sink.done();
+}
+template <bool LDS>
+__device__ __forceinline__ bool any_hit_grid(const Image<LDS> &im, const DevScene &sc, V3 o, V3 d, real time,
+                                             double tmax, bool active, uint32_t &nnode, uint32_t &nprim,
+                                             uint32_t leaf_votes) {
+  AnyHitSink sink;
+  bounded_walk_grid<LDS>(im, sc, o, d, time, tmax, active, sink, nnode, nprim, leaf_votes);
+  return sink.done();
+}
 template <bool FULL>
 __device__ __forceinline__ bool any_hit_bvh4(const Bvh4Reader<FULL> &im, const DevScene &sc, const TraceParams &P, V3 o,
                                              V3 d, double tmax, bool active, uint32_t lane_g, uint32_t &nnode,
                                              uint32_t &nprim) {
-  Closest best = seeded(tmax);
-  const V3d o64 = to_f64(o), d64 = to_f64(d);
-  const Bvh4Ray ray = bvh4_ray<FULL>(sc, o, d);
-  const Bvh4Stack st = bvh4_stack(sc);
-  const float tmax32 = round_up_f32(best.t);  // the bound: fixed, the walk ends at the first hit
-  uint32_t sa = st.lds;
-  uint32_t cur = active ? 0u : kRefNone;  // node 0 = root
-  uint32_t q0 = kRefNone, q1 = kRefNone;  // queued leaves, oldest first
-  if constexpr (FULL) stage_prio<kPrioLeaf>();
-  for (;;) {
-    bvh4_step<FULL>(im, P, ray, tmax32, st, lane_g, cur, sa, q0, q1, nnode);
-    const bool any_walking = __any(cur != kRefNone);
-    const unsigned long long m_pending = __ballot(q0 != kRefNone);
-    if ((m_pending != 0ull && ((uint32_t)__popcll(m_pending) >= P.leaf_votes || __ballot(bvh4_busy(cur, q1)) == 0ull)) ||
-        !any_walking) {
-      if (q0 != kRefNone) bvh4_leaf<FULL>(im, sc, q0, o64, d64, best, nprim);
-      q0 = q1;
-      q1 = kRefNone;
-      if (best.prim >= 0) {  // occluded: drop the node in hand, the queued leaf and the stack
-        cur = kRefNone;
-        q0 = kRefNone;
-        sa = st.lds;
-      }
-      if (!__any(cur != kRefNone) && !__any(q0 != kRefNone)) break;
-    }
-  }
-  if constexpr (FULL) stage_prio<kPrioStage>();
-  return best.prim >= 0;
+  AnyHitSink sink;
+  bounded_walk_bvh4<FULL>(im, sc, P, o, d, tmax, active, lane_g, sink, nnode, nprim);
+  return sink.done();
 }
 
 // ---- STREAM: closest_hit_stream (rtow_trace_hit.h), seeded; the wave leaves when every active lane has a hit ----
@@ -435,14 +283,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     V3 ro = {0, 0, 0}, rd = {0, 0, 1};
     real rtime = 0;
     double tmax = 0.0;
-    if (in) {
-      const vd2 *r = reinterpret_cast<const vd2 *>(Q.rays + (size_t)i * kRayBytes);
-      const vd2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];  // {ox, oy} {oz, time} {dx, dy} {dz, tmax}
-      ro = {r0.x, r0.y, r1.x};
-      rtime = r1.y;
-      rd = {r2.x, r2.y, r3.x};
-      tmax = r3.y;
-    }
+    if (in) load_ray(Q.rays, i, ro, rd, rtime, tmax);
     // a ray whose interval [0.001, tmax] is empty (tmax NaN included) hits nothing: it skips the walk
     const bool active = in && tmax >= RTOW_TMIN;
 
@@ -467,12 +308,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     if (in) Q.occluded[i] = hit ? 1u : 0u;
   }
 
-  // statistics: one atomic per wave and counter
-  const unsigned long long c0 = wave_sum(nprim), c1 = wave_sum(nnode);
-  if (lane == 0) {
-    atomicAdd(&Q.counters[0], c0);
-    atomicAdd(&Q.counters[1], c1);
-  }
+  flush_counters(Q.counters, nprim, nnode);
 }
 
 }  // namespace

@@ -507,12 +507,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_PCAT(rtow_point
     }
   }
 
-  // statistics: one atomic per wave and counter
-  const unsigned long long c0 = wave_sum(nprim), c1 = wave_sum(nnode);
-  if (lane == 0) {
-    atomicAdd(&Q.counters[0], c0);
-    atomicAdd(&Q.counters[1], c1);
-  }
+  flush_counters(Q.counters, nprim, nnode);
 }
 
 }  // namespace

@@ -232,11 +232,8 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     const bool do_regen = !done && need_sample;
     const bool do_scat = !done && pending_hit;
     if (do_regen) {
-      const vd2 *r = reinterpret_cast<const vd2 *>(Q.rays + (size_t)item * kRayBytes);
-      const vd2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];  // {ox, oy} {oz, time} {dx, dy} {dz, tmax}: tmax is not read
-      ro = {r0.x, r0.y, r1.x};
-      rtime = r1.y;
-      rd = {r2.x, r2.y, r3.x};
+      [[maybe_unused]] double tmax;  // (not read: a radiance ray is unbounded)
+      load_ray(Q.rays, item, ro, rd, rtime, tmax);
       depth = P.max_child_rays;
       nb = 0;
 #ifdef RTOW_FAST_MATH
@@ -429,13 +426,9 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     }
   }
 
-  // statistics: one atomic per wave and counter
-  const unsigned long long c0 = wave_sum(nprim), c1 = wave_sum(nnode), c2 = wave_sum(nseg);
-  if (lane == 0) {
-    atomicAdd(&Q.counters[0], c0);
-    atomicAdd(&Q.counters[1], c1);
-    atomicAdd(&Q.counters[2], c2);
-  }
+  flush_counters(Q.counters, nprim, nnode);
+  const unsigned long long c2 = wave_sum(nseg);  // the path segments: this kernel's own third counter
+  if (lane == 0) atomicAdd(&Q.counters[2], c2);
 }
 
 }  // namespace
