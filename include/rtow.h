@@ -451,7 +451,11 @@ int rtow_occluded(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_r
  *                               rounding band of rtow_intersect_device — t against tmax and the gaps between consecutive
  *                               hits up to the first one left out included — the sequence is the exact one; on any
  *                               other ray it is one the band allows.  An exactly tangent ray misses that sphere; GRID's
- *                               triangle cut is det >= 1e-6 |d|;
+ *                               triangle cut is det >= 1e-6 |d|.  Reported t is non-decreasing under every walk, and
+ *                               bit-equal t come in insertion order under BRUTE, BVH and BVH4.  GRID orders by the
+ *                               distance t |d| (insertion index on equal distances) and converts at output, where two
+ *                               distances may round to one t: under GRID the order of entries with bit-equal t is not
+ *                               guaranteed (observed on coplanar overlapping triangles);
  *              RTOW_F32:        refused (RTOW_EINVAL).
  *   kernel     AUTO, fallbacks, residency rules (RTOW_ENOSCENE after a lean upload) and kernel_used as in
  *              rtow_intersect_device.  RTOW_KERNEL_REFTREE: RTOW_EINVAL (the reference's tree misses hits by design and

@@ -688,6 +688,24 @@ def unit_mesh(n, seed):
     return c + rng.uniform(-0.05, 0.05, size=(n, 3, 3))
 
 
+def sheet_stack(layers, m, seed):
+    """[layers * 2 m^2][3][3]: wavy sheets z = 0.1 k + 0.03 sin(5 x + phi_k) cos(4 y + psi_k), k = 0 .. layers - 1, over
+    the unit square, each an m x m grid of two triangles per cell wound so n_z < 0: a ray along +z meets the front of
+    every sheet, one hit per sheet (deep first-k-hits sequences)."""
+    rng = np.random.default_rng(seed)
+    g = np.linspace(0.0, 1.0, m + 1)
+    x, y = np.meshgrid(g, g, indexing="ij")
+    out = []
+    for k in range(layers):
+        phi, psi = rng.uniform(0, 2 * np.pi, 2)
+        v = np.stack([x, y, 0.1 * k + 0.03 * np.sin(5 * x + phi) * np.cos(4 * y + psi)], axis=-1)
+        p00, p10, p01, p11 = v[:-1, :-1], v[1:, :-1], v[:-1, 1:], v[1:, 1:]
+        # (B - A) x (C - A) along -z: A, then the +y neighbour, then the +x neighbour
+        out.append(np.stack([p00, p01, p10], axis=-2).reshape(-1, 3, 3))
+        out.append(np.stack([p11, p10, p01], axis=-2).reshape(-1, 3, 3))
+    return np.concatenate(out)
+
+
 def edge_meshes():
     """name -> [n][3][3]: the shapes where builders and emitters go wrong."""
     rng = np.random.default_rng(7)

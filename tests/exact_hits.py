@@ -67,6 +67,29 @@ The fast build's GRID walk applies the triangle cut to the UNIT direction: det /
 d / |d|; the triangle test is the render's).  For |d| = 1 the two agree; the reference is told which one a walk uses
 (`unit_cut`).
 
+First-k-hits sequences (rtow_first_hits; sequence_decided, check_sequences).  The exact answer is every primitive whose
+test accepts a t in [tmin, tmax], ascending by (t, insertion index), cut at k.  Per ray, with H its HIT candidates
+(decided hits) sorted by exact t and the UND candidates beside them:
+  * decided at k: every gap between consecutive members of H up to and including the one between entry k - 1 and the
+    first one left out is clear, t[j+1] - E[j+1] > t[j] + E[j] (so no kernel can order or cut them otherwise), and no UND
+    candidate has an outcome with t - E at or before t[k-1] + E[k-1]; with fewer than k decided hits any UND candidate
+    makes the ray undecided.  tmax is one of every candidate's decisions already (|t - tmax| > E_t), and the bound of a
+    full list is the computed t of entry k - 1: within E[k-1] of t[k-1], so what the clear gap separates from it stays
+    out and what lies in front of it stays in.  On a decided ray the primitive sequence is H cut at k and the count is
+    min(|H|, k) (members of an exact tie, equal exact t, in either order: a tie is never clear, so this can only matter
+    to a caller that passes its own notion of decided).
+  * every ray, decided or not (what the band allows): 0 <= count <= k, slots >= count the miss record, slots < count
+    distinct primitives; every reported primitive is a candidate of the ray (it may hit within tmax) and its record
+    has t within E of one of that candidate's outcomes with that outcome's front_face — for a decided hit also the
+    point, the triangle normal and the sphere normal of the closest-hit rules; reported t is non-decreasing, and
+    bit-equal consecutive t come in ascending insertion index (not required of the fast GRID walk, which sorts
+    distances t |d| and converts them at output: two distances that differ may round to one t); a decided hit that
+    is not reported requires count == k and t + E >= t_reported[k-1] - E(the candidate reported there): it may be
+    missing only from behind the cut.
+  * the band is TAU as for the other queries: the fast GRID walk's second fast_rsqrt at output repeats the walk's own
+    (the same operands, the same instruction sequence: the same bits), so distance * inv_len at output inverts the
+    direction's scaling with the one rounding the closest-hit walk spends there (d * inv_len: 1, in the count above).
+
 Speed.  A vectorised binary64 filter runs over every (ray, primitive) pair first, with the forward error bound
 GF * S_q, GF = 32 u (the filter's own expressions are at most 10 roundings deep): a pair all of whose decisions are
 beyond (tau + GF) S_q is decided there.  The few others go to the exact path (fractions.Fraction).  Large meshes take a
@@ -780,6 +803,76 @@ def _sphere_of(scene, prim, time):
     return [c0[k] + tm * (c1[k] - c0[k]) for k in range(3)], g[6], float(np.max(np.abs(g[:3]) + np.abs(time * (g[3:6] - g[:3]))))
 
 
+# -- the per-record checks, shared by check (closest hit) and check_sequences (first k hits) --
+def _is_miss_record(h):
+    """The miss-record layout: t = inf, kind = material = -1, front_face = 0."""
+    return bool(math.isinf(h["t"]) and h["kind"] == -1 and h["material"] == -1 and h["front_face"] == 0)
+
+
+def _scene_fields_ok(sc, h):
+    """prim within the scene, kind and material the scene's."""
+    gp = int(h["prim"])
+    return bool(0 <= gp < len(sc.kind) and h["kind"] == sc.kind[gp] and h["material"] == sc.prim_mat[gp])
+
+
+def _explained(h, mine):
+    """t within E of an outcome of one of the candidates `mine`, with that outcome's front_face (t NaN: any)."""
+    t = float(h["t"])
+    for c in mine:
+        for (te, E, fr) in c.outs:
+            if math.isnan(te) or (abs(t - te) <= E and int(h["front_face"]) == fr):
+                return True
+    return False
+
+
+def _check_exact_record(sc, rays, i, h, te, E, front, fail):
+    """A record that must be the exact hit (te, front) of ray i on primitive h.prim: t within E, front_face, the point
+    bound, a triangle's normal bit for bit, the sphere-normal bound.  Returns |t - te| / E."""
+    gp = int(h["prim"])
+    t = float(h["t"])
+    o, d = rays["origin"][i].astype(np.float64), rays["direction"][i].astype(np.float64)
+    err = abs(t - te) / E if E > 0 else (0.0 if t == te else math.inf)
+    if not err <= 1.0:
+        fail(i, f"t {t!r}, exact {te!r} +- {E:.3g}")
+    if int(h["front_face"]) != int(front):
+        fail(i, f"front_face {h['front_face']}, exact {front}")
+    pe = o + te * d
+    pb = np.abs(d) * E + 4 * U * (np.abs(o) + np.abs(te * d)) + 1e-300
+    if not np.all(np.abs(h["point"] - pe) <= pb):
+        fail(i, f"point {h['point']}, exact {pe} +- {pb}")
+    if sc.kind[gp] == TRIANGLE:
+        if not np.array_equal(np.asarray(h["normal"]).view(np.uint64), sc.tri_n[sc.index[gp]].view(np.uint64)):
+            fail(i, f"triangle normal {h['normal']}, record {sc.tri_n[sc.index[gp]]}")
+    else:
+        cf, r, cm = _sphere_of_f(sc, gp, float(rays["time"][i]))
+        nb = 2 * math.sqrt(3) * (float(np.max(pb)) + 4 * U * cm) / abs(r) + 8 * U
+        # in binary64 first: (o + te d - c) / |r| there is within (4 u (|o_i| + |te d_i|) + 5 u cm) / |r| of the exact
+        # quotient (pe 2 roundings, the moving centre 3, the difference and the quotient 1 each), less than nb / 2 — so a
+        # normal within nb / 2 of it is within nb of the exact one and needs no exact arithmetic
+        nf = (pe - cf) / abs(r)
+        if np.all(np.abs(h["normal"] - (nf if h["front_face"] else -nf)) <= 0.5 * nb):
+            return err
+        c, r, cm = _sphere_of(sc, gp, float(rays["time"][i]))
+        ng = [(Fr(float(o[k])) + Fr(te) * Fr(float(d[k])) - c[k]) / abs(Fr(float(r))) for k in range(3)]
+        ng = np.array([float(x) for x in ng])
+        ne = ng if h["front_face"] else -ng
+        nb = 2 * math.sqrt(3) * (float(np.max(pb)) + 4 * U * cm) / abs(r) + 8 * U
+        if not np.all(np.abs(h["normal"] - ne) <= nb):
+            fail(i, f"sphere normal {h['normal']}, exact {ne} +- {nb:.3g}")
+    return err
+
+
+def _sphere_of_f(scene, prim, time):
+    """_sphere_of in binary64: (centre, r, the magnitude of the centre's terms)."""
+    k, i = int(scene.kind[prim]), int(scene.index[prim])
+    if k == SPHERE:
+        g = scene.sph[i]
+        return g[:3], g[3], float(np.max(np.abs(g[:3])))
+    g = scene.mov[i]
+    dc = time * (g[3:6] - g[:3])
+    return g[:3] + dc, g[6], float(np.max(np.abs(g[:3]) + np.abs(dc)))
+
+
 def check(ref, hits, occ=None, what=""):
     """Every field of `hits` (HIT_DTYPE) and `occ` (bool, optional) against the reference.  Returns the counts; raises
     CheckError with the first failures."""
@@ -794,7 +887,6 @@ def check(ref, hits, occ=None, what=""):
 
     for i in range(len(rays)):
         h = hits[i]
-        o, d = rays["origin"][i].astype(np.float64), rays["direction"][i].astype(np.float64)
         gp = int(h["prim"])
         if occ is not None and ref.occ_decided[i] and bool(occ[i]) != bool(ref.occ[i]):
             fail(i, f"occluded {bool(occ[i])}, exact {bool(ref.occ[i])}")
@@ -804,14 +896,14 @@ def check(ref, hits, occ=None, what=""):
             if not occ[i] and any(c.status == HIT for c in ref.cands[i]):
                 fail(i, "not occluded with a decided hit")
         if gp < 0:
-            if not (math.isinf(h["t"]) and h["kind"] == -1 and h["material"] == -1 and h["front_face"] == 0):
+            if not _is_miss_record(h):
                 fail(i, f"miss record {h}")
             if ref.decided[i] and ref.ties[i]:
                 fail(i, f"miss, exact hit {ref.ties[i]} at {ref.t[i]!r}")
             elif not ref.decided[i] and any(c.status == HIT for c in ref.cands[i]):
                 fail(i, "miss with a decided hit")
             continue
-        if gp >= len(sc.kind) or h["kind"] != sc.kind[gp] or h["material"] != sc.prim_mat[gp]:
+        if not _scene_fields_ok(sc, h):
             fail(i, f"prim {gp}: kind {h['kind']} material {h['material']}")
             continue
         t = float(h["t"])
@@ -819,41 +911,15 @@ def check(ref, hits, occ=None, what=""):
             if gp not in ref.ties[i]:
                 fail(i, f"prim {gp} t {t!r}, exact {ref.ties[i]} at {ref.t[i]!r}")
                 continue
-            te, E = ref.t[i], ref.E[i]
-            if t != te:
+            if t != ref.t[i]:
                 diff += 1
-            err = abs(t - te) / E if E > 0 else (0.0 if t == te else math.inf)
-            worst = max(worst, err)
-            if not err <= 1.0:
-                fail(i, f"t {t!r}, exact {te!r} +- {E:.3g}")
-            if int(h["front_face"]) != int(ref.front[i]):
-                fail(i, f"front_face {h['front_face']}, exact {ref.front[i]}")
-            pe = o + te * d
-            pb = np.abs(d) * E + 4 * U * (np.abs(o) + np.abs(te * d)) + 1e-300
-            if not np.all(np.abs(h["point"] - pe) <= pb):
-                fail(i, f"point {h['point']}, exact {pe} +- {pb}")
-            if sc.kind[gp] == TRIANGLE:
-                if not np.array_equal(np.asarray(h["normal"]).view(np.uint64), sc.tri_n[sc.index[gp]].view(np.uint64)):
-                    fail(i, f"triangle normal {h['normal']}, record {sc.tri_n[sc.index[gp]]}")
-            else:
-                c, r, cm = _sphere_of(sc, gp, float(rays["time"][i]))
-                ng = [(Fr(float(o[k])) + Fr(te) * Fr(float(d[k])) - c[k]) / abs(Fr(float(r))) for k in range(3)]
-                ng = np.array([float(x) for x in ng])
-                ne = ng if h["front_face"] else -ng
-                nb = 2 * math.sqrt(3) * (float(np.max(pb)) + 4 * U * cm) / abs(r) + 8 * U
-                if not np.all(np.abs(h["normal"] - ne) <= nb):
-                    fail(i, f"sphere normal {h['normal']}, exact {ne} +- {nb:.3g}")
+            worst = max(worst, _check_exact_record(sc, rays, i, h, ref.t[i], ref.E[i], ref.front[i], fail))
         else:
             mine = [c for c in ref.cands[i] if c.prim == gp]
             if not mine:
                 fail(i, f"undecided: prim {gp} cannot hit")
                 continue
-            ok = False
-            for c in mine:
-                for (te, E, fr) in c.outs:
-                    if math.isnan(te) or (abs(t - te) <= E and int(h["front_face"]) == fr):
-                        ok = True
-            if not ok:
+            if not _explained(h, mine):
                 fail(i, f"undecided: prim {gp} t {t!r} front {h['front_face']}, outcomes {mine[0].outs}")
             for c in ref.cands[i]:
                 if c.status == HIT and c.prim != gp and c.t + c.E < t - max(c.E for c in mine):
@@ -863,6 +929,134 @@ def check(ref, hits, occ=None, what=""):
     stats = {"rays": n, "decided": int(ref.decided.sum()), "undecided": int(n - ref.decided.sum()),
              "occ_undecided": int(n - ref.occ_decided.sum()), "t_differs": diff, "worst_t_err": worst,
              "exact_pairs": ref.n_exact}
+    if bad:
+        raise CheckError(f"{what}: {len(bad)}+ failures: {bad}")
+    return stats
+
+
+# ---- first-k-hits sequences ---------------------------------------------------------------------------------------------
+def _decided_hits(cs):
+    """The HIT candidates of one ray, ascending by exact t (a stable sort: equal t in insertion order)."""
+    return sorted((c for c in cs if c.status == HIT), key=lambda c: (c.t, c.prim))
+
+
+def _sequence_decided(cs, k):
+    H = _decided_hits(cs)
+    und = [c for c in cs if c.status == UND]
+    for j in range(min(len(H) - 1, k)):  # gaps j | j + 1, up to the one between entry k - 1 and the first one left out
+        if not (H[j + 1].t - H[j + 1].E > H[j].t + H[j].E):
+            return False
+    if len(H) < k:
+        return not und
+    last = H[k - 1]
+    for c in und:
+        for (t, E, _) in c.outs:
+            if not (t - E > last.t + last.E):  # (NaN: any t)
+                return False
+    return True
+
+
+def sequence_decided(ref, k):
+    """Per ray: the first-k-hits sequence is certain (the header's sequence rules)."""
+    return np.array([_sequence_decided(cs, k) for cs in ref.cands], dtype=bool).reshape(len(ref.cands))
+
+
+def check_sequences(ref, hits, counts, k, what="", sorted_by_index=True):
+    """`hits` [n, k] (HIT_DTYPE) and `counts` [n] of a first-k-hits query against the reference (built with the rays'
+    own tmax): shape, soundness, order, completeness, and the exact sequence on decided rays (the header's sequence
+    rules).  sorted_by_index=False drops only the index order of bit-equal t (the fast GRID walk).  Returns the counts;
+    raises CheckError with the first failures."""
+    sc, rays = ref.scene, ref.rays
+    n = len(rays)
+    assert hits.shape == (n, k) and len(counts) == n, (hits.shape, len(counts), n, k)
+    bad = []
+    worst = 0.0
+    unordered = 0
+    n_decided = 0
+    cols = {f: np.ascontiguousarray(hits[f]) for f in ("t", "point", "normal", "prim", "kind", "material", "front_face")}
+
+    def rec(i, s):  # (slot s of ray i as a mapping: plain arrays index faster than structured ones)
+        return {f: a[i, s] for f, a in cols.items()}
+
+    def fail(i, msg):
+        if len(bad) < 8:
+            bad.append((int(i), msg))
+
+    for i in range(n):
+        cs = ref.cands[i]
+        decided = _sequence_decided(cs, k)
+        n_decided += decided
+        cnt = int(counts[i])
+        # shape
+        if not 0 <= cnt <= k:
+            fail(i, f"count {cnt} outside [0, {k}]")
+            continue
+        for s in range(cnt, k):
+            if cols["prim"][i, s] >= 0 or not _is_miss_record(rec(i, s)):
+                fail(i, f"slot {s} >= count {cnt} is no miss record: {hits[i, s]}")
+        prims = [int(cols["prim"][i, s]) for s in range(cnt)]
+        if any(p < 0 for p in prims):
+            fail(i, f"a miss record below count {cnt}: prims {prims}")
+            continue
+        if len(set(prims)) != cnt:
+            fail(i, f"a primitive reported twice: {prims}")
+        # soundness
+        by_prim = {}
+        for c in cs:
+            by_prim.setdefault(c.prim, []).append(c)
+        ok = True
+        for s, gp in enumerate(prims):
+            h = rec(i, s)
+            if not _scene_fields_ok(sc, h):
+                fail(i, f"slot {s} prim {gp}: kind {h['kind']} material {h['material']}")
+                ok = False
+                continue
+            mine = by_prim.get(gp)
+            if not mine:
+                fail(i, f"slot {s}: prim {gp} t {float(h['t'])!r} cannot hit within tmax {float(rays['tmax'][i])!r}")
+                ok = False
+                continue
+            if not _explained(h, mine):
+                fail(i, f"slot {s}: prim {gp} t {float(h['t'])!r} front {h['front_face']}, outcomes {mine[0].outs}")
+            for c in mine:
+                if c.status == HIT:
+                    worst = max(worst, _check_exact_record(sc, rays, i, h, c.t, c.E, c.front, fail))
+        if not ok:
+            continue
+        # order
+        ts = [float(cols["t"][i, s]) for s in range(cnt)]
+        for s in range(cnt - 1):
+            if not ts[s] <= ts[s + 1]:
+                fail(i, f"t descends at slot {s}: {ts[s]!r} > {ts[s + 1]!r}")
+            elif ts[s] == ts[s + 1] and prims[s] > prims[s + 1]:
+                unordered += 1
+                if sorted_by_index:
+                    fail(i, f"equal t {ts[s]!r} at slots {s}, {s + 1} out of index order: {prims[s]}, {prims[s + 1]}")
+        # completeness: a decided hit may be missing only from behind the cut
+        H = _decided_hits(cs)
+        got = set(prims)
+        for c in H:
+            if c.prim in got:
+                continue
+            if cnt < k:
+                fail(i, f"decided hit prim {c.prim} at {c.t!r} missing, count {cnt} < {k}")
+                break
+            e_last = max(x.E for x in by_prim[prims[k - 1]])
+            if not c.t + c.E >= ts[k - 1] - e_last:
+                fail(i, f"decided hit prim {c.prim} at {c.t!r} missing in front of the last entry at {ts[k - 1]!r}")
+                break
+        # decided rays: the exact sequence (members of an exact tie in either order)
+        if decided:
+            want = H[:k]
+            if cnt != len(want):
+                fail(i, f"decided: count {cnt}, exact {len(want)}")
+            elif prims != [c.prim for c in want]:
+                tex = {c.prim: ref._tex(i, c) for c in want}
+                same = sorted(prims) == sorted(tex) and all(tex[p] == tex[c.prim] for p, c in zip(prims, want))
+                if not same:
+                    fail(i, f"decided: prims {prims}, exact {[c.prim for c in want]}")
+    stats = {"rays": n, "decided": int(n_decided), "undecided": int(n - n_decided), "worst_t_err": worst,
+             "unordered_equal_t": unordered, "exact_pairs": ref.n_exact}
     if bad:
         raise CheckError(f"{what}: {len(bad)}+ failures: {bad}")
     return stats

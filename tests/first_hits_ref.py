@@ -303,3 +303,45 @@ def ties_rays(seed=19):
         o.append(g.uniform(-4, 4, 3) + [0, 2, -3]), d.append(g.normal(size=3))
     rays = rtow.make_rays(np.array(o), np.array(d), time=g.random(len(o)))
     return rays
+
+
+# ------------------------------------------------------------------------------- rays that meet many primitives ---
+def _scaled_segments(g, a, b):
+    """Rays from a toward b with |d| scaled by exp(U(-3, 3)), seeded times; half with tmax = inf, half with a uniform
+    fraction of 1.2 segment lengths in the ray's own parameter."""
+    n = len(a)
+    s = np.exp(g.uniform(-3, 3, size=(n, 1)))
+    tmax = np.where(g.random(n) < 0.5, math.inf, g.random(n) * 1.2 / s[:, 0])
+    return rtow.make_rays(a, (b - a) * s, time=g.random(n), tmax=tmax)
+
+
+def chord_rays(n, seed):
+    """Chords across the cover scenes' field of small spheres: both ends on the circle of radius 13 about the y axis at
+    heights 0.05 .. 0.4, the far end opposite the near one within +-1 rad."""
+    g = np.random.default_rng(seed)
+    phi = g.uniform(0, 2 * np.pi, n)
+    psi = phi + np.pi + g.uniform(-1, 1, n)
+    a = np.c_[13 * np.cos(phi), g.uniform(0.05, 0.4, n), 13 * np.sin(phi)]
+    b = np.c_[13 * np.cos(psi), g.uniform(0.05, 0.4, n), 13 * np.sin(psi)]
+    return _scaled_segments(g, a, b)
+
+
+def sheet_rays(n, seed):
+    """Through accel_images.sheet_stack: from z = -0.5 to z = 1.6 through seeded points of [0.05, 0.95]^2."""
+    g = np.random.default_rng(seed)
+    a = np.c_[g.uniform(0.05, 0.95, size=(n, 2)), np.full(n, -0.5)]
+    b = np.c_[g.uniform(0.05, 0.95, size=(n, 2)), np.full(n, 1.6)]
+    return _scaled_segments(g, a, b)
+
+
+def tmax_at_hits(rays, t, counts):
+    """The rays that hit something, each with tmax at one of its own hits: entry j = 0, 3 or 7 of `t` [n, 8] (the
+    deepest of these the ray has; j cycles over the rays) — its bits, the double below it or the double above it (cycling
+    too)."""
+    keep = np.flatnonzero(np.asarray(counts) > 0)
+    out = rays[keep].copy()
+    for m, i in enumerate(keep):
+        j = max(x for x in (0, 3, 7)[:m % 3 + 1] if x < counts[i])
+        v = float(t[i, j])
+        out["tmax"][m] = (v, np.nextafter(v, -math.inf), np.nextafter(v, math.inf))[(m // 3) % 3]
+    return out

@@ -190,12 +190,7 @@ def tangent_rays(centres, radii, times, seed):
     return rtow.make_rays(np.array(o), np.array(d), time=np.array(tm))
 
 
-def test_tangent_rays(qctx, logged):
-    """The ground sphere, the small spheres, a hollow sphere, moving spheres at several times (handmade scene and the
-    moving cover scene)."""
-    h = handmade_scene()
-    view = SceneView(h)
-    sc = ex.Scene.of(view)
+def handmade_tangent_rays(view):
     c, r, t = [], [], []
     for s in view.sph:
         for _ in range(6):
@@ -204,8 +199,10 @@ def test_tangent_rays(qctx, logged):
         for tm in (0.0, 0.25, 0.5, 1.0):
             for _ in range(3):
                 c.append(m[:3] + tm * (m[3:6] - m[:3])), r.append(m[6]), t.append(tm)
-    run_case(qctx, "tangent/handmade", h.c, sc, tangent_rays(c, r, t, 4))
-    hs, view, sc, log = logged["cover_moving"]
+    return tangent_rays(c, r, t, 4)
+
+
+def cover_tangent_rays(view):
     g = np.random.default_rng(6)
     c, r, t = [view.sph[0, :3]] * 4, [view.sph[0, 3]] * 4, [0.0] * 4
     for i in g.choice(len(view.sph), 40, replace=False):
@@ -214,12 +211,21 @@ def test_tangent_rays(qctx, logged):
         tm = float(g.choice([0.0, 0.5, 1.0, g.random()]))
         m = view.mov[i]
         c.append(m[:3] + tm * (m[3:6] - m[:3])), r.append(m[6]), t.append(tm)
-    run_case(qctx, "tangent/cover_moving", hs, sc, tangent_rays(c, r, t, 5))
+    return tangent_rays(c, r, t, 5)
+
+
+def test_tangent_rays(qctx, logged):
+    """The ground sphere, the small spheres, a hollow sphere, moving spheres at several times (handmade scene and the
+    moving cover scene)."""
+    h = handmade_scene()
+    view = SceneView(h)
+    run_case(qctx, "tangent/handmade", h.c, ex.Scene.of(view), handmade_tangent_rays(view))
+    hs, view, sc, log = logged["cover_moving"]
+    run_case(qctx, "tangent/cover_moving", hs, sc, cover_tangent_rays(view))
 
 
 # ---- the triangle cut, surfaces, direction magnitudes ------------------------------------------------------------------
-def test_rays_at_the_det_cut(qctx, logged):
-    hs, view, sc, log = logged["suzanne"]
+def det_cut_rays(view, sc):
     g = np.random.default_rng(8)
     o, d = [], []
     for k in g.choice(len(view.tri), 150, replace=False):
@@ -229,36 +235,48 @@ def test_rays_at_the_det_cut(qctx, logged):
         for delta in (-1e-3, -1e-9, -1e-12, 0.0, 1e-12, 1e-9, 1e-3):
             dd = -n / np.dot(n, n) * 1e-6 * (1 + delta)
             o.append(P - 100 * dd), d.append(dd)
-    run_case(qctx, "det_cut/suzanne", hs, sc, rtow.make_rays(np.array(o), np.array(d)))
+    return rtow.make_rays(np.array(o), np.array(d))
 
 
-@pytest.mark.parametrize("name", ["cover_moving", "suzanne"])
-def test_rays_from_surfaces(qctx, logged, name):
-    hs, view, sc, log = logged[name]
+def test_rays_at_the_det_cut(qctx, logged):
+    hs, view, sc, log = logged["suzanne"]
+    run_case(qctx, "det_cut/suzanne", hs, sc, det_cut_rays(view, sc))
+
+
+def surface_rays(log):
     hit = log[np.isfinite(log[:, 10])]
     hit = _sub(hit, 1500, 4)
     g = np.random.default_rng(10)
     p = hit[:, 3:6] + hit[:, 10:11] * hit[:, 6:9]
     d = g.normal(size=(len(hit), 3))
-    run_case(qctx, f"surfaces/{name}", hs, sc, rtow.make_rays(p, d, time=hit[:, 9]))
+    return rtow.make_rays(p, d, time=hit[:, 9])
 
 
 @pytest.mark.parametrize("name", ["cover_moving", "suzanne"])
-def test_direction_magnitudes(qctx, logged, name):
+def test_rays_from_surfaces(qctx, logged, name):
     hs, view, sc, log = logged[name]
+    run_case(qctx, f"surfaces/{name}", hs, sc, surface_rays(log))
+
+
+def magnitude_rays(log):
     parts = []
     for k, s in enumerate((1e-4, 1e-2, 1e2, 1e4)):
         r = rays_of(_sub(log, 800, 20 + k))
         r["direction"] *= s
         parts.append(r)
-    run_case(qctx, f"magnitudes/{name}", hs, sc, np.concatenate(parts))
+    return np.concatenate(parts)
+
+
+@pytest.mark.parametrize("name", ["cover_moving", "suzanne"])
+def test_direction_magnitudes(qctx, logged, name):
+    hs, view, sc, log = logged[name]
+    run_case(qctx, f"magnitudes/{name}", hs, sc, magnitude_rays(log))
 
 
 # ---- far scenes, refits ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("offset", [1e4, 1e5])
-@pytest.mark.parametrize("name", ["cover_static", "suzanne"])
-def test_far_scenes(qctx, logged, name, offset):
-    hs, view, sc0, log = logged[name]
+def far_case(hs, log, offset):
+    """(scene to upload, its exact_hits.Scene, rays, what keeps the upload's arrays alive): the scene and 3000 logged
+    rays moved by `offset` x (1, -0.5, 0.75)."""
     G = ai.Geometry.of_scene(hs.c)
     off = np.array([offset, -0.5 * offset, 0.75 * offset])
     H = deform(G, lambda p: p + off)
@@ -267,18 +285,31 @@ def test_far_scenes(qctx, logged, name, offset):
     sc = ex.Scene.class_major(H.sph, H.mov, H.tri, H.pmat)
     rays = rays_of(_sub(log, 3000, 5))
     rays["origin"] += off
+    return up, sc, rays, keep
+
+
+@pytest.mark.parametrize("offset", [1e4, 1e5])
+@pytest.mark.parametrize("name", ["cover_static", "suzanne"])
+def test_far_scenes(qctx, logged, name, offset):
+    hs, view, sc0, log = logged[name]
+    up, sc, rays, keep = far_case(hs, log, offset)
     run_case(qctx, f"far/{name}/{offset:g}", up, sc, rays)
 
 
-@pytest.mark.parametrize("motion", ["translate", "scale1000", "flatten"])
-@pytest.mark.parametrize("name", ["cover_moving", "mesh96k"])
-def test_after_refit(qctx, logged, big_mesh, name, motion):
-    hs = logged["cover_moving"][0] if name == "cover_moving" else big_mesh[0]
+def refit_case(hs, motion, n):
+    """(scene to upload, scene to refit over it, the refitted geometry's exact_hits.Scene, 3 n rays, keep-alive)."""
     G = ai.Geometry.of_scene(hs.c)
     keep = []
     base = scene_of(G, keep)
     H = motions(G)[motion][0]
     new = scene_of(H, keep)
     sc = ex.Scene.class_major(H.sph, H.mov, H.tri, H.pmat)
-    rays = rays_for(H, 1500 if name == "cover_moving" else 100, 7)
+    return base, new, sc, rays_for(H, n, 7), keep
+
+
+@pytest.mark.parametrize("motion", ["translate", "scale1000", "flatten"])
+@pytest.mark.parametrize("name", ["cover_moving", "mesh96k"])
+def test_after_refit(qctx, logged, big_mesh, name, motion):
+    hs = logged["cover_moving"][0] if name == "cover_moving" else big_mesh[0]
+    base, new, sc, rays, keep = refit_case(hs, motion, 1500 if name == "cover_moving" else 100)
     run_case(qctx, f"refit/{name}/{motion}", base, sc, rays, refit=new)
