@@ -498,6 +498,20 @@ int rtow_first_hits(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow
  *                               k term is absent for spheres), and that primitive's D is within the same bands of the
  *                               exact minimum.  The strict build meets the same bound with 32 u;
  *              RTOW_F32:        refused (RTOW_EINVAL).
+ *   point      the reported point q of the reported primitive, with tau = 32 u (strict), 64 u (fast):
+ *                on the surface: the exact distance from q to the record's exact surface is <= tau S_q, with S_q = |a|_1 +
+ *                  |e1|_1 + |e2|_1 for a triangle (q = (a + e1 s) + e2 t: at most 4 roundings per component on magnitudes
+ *                  that sum to S_q; edge parameters are clamped to [0, 1], and the plane candidate's s + t exceeds 1 by a
+ *                  few u, in the fast build by twice its reciprocal's 4e-15) and S_q = |c|_1 + R (|c0|_1 +
+ *                  |time (c1 - c0)|_1 + R when moving) for a sphere (the unit vector's 3 roundings, the root and the
+ *                  reciprocal, scaled by R and added to c);
+ *                consistent with dist: | |p - q| - dist | <= tau (S + S_q), S as above (dist comes from the residual
+ *                  w - e1 s and q from a + e1 s: they differ by their own roundings only).  At a sphere's centre
+ *                  q = c + (R, 0, 0) meets both.
+ *   overflow   when the exact squared distance exceeds the binary64 range (|p - q| above about 1e154), dist is +inf with a
+ *              primitive reported if max_dist is +inf (+inf <= +inf is accepted; which primitive is not specified, and a
+ *              finite max_dist reports a miss); point is then finite but need not meet the point clauses (a sphere
+ *              reports its centre).  No field is NaN.
  *   kernel     BRUTE tests every primitive; BVH walks the binary tree; BVH4 the 4-wide tree, nearest child first; GRID
  *              has no point walk and is answered by BVH (kernel_used says BVH); AUTO takes BVH4 if the 4-wide image is
  *              resident, else BVH if the binary image is, else BRUTE (so it never fails on a resident scene).  An explicit
