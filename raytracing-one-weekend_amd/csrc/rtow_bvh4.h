@@ -92,6 +92,34 @@ struct Bvh4Image {
   bool ok = false;
 };
 
+// Sections of the image, for both builders: [nodes][triangle records, 96 B][material indices][materials], each
+// 16-byte aligned
+struct Bvh4Layout {
+  uint32_t off_tri = 0, off_pmat = 0, off_mats = 0;
+  size_t total = 0;
+};
+inline Bvh4Layout bvh4_layout(size_t n_nodes, uint32_t node_bytes, size_t nt, size_t mats_bytes) {
+  auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+  Bvh4Layout l;
+  l.off_tri = (uint32_t)(n_nodes * node_bytes);
+  l.off_pmat = (uint32_t)up16(l.off_tri + nt * 96);
+  l.off_mats = (uint32_t)up16(l.off_pmat + nt * 4);
+  l.total = up16(l.off_mats + mats_bytes);
+  return l;
+}
+
+// The mesh's own frame of the binary16 planes, for both builders: the root box (lo, hi) maps to [-1000, 1000] per
+// axis (padded planes stay below 1024, where the binary16 spacing doubles), so that a plane is at most 1/4000 of the
+// mesh's extent away from where it should be (1/12000 on average) and nothing is near a denormal
+inline void bvh4_half_frame(const double lo[3], const double hi[3], double map_c[3], double map_s[3]) {
+  const double widest = std::max({hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]});
+  for (int k = 0; k < 3; ++k) {
+    const double half_k = std::max({0.5 * (hi[k] - lo[k]), 1e-4 * widest, 1e-30});  // (a flat mesh has no extent in one axis)
+    map_c[k] = 0.5 * (lo[k] + hi[k]);
+    map_s[k] = 1000.0 / half_k;
+  }
+}
+
 // `bvh`: SAH BVH2 over triangles only with leaves of <= 4 primitives; `tri` [n][12] (a e1 e2 n) and
 // `pmat` in INSERTION order (permuted into leaf order here).
 inline void make_bvh4_image(const HostBvh &bvh, const std::vector<double> &tri, const std::vector<int32_t> &pmat,
@@ -120,16 +148,7 @@ inline void make_bvh4_image(const HostBvh &bvh, const std::vector<double> &tri, 
     scale = std::max(scale, std::fabs(cam_origin[k]));
   }
 
-  // the mesh's own frame: the root box maps to [-1000, 1000] per axis (padded planes stay below 1024, where the
-  // binary16 spacing doubles), so that a plane is at most 1/4000 of the mesh's extent away from where it should be
-  // (1/12000 on average) and nothing is near a denormal
-  for (int k = 0; half && k < 3; ++k) {
-    const double lo = bvh.box[k], hi = bvh.box[3 + k];
-    const double widest = std::max({bvh.box[3] - bvh.box[0], bvh.box[4] - bvh.box[1], bvh.box[5] - bvh.box[2]});
-    const double half_k = std::max({0.5 * (hi - lo), 1e-4 * widest, 1e-30});  // (a flat mesh has no extent in one axis)
-    img.map_c[k] = 0.5 * (lo + hi);
-    img.map_s[k] = 1000.0 / half_k;
-  }
+  if (half) bvh4_half_frame(&bvh.box[0], &bvh.box[3], img.map_c, img.map_s);
 
   // (first_inner / first_rec: the node index its first inner child gets and the record slot of its first leaf
   // triangle — running sums of the pass below, so that the second pass can write any node without the ones before it)
@@ -184,12 +203,11 @@ inline void make_bvh4_image(const HostBvh &bvh, const std::vector<double> &tri, 
   }
   const size_t n4count = nodes.size();
 
-  auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-  const size_t nodes_bytes = n4count * node_bytes;
-  img.off_tri = (uint32_t)nodes_bytes;
-  img.off_pmat = (uint32_t)up16(img.off_tri + nt * 96);
-  img.off_mats = (uint32_t)up16(img.off_pmat + nt * 4);
-  img.blob.assign(up16(img.off_mats + mats_bytes.size()), 0);
+  const Bvh4Layout lay = bvh4_layout(n4count, node_bytes, nt, mats_bytes.size());
+  img.off_tri = lay.off_tri;
+  img.off_pmat = lay.off_pmat;
+  img.off_mats = lay.off_mats;
+  img.blob.assign(lay.total, 0);
   img.n_nodes = (int32_t)n4count;
   img.depth = depth;
   unsigned char *B = img.blob.data();

@@ -5,39 +5,15 @@
 // ring of event pairs that time every trace-kernel launch without a host sync.
 // There is no CPU fallback: without a usable HIP device every entry point fails
 // with RTOW_ENODEV / RTOW_EHIP.
+//
+// This file renders and queries the resident scene; what makes a scene resident (upload, refit, the diagnostics
+// that read the images back) is rtow_scene.cpp.  rtow_ctx.h is what the two share.
 
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <algorithm>
-#include <chrono>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/rtow.h"
-#include "rtow_bvh.h"
-#include "rtow_bvh4.h"
-#include "rtow_device.h"
-#include "rtow_grid.h"
-#include "rtow_reftree.h"
+#include "rtow_ctx.h"
 
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
 
 // No C++ exception crosses the C ABI (include/rtow.h): the entry points that allocate or start threads run
 // their bodies through this.
@@ -69,41 +45,10 @@ int set_last_error(int code, const char *fmt, ...) {
 }  // namespace rtow
 namespace {
 
-#define HIPCHK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return fail(RTOW_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
 constexpr int kBlock = 256;      // STREAM kernel workgroup
 constexpr int kStreamTileMin = 64;  // STREAM kernel: from this many triangles on they are streamed through LDS tiles (below:
                                     //   scalar loads — the kernel's real use, scenes of <= 16 primitives)
 constexpr int kBvhBlock = 512;   // BVH kernel workgroup (one LDS scene image per workgroup)
-constexpr unsigned kLdsLimit = 160u * 1024u;
-constexpr int kEventRing = 256;
-
-struct DevBuf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  int ensure(size_t need) {
-    if (need <= bytes) return RTOW_OK;
-    if (p) {
-      HIPCHK(hipFree(p));
-      p = nullptr;
-      bytes = 0;
-    }
-    size_t want = need + need / 8 + 256;
-    HIPCHK(hipMalloc(&p, want));
-    bytes = want;
-    return RTOW_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-};
 
 // magic/shift for fastdiv(): libdivide's branch-free u32 scheme
 // q = (((n - t) >> 1) + t) >> shift with t = mulhi(n, magic)
@@ -131,122 +76,9 @@ rtow::FastDiv make_fastdiv(uint32_t d) {
   return f;
 }
 
-// Host-to-device copies of a scene upload go through one pinned staging arena and are queued on the null
-// stream without a host wait each (a dozen small synchronous copies were 0.2 ms of a cover-scene upload); the
-// arena is rewound at the start of the next upload, behind that upload's device synchronisation.  What does
-// not fit (a big mesh's images) is copied synchronously from pageable memory as before.
-struct PinnedArena {
-  unsigned char *p = nullptr;
-  size_t cap = 0, used = 0;
-};
-thread_local PinnedArena *g_arena = nullptr;  // the arena of the upload in progress on this thread
-
-template <class T>
-int upload(DevBuf &b, const std::vector<T> &v) {
-  size_t n = v.size() * sizeof(T);
-  int rc = b.ensure(n ? n : sizeof(T));
-  if (rc) return rc;
-  if (!n) return RTOW_OK;
-  PinnedArena *a = g_arena;
-  const size_t at = a ? (a->used + 255) / 256 * 256 : 0;
-  if (a && a->p && at + n <= a->cap) {
-    std::memcpy(a->p + at, v.data(), n);
-    a->used = at + n;
-    HIPCHK(hipMemcpyAsync(b.p, a->p + at, n, hipMemcpyHostToDevice, nullptr));
-  } else {
-    HIPCHK(hipMemcpy(b.p, v.data(), n, hipMemcpyHostToDevice));
-  }
-  return RTOW_OK;
-}
-
-// A small host block to a device address inside an upload: through the arena like upload() (the source may be a
-// stack buffer: an asynchronous copy must not read it after this returns), synchronously when the arena is full.
-int h2d_block(void *dst, const void *src, size_t n) {
-  PinnedArena *a = g_arena;
-  const size_t at = a ? (a->used + 255) / 256 * 256 : 0;
-  if (a && a->p && at + n <= a->cap) {
-    std::memcpy(a->p + at, src, n);
-    a->used = at + n;
-    HIPCHK(hipMemcpyAsync(dst, a->p + at, n, hipMemcpyHostToDevice, nullptr));
-  } else {
-    HIPCHK(hipMemcpy(dst, src, n, hipMemcpyHostToDevice));
-  }
-  return RTOW_OK;
-}
-
-// Scene image of the f32 build, derived from a binary64 image: the same prefix (nodes or
-// header+cells, then ids — everything before the sphere records), the binary64 sphere and moving
-// records (large-primitive list, BVH kernel, shading), binary32 triangle records (the only
-// triangle section), binary32 sphere and moving records (grid cells), material indices, materials.
-struct Image32 {
-  std::vector<unsigned char> blob;  // prefix left zeroed when `prefix` is NULL (filled on the device)
-  uint32_t off_sph = 0, off_mov = 0, off_tri = 0, off_sph32 = 0, off_mov32 = 0, off_pmat = 0, off_mats = 0;
-};
-// the section offsets of that image; returns its size
-size_t layout_image32(uint32_t prefix_bytes, size_t ns, size_t nm, size_t nt, size_t n_pmat, size_t mats_bytes, Image32 &out) {
-  auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-  out.off_sph = prefix_bytes;
-  out.off_mov = (uint32_t)(out.off_sph + ns * 32);
-  out.off_tri = (uint32_t)(out.off_mov + nm * 64);
-  out.off_sph32 = (uint32_t)up16(out.off_tri + nt * 48);
-  out.off_mov32 = (uint32_t)(out.off_sph32 + ns * 16);
-  out.off_pmat = (uint32_t)up16(out.off_mov32 + nm * 32);
-  out.off_mats = (uint32_t)up16(out.off_pmat + n_pmat * 4);
-  return up16(out.off_mats + mats_bytes);
-}
-void make_image32(const unsigned char *prefix, uint32_t prefix_bytes, const std::vector<double> &sph,
-                  const std::vector<double> &mov, const std::vector<double> &tri, const std::vector<int32_t> &pmat,
-                  const std::vector<unsigned char> &mats_bytes, Image32 &out) {
-  const size_t ns = sph.size() / 4, nm = mov.size() / 8, nt = tri.size() / 12;
-  out.blob.assign(layout_image32(prefix_bytes, ns, nm, nt, pmat.size(), mats_bytes.size(), out), 0);
-  unsigned char *b = out.blob.data();
-  if (prefix) std::memcpy(b, prefix, prefix_bytes);
-  if (ns) std::memcpy(b + out.off_sph, sph.data(), ns * 32);
-  if (nm) std::memcpy(b + out.off_mov, mov.data(), nm * 64);
-  float *t32 = reinterpret_cast<float *>(b + out.off_tri);
-  for (size_t i = 0; i < nt * 12; ++i) t32[i] = (float)tri[i];  // A e1 e2 n, 12 floats per triangle
-  float *s32 = reinterpret_cast<float *>(b + out.off_sph32);
-  for (size_t i = 0; i < ns * 4; ++i) s32[i] = (float)sph[i];    // cx cy cz copysign(r*r, r)
-  float *m32 = reinterpret_cast<float *>(b + out.off_mov32);
-  for (size_t i = 0; i < nm; ++i) {                              // c0xyz dx | dy dz copysign(r*r, r) 0
-    for (int k = 0; k < 7; ++k) m32[i * 8 + k] = (float)mov[i * 8 + k];
-    m32[i * 8 + 7] = 0.0f;
-  }
-  if (!pmat.empty()) std::memcpy(b + out.off_pmat, pmat.data(), pmat.size() * 4);
-  if (!mats_bytes.empty()) std::memcpy(b + out.off_mats, mats_bytes.data(), mats_bytes.size());
-}
-
-double now_ms() {
-  using namespace std::chrono;
-  return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
-namespace rtow {  // csrc/rtow_build.hip
-int lbvh_build(const double *sph, const double *sph_r, const double *mov, const double *tri, int ns, int nm,
-               int nt, double time0, double time1, const double cam_origin[3], int leaf_max, void *stream,
-               void **handle, int *n_nodes, int ploc_radius);
-int lbvh_emit(void *handle, int leaf_max, unsigned char *blob_dev, uint32_t off_ids, int n_nodes, void *stream);
-int lbvh_bvh4_collapse(void *handle, int leaf_max, void *stream, int *n_nodes, int *depth, float root_box[6]);
-int lbvh_bvh4_emit(void *handle, unsigned char *blob_dev, int half, const double map_c[3], const double map_s[3],
-                   uint32_t off_tri, uint32_t off_pmat, const double *tri, const int32_t *prim_mat, void *stream);
-void lbvh_release(void *handle);
-// csrc/rtow_build_grid.hip
-struct GridBuildBounds {
-  double gmn[3], gmx[3];
-  double scale_prims;
-  int32_t n_small, n_large;
-};
-int grid_build_phase1(const double *sph, const double *sph_r, const double *mov, const double *tri, int ns, int nm,
-                      int nt, double time0, double time1, double large_ratio, void *stream, void **handle,
-                      GridBuildBounds *out);
-int grid_build_phase2(void *handle, const float gminf[3], const float cellf[3], const int32_t n[3], double pad,
-                      void *stream, unsigned long long *total_ids, unsigned long long *max_list);
-int grid_build_phase3(void *handle, const float gminf[3], const float cellf[3], const int32_t n[3], double pad,
-                      unsigned long long total_ids, unsigned char *blob_dev, uint32_t off_cells, uint32_t off_ids,
-                      void *stream, const double *sph, uint32_t off_fat, const double *mov, int ns, uint32_t fat_stride);
-void grid_build_release(void *handle);
+namespace rtow {
 // csrc/rtow_{query,occlude,pointq}_{strict,fast}.hip (rtow_query.h, rtow_occlude.h, rtow_pointq.h): the three query kinds
 // share one launcher and one occupancy signature (`map` is unused by the occlusion query)
 using QueryLaunchFn = int(const TraceParams &p, const void *in, void *out, uint32_t n, const int32_t *map,
@@ -278,239 +110,7 @@ using CameraRaysLaunchFn = int(const TraceParams &p, void *rays, void *ids, uint
 GuidesLaunchFn launch_guides_strict, launch_guides_fast;
 CameraRaysLaunchFn launch_camera_rays_strict, launch_camera_rays_fast;
 QueryOccupancyFn guides_occupancy_strict, guides_occupancy_fast;
-// csrc/rtow_refit.hip (rtow_scene_refit): 0, or 1 when a launch failed
-int refit_records(const double *g_sph, const double *g_mov, const double *g_tri, int ns, int nm, int nt, double *sph,
-                  double *sph_r, double *mov, double *tri, double *tri16, void *stream);
-int refit_prim_boxes(const double *sph, const double *sph_r, const double *mov, const double *tri, int ns, int nm, int nt,
-                     double time0, double time1, double *pbox, void *stream);
-int refit_tri_section(int nt, const double *tri, const int32_t *pmat_tri, const int32_t *map, unsigned char *dst,
-                      uint32_t off_tri, uint32_t off_pmat, int f32, void *stream);
-int refit_spheres32(int ns, int nm, const double *sph, const double *mov, unsigned char *dst, uint32_t off_sph32,
-                    uint32_t off_mov32, void *stream);
-int refit_bvh2_links(const unsigned char *blob, int n_nodes, int32_t *parent, void *stream);
-int refit_bvh2(unsigned char *blob, int n_nodes, uint32_t off_ids, int n_ids, const int32_t *map, int cls_base,
-               const double *pbox, const int32_t *parent, uint32_t *flags, double *nbox, double *partials, int emit,
-               const double cam_origin[3], double *area_out, void *stream);
-int refit_bvh4_links(const unsigned char *blob4, int n4, uint32_t node_bytes, uint32_t child_off, int32_t *parent,
-                     int32_t *need, void *stream);
-int refit_bvh4(unsigned char *blob4, int n4, uint32_t node_bytes, uint32_t child_off, int half, int n_rec, const int32_t *map,
-               int cls_base, const double *pbox, const int32_t *parent, const int32_t *need, uint32_t *flags, double *nbox,
-               double *sbox, const double cam_origin[3], double *frame, void *stream);
 }  // namespace rtow
-
-// Experiment knobs (RTOW_* environment variables), read ONCE at rtow_ctx_create: nothing on the
-// render path touches the environment.
-struct Knobs {
-  int bvh_leaf = 0;               // RTOW_BVH_LEAF: leaf size cap of the BVH builders (0 = default)
-  double bvh_ct = -1.0;           // RTOW_BVH_CT: SAH cost of descending one level (< 0: 0, meshes 1.5)
-  bool no_leaf_order = false;     // RTOW_NO_LEAF_ORDER
-  double grid_cpp = 1.0;          // RTOW_GRID_CPP: grid cells per primitive (C2 0.5 / 0.75 / 1 / 1.25 / 1.5 / 2 / 2.5:
-                                  // 11.01 / 11.03 / 11.18 / 10.72 / 10.99 / 10.98 / 10.85 Gsamples/s; moving 9.47 / 9.53 / 9.45 /
-                                  // 9.14 / 8.99 / 8.83 / 7.64; 3-D clouds are indifferent, scripts/bench_cloud.py)
-  double grid_large = 4.0;        // RTOW_GRID_LARGE: diagonal ratio that makes a primitive "large"
-  int grid_max_tris = 8192;       // RTOW_GRID_MAX_TRIS
-  unsigned long long partials_cap = 8ull << 30;  // RTOW_PARTIALS_MAX_MB
-  int bvh_block = 0;              // RTOW_BVH_BLOCK: 256 / 512 / 1024 (0 = automatic)
-  int blocks_per_cu = 0;          // RTOW_BLOCKS_PER_CU (0 = occupancy query)
-  bool no_tiles = false;          // RTOW_NO_TILES
-  int sky_eighths = 1;            // RTOW_SKY_EIGHTHS
-  bool stamps = false;            // RTOW_STAMPS: diagnostic region-stamp build
-  bool bvh4_no_aux = false;       // RTOW_BVH4_NO_AUX: materials / material indices stay in L2 when only the top of the tree is staged
-  bool no_bvh4 = false;           // RTOW_NO_BVH4: triangle meshes keep the binary threaded walk
-  // Scheduling of the trip kernels (measured on one MI355X; 0 / "off" switches a measure off):
-  int fetch_votes = 0;            // RTOW_FETCH_VOTES: lanes that must need a work item before the fetch block runs
-                                  // (0 = per kernel: 4, BVH4 2 — 2 / 4 / 8: C4 4.01 / 3.99 / 3.89, C5 1.98 / 1.96 / 1.92, C2 10.72 / 10.73 / 10.71)
-  int leaf_votes = 0;             // RTOW_LEAF_VOTES: lanes that must hold a queued cell / leaf before a leaf phase
-                                  //   (0 = per kernel: GRID 16, BVH4 28)
-  int walk_cap = -1, walk_max_open = 0;  // RTOW_WALK_CAP=cap,max_open | off: resumable walk (-1 = per kernel:
-                                         //   GRID 3,16; BVH4 4,24 with every node in LDS, 4,32 otherwise)
-  bool bvh4_sm = false;           // RTOW_BVH4_SM: the state-machine form of the BVH4 kernel (rtow_trace_sm4.h)
-  int sm4_votes[3] = {8, 16, 16};  // RTOW_SM4_VOTES=restart,scatter,leaf: quorum of the state machine's blocks
-  int bvh4_stack_k = 0;           // RTOW_BVH4_STACK_K: image staged whole if this many stack entries per lane still fit
-                                  //   (default 8), else the entries per lane beside the staged top of the tree (default 24)
-  int sched_chunk = 10;           // RTOW_SCHED_CHUNK: fast builds: samples per work item aimed at (0 = one item per stream and
-                                  //   pixel, like the strict build).  5 / 10 / 20 / 25: 10.88 / 11.18 / 10.22 / 9.55 Gsamples/s on C2
-  int sched_chunk_mesh = 16;      //   ... for a scene of triangles only (its walks are longer and resumable: fewer, longer items;
-                                  //   4 / 8 / 16 / 32 samples: 4.60 / 4.64 / 4.69 / 4.68 Gsamples/s on C4, 2.29 / 2.30 / 2.32 / 2.32 on C5)
-  int ploc_radius = -1;           // RTOW_PLOC_RADIUS: device builder: search radius of the PLOC pass (csrc/rtow_build.hip, round 5);
-                                  //   0 = Karras' radix tree (rounds 1-4); -1 = default: 16 up to 16,384 primitives, 8 above
-  int device_tree = 2;            // RTOW_DEVICE_TREE=radix|ploc|sah: how the device builder makes its binary tree (0 / 1 / 2);
-                                  //   sah = binned surface-area heuristic, top-down, level by level (pass 3c): the default
-  bool stream_scalar = false;     // RTOW_STREAM_SCALAR: the STREAM kernel's triangle loop through scalar loads at every size (A/B
-                                  //   against the LDS-tiled loop; rounds 1-5a)
-  bool no_spec = false;           // RTOW_NO_SPEC: always the generic GRID kernel (A/B against the scene-class specialisations)
-  bool no_flat = false;           // RTOW_NO_FLAT: the scene-class kernels keep the 3D walk on a grid with one layer in y (A/B and
-                                  //   tests against the two-axis walk, kSpecFlatY)
-  bool tile_order = true;         // RTOW_TILE_ORDER=0: the queue keeps the row order alone (one segment); default: the tiles through
-                                  //   which no camera ray can reach a primitive are traced last (tile_classify)
-  int empty_levels = 3;           // RTOW_EMPTY_LEVELS: levels of a tile one atomic buys in the queue's empty-tile segment (1..16)
-  int tail_bound = 0;             // RTOW_TAIL_BOUND (tests only): trips of the end-of-launch protocol before a wave gives up
-                                  //   its samples (0 = the structural bound); a small value forces the RTOW_EHIP path
-  int radiance_blocks = 0;        // RTOW_RADIANCE_BLOCKS (tests only): cap on the workgroups of a radiance query (0 = none), so
-                                  //   that a small batch makes every lane take many rays
-  int guides_blocks = 0;          // RTOW_GUIDES_BLOCKS (tests only): the same cap for rtow_guides*: every lane takes many pixels
-  void read() {
-    auto geti = [](const char *n, int d) { const char *e = std::getenv(n); return e ? std::atoi(e) : d; };
-    auto getd = [](const char *n, double d) { const char *e = std::getenv(n); return e ? std::atof(e) : d; };
-    bvh_leaf = geti("RTOW_BVH_LEAF", 0);
-    bvh_ct = getd("RTOW_BVH_CT", -1.0);
-    no_leaf_order = std::getenv("RTOW_NO_LEAF_ORDER") != nullptr;
-    grid_cpp = getd("RTOW_GRID_CPP", 1.0);
-    grid_large = getd("RTOW_GRID_LARGE", 4.0);
-    grid_max_tris = geti("RTOW_GRID_MAX_TRIS", 8192);
-    if (const char *e = std::getenv("RTOW_PARTIALS_MAX_MB")) partials_cap = (unsigned long long)std::atoll(e) << 20;
-    bvh_block = geti("RTOW_BVH_BLOCK", 0);
-    if (bvh_block != 256 && bvh_block != 512 && bvh_block != 1024) bvh_block = 0;
-    blocks_per_cu = geti("RTOW_BLOCKS_PER_CU", 0);
-    if (blocks_per_cu < 1 || blocks_per_cu > 16) blocks_per_cu = 0;
-    no_tiles = std::getenv("RTOW_NO_TILES") != nullptr;
-    sky_eighths = std::min(std::max(geti("RTOW_SKY_EIGHTHS", 1), 0), 8);
-    stamps = std::getenv("RTOW_STAMPS") != nullptr;
-    no_bvh4 = std::getenv("RTOW_NO_BVH4") != nullptr;
-    bvh4_no_aux = std::getenv("RTOW_BVH4_NO_AUX") != nullptr;
-    fetch_votes = std::min(std::max(geti("RTOW_FETCH_VOTES", 0), 0), 64);
-    leaf_votes = std::min(std::max(geti("RTOW_LEAF_VOTES", 0), 0), 64);
-    bvh4_sm = std::getenv("RTOW_BVH4_SM") != nullptr;
-    if (const char *e = std::getenv("RTOW_WALK_CAP")) {
-      int a = 0, b = 0;
-      if (std::sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b > 0) {
-        walk_cap = a;
-        walk_max_open = std::min(b, 64);
-      } else {
-        walk_cap = 0;  // "off"
-      }
-    }
-    if (const char *e = std::getenv("RTOW_SM4_VOTES")) {
-      int a = 0, b = 0, d = 0;
-      if (std::sscanf(e, "%d,%d,%d", &a, &b, &d) == 3) {
-        sm4_votes[0] = std::min(std::max(a, 1), 64);
-        sm4_votes[1] = std::min(std::max(b, 1), 64);
-        sm4_votes[2] = std::min(std::max(d, 1), 64);
-      }
-    }
-    bvh4_stack_k = std::min(std::max(geti("RTOW_BVH4_STACK_K", 0), 0), 64);
-    sched_chunk = std::min(std::max(geti("RTOW_SCHED_CHUNK", 10), 0), 4096);
-    sched_chunk_mesh = std::min(std::max(geti("RTOW_SCHED_CHUNK_MESH", 16), 0), 4096);
-    tail_bound = std::max(geti("RTOW_TAIL_BOUND", 0), 0);
-    radiance_blocks = std::max(geti("RTOW_RADIANCE_BLOCKS", 0), 0);
-    guides_blocks = std::max(geti("RTOW_GUIDES_BLOCKS", 0), 0);
-    tile_order = geti("RTOW_TILE_ORDER", 1) != 0;
-    empty_levels = std::min(std::max(geti("RTOW_EMPTY_LEVELS", 3), 1), 16);
-    no_spec = std::getenv("RTOW_NO_SPEC") != nullptr;
-    no_flat = std::getenv("RTOW_NO_FLAT") != nullptr;
-    stream_scalar = std::getenv("RTOW_STREAM_SCALAR") != nullptr;
-    if (const char *e = std::getenv("RTOW_PLOC_RADIUS")) ploc_radius = std::min(std::max(std::atoi(e), 0), 64);
-    if (const char *e = std::getenv("RTOW_DEVICE_TREE"))
-      device_tree = std::strcmp(e, "radix") == 0 ? 0 : (std::strcmp(e, "ploc") == 0 ? 1 : 2);
-    if (ploc_radius >= 0 && !std::getenv("RTOW_DEVICE_TREE")) device_tree = ploc_radius == 0 ? 0 : 1;  // (the radius alone selects PLOC / radix)
-  }
-};
-
-// what a scene upload builds besides the record arrays: rtow_scene_upload builds everything (the scene stays
-// resident for any later render); rtow_render / rtow_render_rgb8 know their config and build what its kernel reads
-// kNeedBvh: the binary threaded image (BVH kernel); kNeedBvh4: the 4-wide image of a triangle mesh (BVH4 kernel) — a
-// render that walks the one does not pay for the other (the 96.8k-triangle mesh: 20 ms of host work and 10 MB of
-// upload less per rtow_render call)
-constexpr unsigned kNeedBvh = 1u, kNeedGrid = 2u, kNeedF32 = 4u, kNeedBvh4 = 8u, kNeedAll = 15u;
-
-struct rtow_ctx {
-  int device = 0;
-  Knobs knobs;
-  int num_cus = 0;
-  bool have_scene = false;
-  rtow::DevScene ds{};
-  rtow::DevCamera cam{};
-  int n_prims = 0;
-  // scene buffers
-  DevBuf sph, sph_r, mov, tri, tri16, prim_mat, mats, blob, cam_dev, gblob;
-  DevBuf blob4;                        // 4-wide BVH image (triangle meshes)
-  bool have_bvh4 = false;
-  bool have_tri16 = false;             // the STREAM kernel's 128-byte-stride triangle records are resident
-  int bvh4_depth = 0;
-  DevBuf blob32, gblob32, cam32_dev;  // the f32 build's scene images and camera
-  rtow::DevScene ds32{};               // ds with the f32 images' pointers and offsets
-  uint32_t gblob_bytes = 0;
-  uint32_t grid_fat_stride = 0;  // bytes per fat cell-list entry of the resident grid image (0: plain id lists)
-  int32_t grid_ny = 0;           // n[1] of the resident grid image's header (0: no grid); 1 selects the two-axis walk
-  GridWalkConsts grid_walk{};    // the walk's constants from that header (rtow_walk_consts.h): TraceParams::walk
-  int64_t last_spec = -1;        // TraceParams::spec of the last trace launch (rtow_debug_last_spec; -1: none yet)
-  bool have_grid = false;
-  uint32_t blob_bytes = 0;
-  long long bvh_nodes = 0;
-  int builder = RTOW_BUILDER_HOST_SAH;      // the builder of the upload in progress / of the resident images
-  int builder_req = RTOW_BUILDER_AUTO;      // what the caller asked for (rtow_ctx_set_builder, RTOW_BUILDER)
-  void *lbvh_scratch = nullptr;  // device builder's buffers, kept across uploads
-  void *grid_scratch = nullptr;
-  rtow_build_info_t build_info{};
-  // RTOW_KERNEL_REFTREE: the reference's own tree is built on first use from a host copy of the scene as uploaded
-  struct HostSceneCopy {
-    std::vector<double> sg, mg, tg;
-    std::vector<int32_t> pk, pi;
-    bool have_order = false;
-    rtow_camera_t cam{};
-  } host_scene;
-  // Queue order of the 64-pixel tiles (tile_queue_table): device table, queue position of a tile -> tile, made by the
-  // first render that needs it and kept while what it depends on stays: the resident scene (scene_gen counts uploads
-  // and refits), the image size, this rank's strips, the tile shape and the ordering knobs.
-  DevBuf tile_table;
-  long long tile_key[10] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t tile_empty = 0;       // tiles of the table's empty segment
-  long long scene_gen = 0;
-  DevBuf rtree;
-  bool have_rtree = false;
-  PinnedArena arena;     // staging of the scene uploads
-  unsigned built = 0;    // kNeed* bits of what the resident scene holds (rtow_render uploads only what its kernel reads)
-  // workspace
-  DevBuf partials, stack, counters, spill;
-  DevBuf out, out8;  // rtow_render / rtow_render_rgb8: device-side output of the host-buffer entry points
-  // rtow_render_rgb8: the reduce kernel of the next single-launch render writes bytes here instead of sums
-  unsigned char *fuse_rgb8 = nullptr;
-  double fuse_spp = 0.0;
-  bool fuse_used = false;
-  DevBuf counters_init;  // what the 48 counters look like before a launch (one D2D copy instead of three memsets)
-  // Samples given up at the end-of-launch bound (rtow_trace_body.h): a device word no launch resets, mirrored into
-  // pinned memory behind every render; every entry point that waits for the device checks it (check_dropped)
-  DevBuf dropped;
-  unsigned long long *h_dropped = nullptr;
-  hipEvent_t upload_ev = nullptr;  // recorded on the null stream behind the last copy / build kernel of a scene upload
-  // launch shape per [precision][kernel-1]: blocks per CU (0 = not queried yet)
-  int occ[3][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
-  // profiling ring: event pairs around each trace-kernel launch since the last collect
-  hipEvent_t ev[kEventRing][2] = {};
-  int ev_count = 0;
-  hipEvent_t call_ev[2] = {};
-  // pinned host mirror of the counters for stats
-  unsigned long long *h_counters = nullptr;
-  // ray queries (rtow_intersect*, rtow_occluded*): counters, events, spill and staging of their own (a query never
-  // touches the render's workspace, profile ring or dropped-sample word); the walk-id -> insertion-index tables are built
-  // at the first closest-hit query that needs them after an upload (query_map)
-  DevBuf q_counters, q_spill, q_rays, q_hits, q_occ, q_map[3];
-  DevBuf q_stack, q_ids, q_rgb;  // rtow_radiance*: the strict build's path stack (sized per launch), the host form's staging
-  DevBuf q_guides;               // rtow_guides: the host form's staging (rtow_camera_rays stages in q_rays / q_ids)
-  DevBuf q_khits, q_kcounts;     // rtow_first_hits: the host form's staging (its rays go through q_rays)
-  bool q_map_ok[3] = {false, false, false};
-  hipEvent_t q_ev[4] = {};
-  unsigned long long *h_qcounters = nullptr;
-  // in-place refits (rtow_scene_refit, csrc/rtow_refit.hip).  What the first refit after an upload derives from the
-  // images as built (before anything is overwritten) is kept until the next upload: the record slot -> triangle maps of
-  // the leaf-ordered images, the parent links of both trees, the area sum of the binary BVH as uploaded.
-  struct Refit {
-    bool ready = false;                // the per-upload state below is derived
-    std::vector<int32_t> slot2tri[2];  // [0] BVH image when ds.leaf_direct, [1] the 4-wide image (class-order triangle index)
-    DevBuf map2, map4, par2, par4, need4, flags, nbox2, nbox4, sbox4, pbox, partials;
-    DevBuf area;                       // [0] area sum of the upload's geometry, [1] of the last refit's; [2..7] 4-wide frame
-    DevBuf g_sph, g_mov, g_tri;        // raw geometry, staged
-    int refits = 0;
-    double refit_ms = 0.0;
-    hipEvent_t ev[2] = {};
-  } rf;
-};
-
-// BVH4: stack entries per lane (4 B x 1024 lanes each) an image staged whole must leave room for (RTOW_BVH4_STACK_K)
-// (round 5: 6, was 8 — suzanne's host tree walks at the same rate with 8, 7 and 6 entries per lane in LDS, and two more
-// entry levels are 8 KB = 64 nodes of room for a mesh near the limit: the device-built suzanne tree, 276 nodes against
-// the host's 261, is staged whole with 7)
-static uint32_t bvh4_min_stack(const rtow_ctx *c) { return c->knobs.bvh4_stack_k > 0 ? (uint32_t)c->knobs.bvh4_stack_k : 6u; }
 
 extern "C" {
 
@@ -593,556 +193,6 @@ void rtow_ctx_destroy(rtow_ctx *c) {
   delete c;
 }
 
-static int validate_scene(const rtow_scene_t *s) {
-  if (!s) return fail(RTOW_EINVAL, "scene is NULL");
-  if (s->n_spheres < 0 || s->n_moving < 0 || s->n_triangles < 0 || s->n_materials < 0)
-    return fail(RTOW_EINVAL, "negative count in scene");
-  const long long np = (long long)s->n_spheres + s->n_moving + s->n_triangles;
-  if (np == 0) return fail(RTOW_EEMPTY, "scene has no primitives");
-  if (s->n_prims != np) return fail(RTOW_EINVAL, "n_prims (%d) != sum of classes (%lld)", s->n_prims, np);
-  if (s->n_materials == 0 || !s->materials) return fail(RTOW_EINVAL, "scene has no materials");
-  if ((s->n_spheres && (!s->sphere_geom || !s->sphere_mat)) ||
-      (s->n_moving && (!s->moving_geom || !s->moving_mat)) ||
-      (s->n_triangles && (!s->triangle_geom || !s->triangle_mat)))
-    return fail(RTOW_EINVAL, "NULL geometry/material array");
-  auto chk = [&](const int32_t *m, int n) {
-    for (int i = 0; i < n; ++i)
-      if (m[i] < 0 || m[i] >= s->n_materials) return false;
-    return true;
-  };
-  if (!chk(s->sphere_mat, s->n_spheres) || !chk(s->moving_mat, s->n_moving) ||
-      !chk(s->triangle_mat, s->n_triangles))
-    return fail(RTOW_EINVAL, "material index out of range");
-  for (int i = 0; i < s->n_materials; ++i)
-    if (s->materials[i].kind < 0 || s->materials[i].kind > 2)
-      return fail(RTOW_EINVAL, "material %d has unknown kind %d", i, s->materials[i].kind);
-  return RTOW_OK;
-}
-
-static void camera_record(const rtow_camera_t &k, rtow::DevCamera &dc) {
-  for (int i = 0; i < 3; ++i) {
-    dc.origin[i] = k.origin[i];
-    dc.u[i] = k.u[i];
-    dc.v[i] = k.v[i];
-    dc.horizontal[i] = k.horizontal[i];
-    dc.vertical[i] = k.vertical[i];
-    dc.llc[i] = k.lower_left_corner[i];
-  }
-  dc.lens_radius = k.lens_radius;
-  dc.t0 = k.t0;
-  dc.t1 = k.t1;
-}
-
-// Material index per primitive (class-major) and the device material records (scene_upload, impl_scene_refit)
-static void scene_materials(const rtow_scene_t *s, std::vector<int32_t> &pmat, std::vector<rtow::DevMaterial> &mats) {
-  const int ns = s->n_spheres, nm = s->n_moving, nt = s->n_triangles;
-  pmat.resize((size_t)ns + nm + nt);
-  for (int i = 0; i < ns; ++i) pmat[i] = s->sphere_mat[i];
-  for (int i = 0; i < nm; ++i) pmat[(size_t)ns + i] = s->moving_mat[i];
-  for (int i = 0; i < nt; ++i) pmat[(size_t)ns + nm + i] = s->triangle_mat[i];
-  mats.resize(s->n_materials);
-  for (int i = 0; i < s->n_materials; ++i) {
-    const rtow_material_t &m = s->materials[i];
-    rtow::DevMaterial &d = mats[i];
-    std::memset(&d, 0, sizeof d);
-    const bool diel = m.kind == RTOW_MAT_DIELECTRIC;  // attenuation {1,1,1}, common-model.cpp:61
-    for (int k = 0; k < 3; ++k) d.att[k] = diel ? 1.0 : m.albedo[k];
-    d.fuzz = m.kind == RTOW_MAT_LAMBERTIAN ? 0.0 : m.fuzz;
-    d.ir = m.ir;
-    d.kind = m.kind;
-  }
-}
-
-// The uniform grid built in HBM (csrc/rtow_build_grid.hip) from the record arrays resident in c->sph / mov / tri; the host
-// does the scalar steps between the phases with the code the host builder uses, so the image is byte-identical.  gimg.ok
-// stays false when the scene does not suit the grid.  sph (host records) decides the fat-list format; mov, tri and pmat
-// are read for their sizes only.  (scene_upload, impl_scene_refit)
-static int grid_device_build(rtow_ctx *c, const rtow_camera_t &cam, int ns, int nm, int nt, const std::vector<double> &sph,
-                             const std::vector<double> &mov, const std::vector<double> &tri, const std::vector<int32_t> &pmat,
-                             const std::vector<unsigned char> &mats_bytes, rtow::GridImage &gimg) {
-  const double cpp = c->knobs.grid_cpp;
-  const double large_ratio = c->knobs.grid_large;
-  int rc;
-  rtow::GridBuildBounds gb;
-  int grc = rtow::grid_build_phase1((const double *)c->sph.p, (const double *)c->sph_r.p, (const double *)c->mov.p,
-                                    (const double *)c->tri.p, ns, nm, nt, cam.t0, cam.t1, large_ratio,
-                                    nullptr, &c->grid_scratch, &gb);
-  if (grc) return fail(RTOW_EHIP, "device grid build failed (phase 1, stage %d): %s", grc, hipGetErrorString(hipGetLastError()));
-  if (gb.n_small > 0 && gb.n_large <= 64) {
-    rtow::GridHeader hd;
-    rtow::grid_header(gb.gmn, gb.gmx, gb.scale_prims, cam.origin, (size_t)gb.n_small, cpp, hd);
-    unsigned long long total_ids = 0, max_list = 0;
-    grc = rtow::grid_build_phase2(c->grid_scratch, hd.gminf, hd.cellf, hd.n, hd.pad, nullptr, &total_ids, &max_list);
-    if (grc) return fail(RTOW_EHIP, "device grid build failed (phase 2, stage %d): %s", grc, hipGetErrorString(hipGetLastError()));
-    if (max_list <= 255 && total_ids + (unsigned long long)gb.n_large < (1u << 24)) {
-      const size_t ncell = (size_t)hd.n[0] * hd.n[1] * hd.n[2];
-      for (int k = 0; k < 3; ++k) gimg.n[k] = hd.n[k];
-      double scale_small = 0.0;  // (the host builder's rule: rtow_grid.h build_grid_image)
-      for (int k = 0; k < 3; ++k)
-        scale_small = std::max({scale_small, std::fabs(gb.gmn[k]), std::fabs(gb.gmx[k]), std::fabs(cam.origin[k])});
-      const uint32_t fat = rtow::grid_wants_fat_lists(nm, nt, ncell, (size_t)total_ids + (size_t)gb.n_large,
-                                                      (size_t)gb.n_large, sph, mov, tri, pmat, mats_bytes, (size_t)total_ids,
-                                                      scale_small);
-      rtow::layout_grid_image(ncell, (size_t)total_ids + (size_t)gb.n_large, (size_t)gb.n_large, sph, mov, tri, pmat,
-                              mats_bytes, gimg, true, fat ? (size_t)total_ids : 0, fat ? fat : 48u);
-      if ((rc = c->gblob.ensure(gimg.total_bytes))) return rc;
-      unsigned char *gp = (unsigned char *)c->gblob.p;
-      unsigned char header[64];
-      const uint32_t off_large = (uint32_t)(gimg.off_ids + total_ids * 4);
-      rtow::write_grid_header(header, hd, gimg.n_large, off_large, gimg.off_fat, gimg.fat_stride);
-      std::memcpy(gimg.header, header, 64);
-      HIPCHK(hipMemsetAsync(gp, 0, gimg.total_bytes, nullptr));
-      if ((rc = h2d_block(gp, header, 64))) return rc;  // (`header` is on the stack: never the source of an async copy)
-      if (ns) HIPCHK(hipMemcpyAsync(gp + gimg.off_sph, c->sph.p, sph.size() * 8, hipMemcpyDeviceToDevice, nullptr));
-      if (nm) HIPCHK(hipMemcpyAsync(gp + gimg.off_mov, c->mov.p, mov.size() * 8, hipMemcpyDeviceToDevice, nullptr));
-      if (nt) HIPCHK(hipMemcpyAsync(gp + gimg.off_tri, c->tri.p, tri.size() * 8, hipMemcpyDeviceToDevice, nullptr));
-      HIPCHK(hipMemcpyAsync(gp + gimg.off_pmat, c->prim_mat.p, pmat.size() * 4, hipMemcpyDeviceToDevice, nullptr));
-      HIPCHK(hipMemcpyAsync(gp + gimg.off_mats, c->mats.p, mats_bytes.size(), hipMemcpyDeviceToDevice, nullptr));
-      grc = rtow::grid_build_phase3(c->grid_scratch, hd.gminf, hd.cellf, hd.n, hd.pad, total_ids, gp, gimg.off_cells,
-                                    gimg.off_ids, nullptr, (const double *)c->sph.p, gimg.off_fat,
-                                    (const double *)c->mov.p, ns, gimg.fat_stride);
-      if (grc) return fail(RTOW_EHIP, "device grid build failed (phase 3, stage %d): %s", grc, hipGetErrorString(hipGetLastError()));
-      gimg.ok = true;
-    }
-  }
-  return RTOW_OK;
-}
-
-// What the context remembers of the grid image that is resident NOW, taken from its 64-byte header: called wherever an
-// image becomes resident (every upload and refit, host- or device-built).  n[1] == 1 selects the two-axis walk; the
-// specialised trace kernels read the walk's constants from the block derived here instead of the header.
-static void grid_header_resident(rtow_ctx *c, const rtow::GridImage &gimg) {
-  c->grid_ny = gimg.ok ? gimg.n[1] : 0;
-  c->grid_walk = gimg.ok ? make_grid_walk_consts(gimg.header, gimg.off_ids, gimg.off_cells) : GridWalkConsts{};
-}
-
-static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need);
-static int impl_scene_upload(rtow_ctx *c, const rtow_scene_t *s) {
-  // AUTO knows no config here: the host builder (include/rtow.h), whatever an earlier rtow_render resolved AUTO to
-  if (c && c->builder_req == RTOW_BUILDER_AUTO) c->builder = RTOW_BUILDER_HOST_SAH;
-  return scene_upload(c, s, kNeedAll);
-}
-
-static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  int rc = validate_scene(s);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipDeviceSynchronize());
-  if (!c->arena.p) {
-    if (hipHostMalloc((void **)&c->arena.p, 8u << 20, hipHostMallocDefault) == hipSuccess)
-      c->arena.cap = 8u << 20;
-    else
-      c->arena.p = nullptr;  // (uploads then copy synchronously)
-  }
-  c->arena.used = 0;
-  struct ArenaScope {  // the free function upload() finds the arena of the upload in progress here
-    explicit ArenaScope(PinnedArena *a) { g_arena = a; }
-    ~ArenaScope() { g_arena = nullptr; }
-  } arena_scope(&c->arena);
-  if (need & kNeedF32) need |= kNeedBvh | kNeedGrid;  // the binary32 images are derived from the binary64 ones (BVH2, grid)
-  c->built = 0;
-  c->have_scene = false;
-  c->have_rtree = false;
-  c->q_map_ok[0] = c->q_map_ok[1] = c->q_map_ok[2] = false;  // (the ray queries' id tables belong to the old scene)
-  c->scene_gen++;  // (the tile table belongs to the old scene)
-  c->rf.ready = false;
-  c->rf.refits = 0;
-  c->rf.refit_ms = 0.0;
-  c->build_info.ref_tree_nodes = 0;
-  c->build_info.ref_tree_stupid_volume = 0.0;
-  const double t_up0 = now_ms();
-  {
-    rtow_ctx::HostSceneCopy &h = c->host_scene;
-    h.sg.assign(s->sphere_geom, s->sphere_geom + 4 * (size_t)s->n_spheres);
-    h.mg.assign(s->moving_geom, s->moving_geom + 8 * (size_t)s->n_moving);
-    h.tg.assign(s->triangle_geom, s->triangle_geom + 9 * (size_t)s->n_triangles);
-    h.cam = s->camera;
-    h.have_order = s->prim_kind && s->prim_index;
-    if (h.have_order) {
-      for (int i = 0; i < s->n_prims; ++i) {
-        const int k = s->prim_kind[i], ix = s->prim_index[i];
-        const int cnt = k == RTOW_PRIM_SPHERE ? s->n_spheres : k == RTOW_PRIM_MOVING_SPHERE ? s->n_moving
-                        : k == RTOW_PRIM_TRIANGLE ? s->n_triangles : -1;
-        if (ix < 0 || ix >= cnt) return fail(RTOW_EINVAL, "prim_kind / prim_index entry %d out of range", i);
-      }
-      h.pk.assign(s->prim_kind, s->prim_kind + s->n_prims);
-      h.pi.assign(s->prim_index, s->prim_index + s->n_prims);
-    } else {
-      h.pk.clear();
-      h.pi.clear();
-    }
-  }
-
-  // Ray-independent terms, computed with the reference's operations (this file is
-  // built with -ffp-contract=off, so each is one IEEE operation, as on the CPU).
-  const int ns = s->n_spheres, nm = s->n_moving, nt = s->n_triangles;
-  std::vector<double> sph((size_t)ns * 4), sph_r(ns), mov((size_t)nm * 8), tri((size_t)nt * 12);
-  for (int i = 0; i < ns; ++i) {
-    const double *g = s->sphere_geom + 4 * (size_t)i;
-    sph[4 * (size_t)i + 0] = g[0];
-    sph[4 * (size_t)i + 1] = g[1];
-    sph[4 * (size_t)i + 2] = g[2];
-    // radius * radius (src/common-model.cpp:73), carrying the radius' sign: the tests take |.|
-    // for free (VOP3 input modifier), the shading step reads the sign (front_facing, :88)
-    sph[4 * (size_t)i + 3] = std::copysign(g[3] * g[3], g[3]);
-    sph_r[i] = g[3];
-  }
-  for (int i = 0; i < nm; ++i) {
-    const double *g = s->moving_geom + 8 * (size_t)i;
-    double *d = &mov[8 * (size_t)i];
-    d[0] = g[0];
-    d[1] = g[1];
-    d[2] = g[2];
-    d[3] = g[3] - g[0];  // center1 - center0, src/oo-primitives.h:65
-    d[4] = g[4] - g[1];
-    d[5] = g[5] - g[2];
-    d[6] = std::copysign(g[6] * g[6], g[6]);
-    d[7] = g[6];
-  }
-  for (int i = 0; i < nt; ++i) {
-    const double *g = s->triangle_geom + 9 * (size_t)i;
-    double *d = &tri[12 * (size_t)i];
-    const double e1[3] = {g[3] - g[0], g[4] - g[1], g[5] - g[2]};  // b - a
-    const double e2[3] = {g[6] - g[0], g[7] - g[1], g[8] - g[2]};  // c - a
-    d[0] = g[0];
-    d[1] = g[1];
-    d[2] = g[2];
-    for (int k = 0; k < 3; ++k) {
-      d[3 + k] = e1[k];
-      d[6 + k] = e2[k];
-    }
-    // n = cross(e1, e2), src/common-model.cpp:108
-    d[9] = e1[1] * e2[2] - e2[1] * e1[2];
-    d[10] = e1[2] * e2[0] - e2[2] * e1[0];
-    d[11] = e1[0] * e2[1] - e2[0] * e1[1];
-  }
-  std::vector<int32_t> pmat;
-  std::vector<rtow::DevMaterial> mats;
-  scene_materials(s, pmat, mats);
-
-  // BVH over the same records, packed with them into one scene image
-  // host SAH stops splitting by cost (mostly 1-2 primitives per leaf, cap 4); the radix tree has
-  // no cost model, so its leaves are capped at 2 (measured: 1 and 2 equal, 4 is 8-17 % slower)
-  int leaf_max = c->builder == RTOW_BUILDER_DEVICE_LBVH ? 2 : 4;
-  // Triangle meshes (the tree the 4-wide image is collapsed from): PAIRS of triangles per leaf — a cost of 1.5
-  // primitive tests per level descended makes the SAH stop at two triangles, the cap keeps it from stopping
-  // earlier.  Against single-triangle leaves (cost 0, what the builder makes of any cap): suzanne 452 -> 261
-  // 4-wide nodes, the whole image now fits LDS with 7 stack entries per lane, 4.06 -> 4.67 Gsamples/s; the
-  // 96.8k-triangle mesh 2.00 -> 2.08.  (Cost 1 / cap 4: 4.45 / 2.01; cap 3: 4.49 / 2.01; cost 3 / cap 2: the same
-  // tree as 1.5 / 2.)  The binary walk over the same tree loses 3.5 % on suzanne (3.39 -> 3.27): it is the fallback.
-  const bool mesh_tree = ns == 0 && nm == 0 && nt > 0 && c->builder != RTOW_BUILDER_DEVICE_LBVH && !c->knobs.no_bvh4;
-  if (mesh_tree) leaf_max = 2;
-  if (c->knobs.bvh_leaf > 0) leaf_max = std::min(std::max(c->knobs.bvh_leaf, 1), 7);
-  rtow::SceneImage img;
-  std::vector<unsigned char> mats_bytes(mats.size() * sizeof(rtow::DevMaterial));
-  std::memcpy(mats_bytes.data(), mats.data(), mats_bytes.size());
-  if ((rc = upload(c->sph, sph)) || (rc = upload(c->sph_r, sph_r)) || (rc = upload(c->mov, mov)) ||
-      (rc = upload(c->tri, tri)) || (rc = upload(c->prim_mat, pmat)) || (rc = upload(c->mats, mats)))
-    return rc;
-  // the STREAM kernel's copy of the triangle records at a 128-byte stride (rtow_device.h): for the uploads that may be
-  // followed by a STREAM render of triangles — everything (rtow_scene_upload) or nothing but the records (a render
-  // that asked for the STREAM / reference-tree kernels)
-  c->have_tri16 = false;
-  if (nt > 0 && (need == kNeedAll || need == 0u)) {
-    std::vector<double> tri16((size_t)nt * 16, 0.0);
-    for (int i = 0; i < nt; ++i) std::memcpy(&tri16[(size_t)i * 16], &tri[(size_t)i * 12], 12 * sizeof(double));
-    if ((rc = upload(c->tri16, tri16))) return rc;
-    c->have_tri16 = true;
-  }
-  bool leaf_direct = false;
-  std::vector<double> tri_img;    // leaf-ordered copies (triangle meshes, host builder)
-  std::vector<int32_t> pmat_img;
-  const double t_bvh0 = now_ms();
-  c->have_bvh4 = false;
-  c->build_info.bvh4_nodes = 0;
-  c->build_info.bvh4_image_bytes = 0;
-  c->build_info.bvh4_node_bytes = 0;
-  const bool want2 = (need & kNeedBvh) != 0, want4 = (need & kNeedBvh4) != 0 && ns == 0 && nm == 0 && nt > 0 && !c->knobs.no_bvh4;
-  if (want2 || want4) {
-  if (c->builder == RTOW_BUILDER_DEVICE_LBVH) {
-    // the tree is built in HBM from the record arrays just uploaded; the host only lays out
-    // the image sections around it
-    int n_nodes = 0;
-    int brc = rtow::lbvh_build((const double *)c->sph.p, (const double *)c->sph_r.p, (const double *)c->mov.p,
-                               (const double *)c->tri.p, ns, nm, nt, s->camera.t0, s->camera.t1, s->camera.origin,
-                               leaf_max, nullptr, &c->lbvh_scratch, &n_nodes,
-                               c->knobs.device_tree == 2   ? -1
-                               : c->knobs.device_tree == 0 ? 0
-                               : c->knobs.ploc_radius > 0  ? c->knobs.ploc_radius
-                                                           : (ns + nm + nt <= 16384 ? 16 : 8));
-    if (brc) return fail(RTOW_EHIP, "device BVH build failed (stage %d): %s", brc, hipGetErrorString(hipGetLastError()));
-    if (want2) {
-    rtow::layout_scene_image(n_nodes, (size_t)(ns + nm + nt), sph, mov, tri, pmat, mats_bytes, img, true);
-    if ((rc = c->blob.ensure(img.total_bytes))) return rc;
-    // image sections: device-to-device copies of the arrays uploaded above, zeroed node section
-    unsigned char *bp = (unsigned char *)c->blob.p;
-    HIPCHK(hipMemsetAsync(bp, 0, img.off_sph, nullptr));
-    if (ns) HIPCHK(hipMemcpyAsync(bp + img.off_sph, c->sph.p, sph.size() * 8, hipMemcpyDeviceToDevice, nullptr));
-    if (nm) HIPCHK(hipMemcpyAsync(bp + img.off_mov, c->mov.p, mov.size() * 8, hipMemcpyDeviceToDevice, nullptr));
-    if (nt) HIPCHK(hipMemcpyAsync(bp + img.off_tri, c->tri.p, tri.size() * 8, hipMemcpyDeviceToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(bp + img.off_pmat, c->prim_mat.p, pmat.size() * 4, hipMemcpyDeviceToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(bp + img.off_mats, c->mats.p, mats_bytes.size(), hipMemcpyDeviceToDevice, nullptr));
-    brc = rtow::lbvh_emit(c->lbvh_scratch, leaf_max, bp, img.off_ids, n_nodes, nullptr);
-    if (brc == 4) return fail(RTOW_EINVAL, "internal error: device-built scene image failed validation (BVH links)");
-    if (brc) return fail(RTOW_EHIP, "device BVH emit failed (stage %d): %s", brc, hipGetErrorString(hipGetLastError()));
-    }
-    // triangle meshes: the 4-wide image the BVH4 kernel walks, collapsed from the same radix tree ON THE DEVICE
-    // (csrc/rtow_build.hip) — the reference builds its tree inside render()'s timer (src/render.cpp:73-110,141-188);
-    // with the device builder nothing of the build runs on the host
-    if (want4 && leaf_max <= 4) {
-      int n4 = 0, depth4 = 0;
-      float rb[6];
-      brc = rtow::lbvh_bvh4_collapse(c->lbvh_scratch, leaf_max, nullptr, &n4, &depth4, rb);
-      if (brc == 4) return fail(RTOW_EINVAL, "internal error: device 4-wide collapse failed validation");
-      if (brc != 0 && brc != 5)
-        return fail(RTOW_EHIP, "device 4-wide collapse failed (stage %d): %s", brc, hipGetErrorString(hipGetLastError()));
-      if (brc == 0) {  // (5: beyond the format's limits — the binary walk takes the scene)
-        auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-        auto layout = [&](uint32_t node_bytes, uint32_t &off_tri, uint32_t &off_pmat, uint32_t &off_mats) {
-          off_tri = (uint32_t)((size_t)n4 * node_bytes);
-          off_pmat = (uint32_t)up16(off_tri + (size_t)nt * 96);
-          off_mats = (uint32_t)up16(off_pmat + (size_t)nt * 4);
-          return up16(off_mats + mats_bytes.size());
-        };
-        uint32_t off_tri4 = 0, off_pmat4 = 0, off_mats4 = 0;
-        size_t total4 = layout(rtow::kBvh4NodeBytes, off_tri4, off_pmat4, off_mats4);
-        // the same rule as the host builder: binary32 planes when LDS holds the whole image beside the stack,
-        // 64-byte nodes with binary16 planes in the mesh's own frame otherwise (rtow_bvh4.h)
-        const bool half = total4 + bvh4_min_stack(c) * 4u * 1024u > kLdsLimit;
-        double map_c[3] = {0, 0, 0}, map_s[3] = {1, 1, 1};
-        if (half) {
-          total4 = layout(rtow::kBvh4HalfNodeBytes, off_tri4, off_pmat4, off_mats4);
-          const double widest = std::max({(double)rb[3] - rb[0], (double)rb[4] - rb[1], (double)rb[5] - rb[2]});
-          for (int k = 0; k < 3; ++k) {
-            const double lo = rb[k], hi = rb[3 + k];
-            const double half_k = std::max({0.5 * (hi - lo), 1e-4 * widest, 1e-30});
-            map_c[k] = 0.5 * (lo + hi);
-            map_s[k] = 1000.0 / half_k;
-          }
-        }
-        if ((rc = c->blob4.ensure(total4))) return rc;
-        unsigned char *b4 = (unsigned char *)c->blob4.p;
-        HIPCHK(hipMemsetAsync(b4 + off_pmat4, 0, total4 - off_pmat4, nullptr));  // (alignment gaps)
-        HIPCHK(hipMemcpyAsync(b4 + off_mats4, c->mats.p, mats_bytes.size(), hipMemcpyDeviceToDevice, nullptr));
-        brc = rtow::lbvh_bvh4_emit(c->lbvh_scratch, b4, half ? 1 : 0, map_c, map_s, off_tri4, off_pmat4,
-                                   (const double *)c->tri.p, (const int32_t *)c->prim_mat.p, nullptr);
-        if (brc == 4) return fail(RTOW_EINVAL, "internal error: device-built 4-wide image failed validation");
-        if (brc) return fail(RTOW_EHIP, "device 4-wide emit failed (stage %d): %s", brc, hipGetErrorString(hipGetLastError()));
-        c->have_bvh4 = true;
-        c->bvh4_depth = depth4;
-        c->ds.blob4 = b4;
-        c->ds.blob4_bytes = (uint32_t)total4;
-        c->ds.b4_off_tri = off_tri4;
-        c->ds.b4_off_pmat = off_pmat4;
-        c->ds.b4_off_mats = off_mats4;
-        c->ds.b4_half = half ? 1u : 0u;
-        for (int k = 0; k < 3; ++k) {
-          c->ds.b4_c[k] = map_c[k];
-          c->ds.b4_is[k] = (float)(1.0 / map_s[k]);
-        }
-        c->build_info.bvh4_nodes = n4;
-        c->build_info.bvh4_image_bytes = (int32_t)total4;
-        c->build_info.bvh4_node_bytes = (int32_t)(half ? rtow::kBvh4HalfNodeBytes : rtow::kBvh4NodeBytes);
-      }
-    }
-  } else {
-    rtow::HostBvh bvh;
-    const double c_trav = c->knobs.bvh_ct >= 0.0 ? c->knobs.bvh_ct : (mesh_tree ? 1.5 : 0.0);
-    rtow::build_bvh(sph, sph_r, mov, tri, bvh, leaf_max, c_trav, s->camera.t0, s->camera.t1);
-    std::vector<int32_t> prim_order;  // the tree's primitive order before the leaf-order pass renumbers it (for the 4-wide image)
-    if (want4 && leaf_max <= 4) prim_order = bvh.prim;
-    if (want2) {
-    if (ns == 0 && nm == 0 && !c->knobs.no_leaf_order) {
-      // Triangle meshes: the image holds the triangle records and their material indices in LEAF order
-      // and the id list is the identity, so a leaf test reads its records directly instead of id ->
-      // record (one LDS / L2 round trip less per leaf, and leaf neighbours are memory neighbours:
-      // +10 % on the 96.8k-triangle mesh, whose image lives in global memory).  `best.prim` is then a
-      // leaf slot; shading reads the same permuted sections.  (Host builder only.)
-      tri_img.resize(tri.size());
-      pmat_img.resize(pmat.size());
-      for (size_t sl = 0; sl < bvh.prim.size(); ++sl) {
-        std::memcpy(&tri_img[sl * 12], &tri[(size_t)bvh.prim[sl] * 12], 96);
-        pmat_img[sl] = pmat[bvh.prim[sl]];
-      }
-      for (size_t sl = 0; sl < bvh.prim.size(); ++sl) bvh.prim[sl] = (int32_t)sl;
-      rtow::make_scene_image(bvh, sph, mov, tri_img, s->camera.origin, img, pmat_img, mats_bytes);
-      leaf_direct = true;
-    } else
-    rtow::make_scene_image(bvh, sph, mov, tri, s->camera.origin, img, pmat, mats_bytes);
-    if (!rtow::validate_scene_image(img, ns + nm + nt))
-      return fail(RTOW_EINVAL, "internal error: scene image failed validation (BVH links)");
-    if ((rc = upload(c->blob, img.blob))) return rc;
-    }
-    // triangle meshes: the 4-wide tree collapsed from the same SAH tree (rtow_bvh4.h)
-    c->have_bvh4 = false;
-    if (want4) {
-      rtow::Bvh4Image img4;
-      if (!prim_order.empty()) {  // the same SAH tree, collapsed (leaves of at most 4 triangles)
-        bvh.prim = prim_order;
-        // an image that LDS cannot hold whole is read from L2 below the top of its tree: 64-byte nodes with
-        // binary16 planes (4 loads per node instead of 7; rtow_bvh4.h).  The records alone decide it for a big mesh
-        // (no point in building the binary32 image first: 20 ms of the 96.8k-triangle mesh's upload)
-        const bool surely_half = (size_t)nt * 100u + bvh4_min_stack(c) * 4u * 1024u > kLdsLimit;
-        rtow::make_bvh4_image(bvh, tri, pmat, mats_bytes, s->camera.origin, img4, /*half=*/surely_half);
-        if (!surely_half && img4.ok && img4.blob.size() + bvh4_min_stack(c) * 4u * 1024u > kLdsLimit)
-          rtow::make_bvh4_image(bvh, tri, pmat, mats_bytes, s->camera.origin, img4, /*half=*/true);
-      }
-      if (img4.ok) {
-        if (!rtow::validate_bvh4_image(img4, (size_t)nt))
-          return fail(RTOW_EINVAL, "internal error: 4-wide scene image failed validation");
-        if ((rc = upload(c->blob4, img4.blob))) return rc;
-        c->have_bvh4 = true;
-        c->bvh4_depth = img4.depth;
-        c->ds.blob4 = (const unsigned char *)c->blob4.p;
-        c->ds.blob4_bytes = (uint32_t)img4.blob.size();
-        c->ds.b4_off_tri = img4.off_tri;
-        c->ds.b4_off_pmat = img4.off_pmat;
-        c->ds.b4_off_mats = img4.off_mats;
-        c->ds.b4_half = img4.half ? 1u : 0u;
-        for (int k = 0; k < 3; ++k) {
-          c->ds.b4_c[k] = img4.map_c[k];
-          c->ds.b4_is[k] = (float)(1.0 / img4.map_s[k]);
-        }
-        c->build_info.bvh4_nodes = img4.n_nodes;
-        c->build_info.bvh4_image_bytes = (int32_t)img4.blob.size();
-        c->build_info.bvh4_node_bytes = (int32_t)img4.node_bytes();
-      }
-    }
-  }
-  }  // kNeedBvh
-  const double t_bvh1 = now_ms();
-  c->blob_bytes = (uint32_t)img.total_bytes;
-  c->bvh_nodes = img.n_nodes;
-  // uniform grid over the small primitives (when the scene suits it)
-  rtow::GridImage gimg;
-  const double cpp = c->knobs.grid_cpp;
-  const double large_ratio = c->knobs.grid_large;
-  // big meshes never take the grid (a triangle spans many cells: 0.4x the BVH):
-  // skip the host build, a GRID request then falls back to the BVH
-  const int grid_max_tris = c->knobs.grid_max_tris;
-  bool grid_on_device = false;
-  if (!(need & kNeedGrid)) {
-    // (not asked for)
-  } else if (nt <= grid_max_tris && c->builder == RTOW_BUILDER_DEVICE_LBVH) {
-    // the same grid, built in HBM (csrc/rtow_build_grid.hip)
-    grid_on_device = true;
-    if ((rc = grid_device_build(c, s->camera, ns, nm, nt, sph, mov, tri, pmat, mats_bytes, gimg))) return rc;
-  } else if (nt <= grid_max_tris) {
-    rtow::build_grid_image(sph, sph_r, mov, tri, s->camera.origin, gimg, cpp, large_ratio, s->camera.t0,
-                           s->camera.t1, pmat, mats_bytes);
-  }
-  const double t_grid1 = now_ms();
-  c->have_grid = gimg.ok;
-  c->grid_fat_stride = (gimg.ok && gimg.off_fat) ? gimg.fat_stride : 0u;
-  grid_header_resident(c, gimg);
-  c->gblob_bytes = 0;
-  if (gimg.ok) {
-    if (!grid_on_device && (rc = upload(c->gblob, gimg.blob))) return rc;
-    c->gblob_bytes = (uint32_t)(grid_on_device ? gimg.total_bytes : gimg.blob.size());
-  }
-  for (auto &o : c->occ) o[0] = o[1] = o[2] = o[3] = o[4] = 0;
-
-  rtow::DevScene &ds = c->ds;
-  ds.sph = (const double *)c->sph.p;
-  ds.sph_r = (const double *)c->sph_r.p;
-  ds.mov = (const double *)c->mov.p;
-  ds.tri = (const double *)c->tri.p;
-  ds.tri16 = c->have_tri16 ? (const double *)c->tri16.p : nullptr;
-  ds.prim_mat = (const int32_t *)c->prim_mat.p;
-  ds.mats = (const rtow::DevMaterial *)c->mats.p;
-  ds.n_sph = ns;
-  ds.n_mov = nm;
-  ds.n_tri = nt;
-  ds.n_mats = s->n_materials;
-  ds.blob = (const unsigned char *)c->blob.p;
-  ds.blob_bytes = c->blob_bytes;
-  ds.off_ids = img.off_ids;
-  ds.off_sph = img.off_sph;
-  ds.off_mov = img.off_mov;
-  ds.off_tri = img.off_tri;
-  ds.off_pmat = img.off_pmat;
-  ds.off_mats = img.off_mats;
-  ds.n_nodes = img.n_nodes;
-  ds.leaf_direct = leaf_direct ? 1 : 0;
-  ds.gblob = (const unsigned char *)c->gblob.p;
-  ds.gblob_bytes = c->gblob_bytes;
-  ds.g_off_cells = gimg.off_cells;
-  ds.g_off_ids = gimg.off_ids;
-  ds.g_off_sph = gimg.off_sph;
-  ds.g_off_mov = gimg.off_mov;
-  ds.g_off_tri = gimg.off_tri;
-  ds.g_off_pmat = gimg.off_pmat;
-  ds.g_off_mats = gimg.off_mats;
-  c->n_prims = ns + nm + nt;
-
-  rtow::DevCamera &dc = c->cam;
-  camera_record(s->camera, dc);
-  {
-    std::vector<rtow::DevCamera> one(1, dc);
-    if ((rc = upload(c->cam_dev, one))) return rc;
-  }
-  // ---- the f32 build's images (same trees, binary32 records for the small primitives) ----
-  c->ds32 = c->ds;
-  if (need & kNeedF32) {
-    Image32 b32;
-    const bool device_tree = c->builder == RTOW_BUILDER_DEVICE_LBVH;
-    make_image32(device_tree ? nullptr : img.blob.data(), img.off_sph, sph, mov, leaf_direct ? tri_img : tri,
-                 leaf_direct ? pmat_img : pmat, mats_bytes, b32);
-    if ((rc = upload(c->blob32, b32.blob))) return rc;
-    if (device_tree)  // nodes + ids exist only in HBM
-      HIPCHK(hipMemcpy(c->blob32.p, c->blob.p, img.off_sph, hipMemcpyDeviceToDevice));
-    rtow::DevScene &d32 = c->ds32;
-    d32 = c->ds;
-    d32.blob = (const unsigned char *)c->blob32.p;
-    d32.blob_bytes = (uint32_t)b32.blob.size();
-    d32.off_sph = b32.off_sph;
-    d32.off_mov = b32.off_mov;
-    d32.off_tri = b32.off_tri;
-    d32.off_sph32 = b32.off_sph32;
-    d32.off_mov32 = b32.off_mov32;
-    d32.off_pmat = b32.off_pmat;
-    d32.off_mats = b32.off_mats;
-    d32.gblob = nullptr;
-    d32.gblob_bytes = 0;
-    if (gimg.ok) {
-      Image32 g32;
-      make_image32(grid_on_device ? nullptr : gimg.blob.data(), gimg.off_sph, sph, mov, tri, pmat, mats_bytes, g32);
-      if ((rc = upload(c->gblob32, g32.blob))) return rc;
-      if (grid_on_device)  // header, cells and ids exist only in HBM
-        HIPCHK(hipMemcpy(c->gblob32.p, c->gblob.p, gimg.off_sph, hipMemcpyDeviceToDevice));
-      d32.gblob = (const unsigned char *)c->gblob32.p;
-      d32.gblob_bytes = (uint32_t)g32.blob.size();
-      d32.g_off_sph = g32.off_sph;
-      d32.g_off_mov = g32.off_mov;
-      d32.g_off_tri = g32.off_tri;
-      d32.g_off_sph32 = g32.off_sph32;
-      d32.g_off_mov32 = g32.off_mov32;
-      d32.g_off_pmat = g32.off_pmat;
-      d32.g_off_mats = g32.off_mats;
-    }
-    const double *cd = reinterpret_cast<const double *>(&dc);
-    std::vector<float> cam32(21);
-    for (int i = 0; i < 21; ++i) cam32[i] = (float)cd[i];
-    if ((rc = upload(c->cam32_dev, cam32))) return rc;
-  }
-  // Ordering contract (include/rtow.h): the copies and build kernels above are queued on the null stream without a
-  // host wait; a render on ANOTHER stream (a hipStreamNonBlocking stream is not ordered behind the null stream) waits
-  // for this event first (render_levels)
-  HIPCHK(hipEventRecord(c->upload_ev, nullptr));
-  c->built = need;
-  c->have_scene = true;
-  rtow_build_info_t &bi = c->build_info;
-  bi.builder = c->builder;
-  bi.bvh_nodes = (int32_t)img.n_nodes;
-  bi.bvh_image_bytes = (int32_t)c->blob_bytes;
-  bi.grid_image_bytes = (int32_t)c->gblob_bytes;
-  bi.bvh_build_ms = t_bvh1 - t_bvh0;
-  bi.grid_build_ms = t_grid1 - t_bvh1;
-  bi.upload_ms = now_ms() - t_up0;
-  return RTOW_OK;
-}
-
 static int validate_cfg(const rtow_config_t *cfg) {
   if (!cfg) return fail(RTOW_EINVAL, "config is NULL");
   if (cfg->image_width <= 0 || cfg->image_height <= 0)
@@ -1173,13 +223,6 @@ int rtow_ctx_set_builder(rtow_ctx *c, int32_t builder) {
     return fail(RTOW_EINVAL, "unknown builder %d", builder);
   c->builder_req = builder;
   c->builder = builder == RTOW_BUILDER_DEVICE_LBVH ? RTOW_BUILDER_DEVICE_LBVH : RTOW_BUILDER_HOST_SAH;  // (AUTO without a config: host)
-  return RTOW_OK;
-}
-
-int rtow_build_info(rtow_ctx *c, rtow_build_info_t *out) {
-  if (!c || !out) return fail(RTOW_EINVAL, "NULL argument");
-  if (!c->have_scene) return fail(RTOW_EINVAL, "no scene uploaded");
-  *out = c->build_info;
   return RTOW_OK;
 }
 
@@ -1956,36 +999,6 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
 // ---- ray queries (rtow_intersect / rtow_intersect_device) -------------------------------------------------------------
 constexpr int64_t kMaxQueryRays = (1ll << 31) - 64;  // include/rtow.h
 
-// Record slot of a leaf-ordered image -> class-order triangle index (which: 1 the host-built mesh BVH image, 2 the 4-wide
-// image).  The leaf-ordered images hold exact copies of the class-ordered triangle records, so a slot's triangle is found by
-// matching its 96 bytes (identical records — duplicate triangles — are paired in order: any one of them gives the same hit).
-static int match_slots(rtow_ctx *c, int which, std::vector<int32_t> &slot2tri) {
-  const int nt = c->ds.n_tri;
-  const unsigned char *img = which == 1 ? c->ds.blob + c->ds.off_tri : c->ds.blob4 + c->ds.b4_off_tri;
-  const size_t bytes = (size_t)nt * 96u;
-  std::vector<unsigned char> rec_cls(bytes), rec_img(bytes);
-  HIPCHK(hipMemcpy(rec_cls.data(), c->tri.p, bytes, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(rec_img.data(), img, bytes, hipMemcpyDeviceToHost));
-  std::vector<int32_t> oc((size_t)nt), oi((size_t)nt);
-  for (int i = 0; i < nt; ++i) oc[i] = oi[i] = i;
-  auto by_record = [](const std::vector<unsigned char> &r) {
-    return [&r](int32_t a, int32_t b) {
-      const int m = std::memcmp(&r[(size_t)a * 96u], &r[(size_t)b * 96u], 96);
-      return m != 0 ? m < 0 : a < b;
-    };
-  };
-  std::sort(oc.begin(), oc.end(), by_record(rec_cls));
-  std::sort(oi.begin(), oi.end(), by_record(rec_img));
-  slot2tri.assign((size_t)nt, -1);
-  for (int k = 0; k < nt; ++k) {
-    if (std::memcmp(&rec_cls[(size_t)oc[k] * 96u], &rec_img[(size_t)oi[k] * 96u], 96) != 0)
-      return fail(RTOW_EINVAL, "internal error: the %s image's triangle records are not those of the scene",
-                  which == 1 ? "BVH" : "4-wide");
-    slot2tri[(size_t)oi[k]] = oc[k];
-  }
-  return RTOW_OK;
-}
-
 // Walk-order primitive id -> insertion index (the uploaded scene's prim_kind / prim_index order; class-major order when
 // the scene came without one).  which: 0 class-major ids (STREAM, GRID, REFTREE walks and a device-built BVH image),
 // 1 the record slots of a host-built mesh BVH image (ds.leaf_direct), 2 the record slots of the 4-wide image (match_slots).
@@ -2023,6 +1036,11 @@ static int query_map(rtow_ctx *c, int which, const int32_t **out) {
   c->q_map_ok[which] = true;
   *out = (const int32_t *)b.p;
   return RTOW_OK;
+}
+
+// The table the hits of `kernel`'s walk need: the 4-wide image's record slots, a leaf-ordered binary image's, or class-major ids
+static int query_map_for(rtow_ctx *c, int kernel, const int32_t **out) {
+  return query_map(c, kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0), out);
 }
 
 // What the three queries (rtow_intersect*, rtow_occluded*, rtow_closest_point*) share around their kernels.  QueryKind:
@@ -2180,10 +1198,7 @@ static int query_device(rtow_ctx *c, const QueryKind &k, int32_t precision, int3
 
   const int kernel = q.kernel;
   const int32_t *map = nullptr;
-  if (k.mapped) {
-    const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
-    if ((rc = query_map(c, which, &map))) return rc;
-  }
+  if (k.mapped && (rc = query_map_for(c, kernel, &map))) return rc;
   const int block = q.shape.block;
   const unsigned lds = k.point && kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;
   const int build = q.strict ? 0 : 1;
@@ -2236,8 +1251,7 @@ static int first_hits_device(rtow_ctx *c, int32_t precision, int32_t kernel_req,
 
   const int kernel = q.kernel;
   const int32_t *map = nullptr;
-  const int which = kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0);
-  if ((rc = query_map(c, which, &map))) return rc;
+  if ((rc = query_map_for(c, kernel, &map))) return rc;
   const int block = q.shape.block;
   const unsigned lds = kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;
   const int build = q.strict ? 0 : 1;
@@ -2485,56 +1499,6 @@ int64_t rtow_camera_ray_count(const rtow_config_t *cfg) {
   return (int64_t)(k.npix * k.samples);
 }
 
-// Diagnostic: copy a resident scene image to the host (0 BVH, 1 grid, 2 BVH of the f32 build,
-// 3 grid of the f32 build, 4 the 4-wide BVH, 5 the 48-byte frame record of the 4-wide walk: Bvh4Frame).
-// Used by the tests to compare host- and device-built images and to check them against the geometry.
-struct Bvh4Frame {   // rtow_debug_image(5): what the 4-wide walk decodes binary16 planes with (world = c + h * is)
-  double c[3];       // DevScene::b4_c
-  float is[3];       // DevScene::b4_is, as stored
-  uint32_t half;     // DevScene::b4_half: 64-byte nodes with binary16 planes
-  uint32_t lds_limit;  // DevScene::b4_lds_limit of the resident scene (the launches set their own copy's)
-  uint32_t pad_;
-};
-static_assert(sizeof(Bvh4Frame) == 48, "rtow_debug_image(5) record");
-
-int rtow_debug_image(rtow_ctx *c, int32_t which, void *out, int64_t capacity, int64_t *size_out) {
-  if (!c || !size_out) return fail(RTOW_EINVAL, "NULL argument");
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  const void *src = nullptr;
-  int64_t bytes = 0;
-  Bvh4Frame frame{};
-  switch (which) {
-    case 0: src = c->blob.p; bytes = c->ds.blob_bytes; break;
-    case 1: src = c->gblob.p; bytes = c->ds.gblob_bytes; break;
-    case 2: src = c->blob32.p; bytes = c->ds32.blob_bytes; break;
-    case 3: src = c->gblob32.p; bytes = c->ds32.gblob_bytes; break;
-    case 4: src = c->blob4.p; bytes = c->have_bvh4 ? c->ds.blob4_bytes : 0; break;
-    case 5:
-      if (c->have_bvh4) {
-        for (int k = 0; k < 3; ++k) {
-          frame.c[k] = c->ds.b4_c[k];
-          frame.is[k] = c->ds.b4_is[k];
-        }
-        frame.half = c->ds.b4_half;
-        frame.lds_limit = c->ds.b4_lds_limit;
-        bytes = (int64_t)sizeof frame;
-      }
-      break;
-    default: return fail(RTOW_EINVAL, "unknown image %d", which);
-  }
-  *size_out = bytes;
-  if (!out) return RTOW_OK;  // size query
-  if (capacity < bytes) return fail(RTOW_EINVAL, "buffer too small (%lld < %lld)", (long long)capacity, (long long)bytes);
-  if (which == 5) {
-    if (bytes) std::memcpy(out, &frame, sizeof frame);
-    return RTOW_OK;
-  }
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipDeviceSynchronize());
-  if (bytes) HIPCHK(hipMemcpy(out, src, (size_t)bytes, hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-
 // Diagnostic: the 16 device counters of the last launch (work queue, segments, prim
 // tests, node tests, ... region cycle sums of the RTOW_STAMPS build at [8..12]).
 int rtow_debug_counters(rtow_ctx *c, unsigned long long *out48) {
@@ -2585,44 +1549,6 @@ int rtow_profile_collect(rtow_ctx *c, double *kernel_ms_sum, int32_t *launches) 
   // the asynchronous entry point (rtow_render_device without stats) reports dropped samples here: every launch
   // of the ring has completed
   return waited ? check_dropped(c, false) : RTOW_OK;
-}
-
-// Upload for ONE render whose config is known: only what its kernel reads (the cover scene through the grid
-// kernel needs no BVH image, no 4-wide image and no binary32 images: 0.48 -> 0.15 ms per call).
-static int upload_for(rtow_ctx *c, const rtow_scene_t *scene, const rtow_config_t *cfg) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  int rc = validate_scene(scene);
-  if (rc) return rc;
-  const long long np = (long long)scene->n_spheres + scene->n_moving + scene->n_triangles;
-  unsigned need;
-  const int k = cfg->kernel;
-  const bool mesh = scene->n_spheres == 0 && scene->n_moving == 0 && scene->n_triangles > 0 && !c->knobs.no_bvh4;
-  if (cfg->precision == RTOW_F32)
-    need = kNeedAll;
-  else if (k == RTOW_KERNEL_REFTREE || k == RTOW_KERNEL_BRUTE || (k == RTOW_KERNEL_AUTO && np <= 16))
-    need = 0u;
-  else if ((k == RTOW_KERNEL_AUTO || k == RTOW_KERNEL_GRID) && scene->n_triangles == 0)
-    need = kNeedGrid;
-  else if (k == RTOW_KERNEL_GRID)
-    need = kNeedGrid | kNeedBvh;
-  else if (mesh && (k == RTOW_KERNEL_AUTO || k == RTOW_KERNEL_BVH4))
-    need = kNeedBvh4;  // the 4-wide image only (the binary image is another 20 ms and 10 MB for the 96.8k-triangle mesh)
-  else
-    need = kNeedBvh;
-  if (c->builder_req == RTOW_BUILDER_AUTO) {
-    // AUTO (include/rtow.h): the device builder where it delivers the frame sooner.  Its tree is the host's (binned SAH,
-    // csrc/rtow_build.hip pass 3c: the same node and triangle tests per segment), so what decides is the build: a fixed
-    // ~1.7 ms of launches plus ~0.055 us per triangle on the device, ~0.15 us per triangle on the host's 16 threads
-    // (96,800 triangles: 7 against 12-16 ms) — the device from about 16,000 triangles on, at any sample count.
-    const bool device = mesh && need == kNeedBvh4 && scene->n_triangles >= 16384;
-    c->builder = device ? RTOW_BUILDER_DEVICE_LBVH : RTOW_BUILDER_HOST_SAH;
-  }
-  rc = scene_upload(c, scene, need);
-  if (rc == RTOW_OK && (need & kNeedGrid) && !(need & kNeedBvh) && !c->have_grid)
-    rc = scene_upload(c, scene, need | kNeedBvh);  // the scene does not suit a grid: the walk falls back to the BVH
-  if (rc == RTOW_OK && need == kNeedBvh4 && !c->have_bvh4)
-    rc = scene_upload(c, scene, kNeedBvh);  // beyond the 4-wide format's limits: the binary walk takes the mesh
-  return rc;
 }
 
 static int impl_render(rtow_ctx *c, const rtow_scene_t *scene, const rtow_config_t *cfg, double *rgb_sums_host,
@@ -2703,291 +1629,6 @@ static int impl_render_rgb8(rtow_ctx *c, const rtow_scene_t *scene, const rtow_c
   if ((rc = mirror_dropped(c, nullptr))) return rc;
   HIPCHK(hipMemcpy(rgb8_host, c->out8.p, n, hipMemcpyDeviceToHost));
   return check_dropped(c, true);  // never RTOW_OK with samples dropped, with or without `stats`
-}
-
-// ---- in-place refit (rtow_scene_refit) -------------------------------------------------------------------------------
-// The same shape as the resident scene: counts and insertion order (checked before anything is written).
-static int refit_check_shape(const rtow_ctx *c, const rtow_scene_t *s) {
-  if (s->n_spheres != c->ds.n_sph || s->n_moving != c->ds.n_mov || s->n_triangles != c->ds.n_tri || s->n_prims != c->n_prims ||
-      s->n_materials != c->ds.n_mats)
-    return fail(RTOW_EINVAL, "rtow_scene_refit: the scene's counts (%d spheres, %d moving, %d triangles, %d materials) are not "
-                "the resident scene's (%d, %d, %d, %d): call rtow_scene_upload", s->n_spheres, s->n_moving, s->n_triangles,
-                s->n_materials, c->ds.n_sph, c->ds.n_mov, c->ds.n_tri, c->ds.n_mats);
-  const rtow_ctx::HostSceneCopy &h = c->host_scene;
-  const bool order = s->prim_kind && s->prim_index;
-  if (order != h.have_order ||
-      (order && (std::memcmp(s->prim_kind, h.pk.data(), (size_t)s->n_prims * 4) != 0 ||
-                 std::memcmp(s->prim_index, h.pi.data(), (size_t)s->n_prims * 4) != 0)))
-    return fail(RTOW_EINVAL, "rtow_scene_refit: prim_kind / prim_index differ from the resident scene's insertion order");
-  return RTOW_OK;
-}
-
-// What the first refit after an upload derives from the images as built, before they are overwritten: the slot maps of
-// the leaf-ordered images, the parent links of both trees, and the area sum of the binary BVH for the uploaded geometry.
-static int refit_prepare(rtow_ctx *c) {
-  rtow_ctx::Refit &r = c->rf;
-  const rtow::DevScene &ds = c->ds;
-  const int ns = ds.n_sph, nm = ds.n_mov, nt = ds.n_tri, np = c->n_prims;
-  int rc;
-  const bool bvh2 = (c->built & kNeedBvh) != 0;
-  r.slot2tri[0].clear();
-  r.slot2tri[1].clear();
-  if (bvh2 && ds.leaf_direct) {
-    if ((rc = match_slots(c, 1, r.slot2tri[0])) || (rc = r.map2.ensure((size_t)nt * 4))) return rc;
-    HIPCHK(hipMemcpy(r.map2.p, r.slot2tri[0].data(), (size_t)nt * 4, hipMemcpyHostToDevice));
-  }
-  if (c->have_bvh4) {
-    if ((rc = match_slots(c, 2, r.slot2tri[1])) || (rc = r.map4.ensure((size_t)nt * 4))) return rc;
-    HIPCHK(hipMemcpy(r.map4.p, r.slot2tri[1].data(), (size_t)nt * 4, hipMemcpyHostToDevice));
-  }
-  if ((rc = r.area.ensure(8 * sizeof(double))) || (rc = r.pbox.ensure((size_t)np * 48))) return rc;
-  if (bvh2) {
-    const int n = ds.n_nodes;
-    if ((rc = r.par2.ensure((size_t)n * 4)) || (rc = r.flags.ensure((size_t)n * 4)) || (rc = r.nbox2.ensure((size_t)n * 48)) ||
-        (rc = r.partials.ensure(((size_t)n + 255) / 256 * 8)))
-      return rc;
-    if (rtow::refit_bvh2_links(ds.blob, n, (int32_t *)r.par2.p, nullptr))
-      return fail(RTOW_EHIP, "refit link pass failed: %s", hipGetErrorString(hipGetLastError()));
-    // the upload's geometry: its records and shutter are still resident
-    if (rtow::refit_prim_boxes(ds.sph, ds.sph_r, ds.mov, ds.tri, ns, nm, nt, c->cam.t0, c->cam.t1, (double *)r.pbox.p, nullptr) ||
-        rtow::refit_bvh2(const_cast<unsigned char *>(ds.blob), n, ds.off_ids, np,
-                         ds.leaf_direct ? (const int32_t *)r.map2.p : nullptr, ns + nm,
-                         (const double *)r.pbox.p, (const int32_t *)r.par2.p, (uint32_t *)r.flags.p, (double *)r.nbox2.p,
-                         (double *)r.partials.p, /*emit=*/0, c->cam.origin, (double *)r.area.p, nullptr))
-      return fail(RTOW_EHIP, "refit area pass failed: %s", hipGetErrorString(hipGetLastError()));
-  }
-  if (c->have_bvh4) {
-    const int n4 = c->build_info.bvh4_nodes;
-    const uint32_t nb = ds.b4_half ? rtow::kBvh4HalfNodeBytes : rtow::kBvh4NodeBytes, co = ds.b4_half ? 48u : 96u;
-    if ((rc = r.par4.ensure((size_t)n4 * 4)) || (rc = r.need4.ensure((size_t)n4 * 4)) ||
-        (rc = r.flags.ensure((size_t)std::max(n4, ds.n_nodes) * 4)) || (rc = r.nbox4.ensure((size_t)n4 * 48)) ||
-        (rc = r.sbox4.ensure((size_t)n4 * 192)))
-      return rc;
-    if (rtow::refit_bvh4_links(ds.blob4, n4, nb, co, (int32_t *)r.par4.p, (int32_t *)r.need4.p, nullptr))
-      return fail(RTOW_EHIP, "refit 4-wide link pass failed: %s", hipGetErrorString(hipGetLastError()));
-  }
-  r.ready = true;
-  return RTOW_OK;
-}
-
-static int impl_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  int rc = validate_scene(s);
-  if (rc) return rc;
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  if ((rc = refit_check_shape(c, s))) return rc;
-  const double t_call = now_ms();
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipDeviceSynchronize());  // (earlier work may still read the images)
-  rtow_ctx::Refit &r = c->rf;
-  if (!r.ev[0])
-    for (hipEvent_t &e : r.ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(r.ev[0], nullptr));
-  c->have_scene = false;  // (until every image is consistent again: a failure below leaves no scene)
-  c->arena.used = 0;
-  struct ArenaScope {
-    explicit ArenaScope(PinnedArena *a) { g_arena = a; }
-    ~ArenaScope() { g_arena = nullptr; }
-  } arena_scope(&c->arena);
-  if (!r.ready && (rc = refit_prepare(c))) return rc;
-  rtow::DevScene &ds = c->ds;
-  const int ns = ds.n_sph, nm = ds.n_mov, nt = ds.n_tri, np = c->n_prims;
-  const bool bvh2 = (c->built & kNeedBvh) != 0, f32 = (c->built & kNeedF32) != 0;
-
-  // raw geometry, material indices and records through the pinned arena; the derived records on the device
-  std::vector<int32_t> pmat;
-  std::vector<rtow::DevMaterial> mats;
-  scene_materials(s, pmat, mats);
-  const size_t mats_n = mats.size() * sizeof(rtow::DevMaterial);
-  if ((rc = r.g_sph.ensure((size_t)ns * 32 + 8)) || (rc = r.g_mov.ensure((size_t)nm * 64 + 8)) ||
-      (rc = r.g_tri.ensure((size_t)nt * 72 + 8)))
-    return rc;
-  if ((ns && (rc = h2d_block(r.g_sph.p, s->sphere_geom, (size_t)ns * 32))) ||
-      (nm && (rc = h2d_block(r.g_mov.p, s->moving_geom, (size_t)nm * 64))) ||
-      (nt && (rc = h2d_block(r.g_tri.p, s->triangle_geom, (size_t)nt * 72))) ||
-      (rc = h2d_block(c->prim_mat.p, pmat.data(), (size_t)np * 4)) || (rc = h2d_block(c->mats.p, mats.data(), mats_n)))
-    return rc;
-  auto *sph = (double *)c->sph.p, *sph_r = (double *)c->sph_r.p, *mov = (double *)c->mov.p, *tri = (double *)c->tri.p;
-  const auto *prim_mat = (const int32_t *)c->prim_mat.p;
-  if (rtow::refit_records((const double *)r.g_sph.p, (const double *)r.g_mov.p, (const double *)r.g_tri.p, ns, nm, nt, sph,
-                          sph_r, mov, tri, c->have_tri16 ? (double *)c->tri16.p : nullptr, nullptr))
-    return fail(RTOW_EHIP, "refit record pass failed: %s", hipGetErrorString(hipGetLastError()));
-  if ((bvh2 || c->have_bvh4) &&
-      rtow::refit_prim_boxes(sph, sph_r, mov, tri, ns, nm, nt, s->camera.t0, s->camera.t1, (double *)r.pbox.p, nullptr))
-    return fail(RTOW_EHIP, "refit box pass failed: %s", hipGetErrorString(hipGetLastError()));
-  auto d2d = [](void *dst, const void *src, size_t n) {
-    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, nullptr) : hipSuccess;
-  };
-  const int32_t *map2 = ds.leaf_direct ? (const int32_t *)r.map2.p : nullptr;
-  const rtow_camera_t &cam = s->camera;
-
-  // binary BVH: records, boxes, planes (and the f32 build's copy of it)
-  if (bvh2) {
-    unsigned char *b = (unsigned char *)c->blob.p;
-    if (map2) {
-      if (rtow::refit_tri_section(nt, tri, prim_mat + ns + nm, map2, b, ds.off_tri, ds.off_pmat, 0, nullptr))
-        return fail(RTOW_EHIP, "refit record scatter failed: %s", hipGetErrorString(hipGetLastError()));
-    } else {
-      HIPCHK(d2d(b + ds.off_sph, sph, (size_t)ns * 32));
-      HIPCHK(d2d(b + ds.off_mov, mov, (size_t)nm * 64));
-      HIPCHK(d2d(b + ds.off_tri, tri, (size_t)nt * 96));
-      HIPCHK(d2d(b + ds.off_pmat, prim_mat, (size_t)np * 4));
-    }
-    HIPCHK(d2d(b + ds.off_mats, c->mats.p, mats_n));
-    if (rtow::refit_bvh2(b, ds.n_nodes, ds.off_ids, np, map2, ns + nm, (const double *)r.pbox.p, (const int32_t *)r.par2.p,
-                         (uint32_t *)r.flags.p, (double *)r.nbox2.p, (double *)r.partials.p, /*emit=*/1, cam.origin,
-                         (double *)r.area.p + 1, nullptr))
-      return fail(RTOW_EHIP, "refit BVH pass failed: %s", hipGetErrorString(hipGetLastError()));
-    if (f32) {  // the same layout as uploaded: nodes and ids, then the records
-      const rtow::DevScene &d32 = c->ds32;
-      unsigned char *b32 = (unsigned char *)c->blob32.p;
-      HIPCHK(d2d(b32, b, ds.off_sph));
-      HIPCHK(d2d(b32 + d32.off_sph, sph, (size_t)ns * 32));
-      HIPCHK(d2d(b32 + d32.off_mov, mov, (size_t)nm * 64));
-      if (!map2) HIPCHK(d2d(b32 + d32.off_pmat, prim_mat, (size_t)np * 4));
-      if (rtow::refit_tri_section(nt, tri, prim_mat + ns + nm, map2, b32, d32.off_tri, map2 ? d32.off_pmat : ~0u, 1, nullptr) ||
-          rtow::refit_spheres32(ns, nm, sph, mov, b32, d32.off_sph32, d32.off_mov32, nullptr))
-        return fail(RTOW_EHIP, "refit f32 record scatter failed: %s", hipGetErrorString(hipGetLastError()));
-      HIPCHK(d2d(b32 + d32.off_mats, c->mats.p, mats_n));
-    }
-  }
-
-  // 4-wide BVH: records in leaf order, boxes, planes in a frame from the new root box
-  if (c->have_bvh4) {
-    unsigned char *b4 = (unsigned char *)c->blob4.p;
-    const int n4 = c->build_info.bvh4_nodes;
-    const uint32_t nb = ds.b4_half ? rtow::kBvh4HalfNodeBytes : rtow::kBvh4NodeBytes, co = ds.b4_half ? 48u : 96u;
-    double *frame_dev = (double *)r.area.p + 2;
-    if (rtow::refit_tri_section(nt, tri, prim_mat + ns + nm, (const int32_t *)r.map4.p, b4, ds.b4_off_tri, ds.b4_off_pmat, 0,
-                                nullptr) ||
-        rtow::refit_bvh4(b4, n4, nb, co, (int)ds.b4_half, nt, (const int32_t *)r.map4.p, ns + nm, (const double *)r.pbox.p,
-                         (const int32_t *)r.par4.p, (const int32_t *)r.need4.p, (uint32_t *)r.flags.p, (double *)r.nbox4.p,
-                         (double *)r.sbox4.p, cam.origin, frame_dev, nullptr))
-      return fail(RTOW_EHIP, "refit 4-wide pass failed: %s", hipGetErrorString(hipGetLastError()));
-    HIPCHK(d2d(b4 + ds.b4_off_mats, c->mats.p, mats_n));
-    if (ds.b4_half) {  // the frame is a launch parameter: 48 bytes back
-      double frame[6];
-      HIPCHK(hipMemcpy(frame, frame_dev, sizeof frame, hipMemcpyDeviceToHost));
-      for (int k = 0; k < 3; ++k) {
-        ds.b4_c[k] = frame[k];
-        ds.b4_is[k] = (float)(1.0 / frame[3 + k]);
-      }
-    }
-  }
-
-  // the grid cannot be refit: rebuilt on the device, present exactly when a fresh upload would build it
-  rtow::GridImage gimg;
-  if ((c->built & kNeedGrid) && nt <= c->knobs.grid_max_tris) {
-    std::vector<double> sph_h((size_t)ns * 4), mov_n((size_t)nm * 8), tri_n((size_t)nt * 12);
-    for (int i = 0; i < ns; ++i) {  // (the fat-list format reads the spheres' r*r)
-      const double *g = s->sphere_geom + 4 * (size_t)i;
-      for (int k = 0; k < 3; ++k) sph_h[4 * (size_t)i + k] = g[k];
-      sph_h[4 * (size_t)i + 3] = std::copysign(g[3] * g[3], g[3]);
-    }
-    std::vector<unsigned char> mats_bytes(mats_n);
-    std::memcpy(mats_bytes.data(), mats.data(), mats_n);
-    if ((rc = grid_device_build(c, cam, ns, nm, nt, sph_h, mov_n, tri_n, pmat, mats_bytes, gimg))) return rc;
-  }
-  if (c->built & kNeedGrid) {
-    c->have_grid = gimg.ok;
-    c->grid_fat_stride = (gimg.ok && gimg.off_fat) ? gimg.fat_stride : 0u;
-    grid_header_resident(c, gimg);
-    c->gblob_bytes = gimg.ok ? (uint32_t)gimg.total_bytes : 0u;
-    ds.gblob = (const unsigned char *)c->gblob.p;
-    ds.gblob_bytes = c->gblob_bytes;
-    ds.g_off_cells = gimg.off_cells;
-    ds.g_off_ids = gimg.off_ids;
-    ds.g_off_sph = gimg.off_sph;
-    ds.g_off_mov = gimg.off_mov;
-    ds.g_off_tri = gimg.off_tri;
-    ds.g_off_pmat = gimg.off_pmat;
-    ds.g_off_mats = gimg.off_mats;
-  }
-  rtow::DevScene &d32 = c->ds32;
-  if (f32) {
-    d32.gblob = nullptr;
-    d32.gblob_bytes = 0;
-    if (gimg.ok) {
-      Image32 g32;
-      const size_t total = layout_image32(gimg.off_sph, ns, nm, nt, np, mats_n, g32);
-      if ((rc = c->gblob32.ensure(total))) return rc;
-      unsigned char *g = (unsigned char *)c->gblob32.p;
-      HIPCHK(hipMemsetAsync(g, 0, total, nullptr));
-      HIPCHK(d2d(g, c->gblob.p, gimg.off_sph));  // header, cells and ids
-      HIPCHK(d2d(g + g32.off_sph, sph, (size_t)ns * 32));
-      HIPCHK(d2d(g + g32.off_mov, mov, (size_t)nm * 64));
-      HIPCHK(d2d(g + g32.off_pmat, prim_mat, (size_t)np * 4));
-      HIPCHK(d2d(g + g32.off_mats, c->mats.p, mats_n));
-      if (rtow::refit_tri_section(nt, tri, nullptr, nullptr, g, g32.off_tri, ~0u, 1, nullptr) ||
-          rtow::refit_spheres32(ns, nm, sph, mov, g, g32.off_sph32, g32.off_mov32, nullptr))
-        return fail(RTOW_EHIP, "refit f32 grid records failed: %s", hipGetErrorString(hipGetLastError()));
-      d32.gblob = g;
-      d32.gblob_bytes = (uint32_t)total;
-      d32.g_off_sph = g32.off_sph;
-      d32.g_off_mov = g32.off_mov;
-      d32.g_off_tri = g32.off_tri;
-      d32.g_off_sph32 = g32.off_sph32;
-      d32.g_off_mov32 = g32.off_mov32;
-      d32.g_off_pmat = g32.off_pmat;
-      d32.g_off_mats = g32.off_mats;
-    }
-    d32.g_off_cells = ds.g_off_cells;
-    d32.g_off_ids = ds.g_off_ids;
-  }
-  for (int k = 0; k < 3; ++k) {  // (ds32 is ds with the f32 images' fields)
-    d32.b4_c[k] = ds.b4_c[k];
-    d32.b4_is[k] = ds.b4_is[k];
-  }
-  for (auto &o : c->occ) o[0] = o[1] = o[2] = o[3] = o[4] = 0;  // (image sizes decide the launch shapes)
-
-  // camera, host copy of the scene (the reference tree is rebuilt from it at its next use)
-  camera_record(cam, c->cam);
-  if ((rc = h2d_block(c->cam_dev.p, &c->cam, sizeof c->cam))) return rc;
-  if (f32) {
-    const double *cd = reinterpret_cast<const double *>(&c->cam);
-    float cam32[21];
-    for (int i = 0; i < 21; ++i) cam32[i] = (float)cd[i];
-    if ((rc = h2d_block(c->cam32_dev.p, cam32, sizeof cam32))) return rc;
-  }
-  rtow_ctx::HostSceneCopy &h = c->host_scene;
-  h.sg.assign(s->sphere_geom, s->sphere_geom + 4 * (size_t)ns);
-  h.mg.assign(s->moving_geom, s->moving_geom + 8 * (size_t)nm);
-  h.tg.assign(s->triangle_geom, s->triangle_geom + 9 * (size_t)nt);
-  h.cam = cam;
-  c->scene_gen++;  // (geometry may have moved into tiles that were empty)
-  c->have_rtree = false;
-  c->q_map_ok[1] = c->q_map_ok[2] = false;  // (rebuilt from the refit's slot maps; table 0 does not move)
-
-  HIPCHK(hipEventRecord(r.ev[1], nullptr));
-  HIPCHK(hipEventRecord(c->upload_ev, nullptr));  // ordering contract of rtow_scene_upload
-  c->have_scene = true;
-  r.refits++;
-  r.refit_ms = now_ms() - t_call;
-  return RTOW_OK;
-}
-
-int rtow_refit_info(rtow_ctx *c, rtow_refit_info_t *out) {
-  if (!c || !out) return fail(RTOW_EINVAL, "NULL argument");
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  std::memset(out, 0, sizeof *out);
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipDeviceSynchronize());
-  const rtow_ctx::Refit &r = c->rf;
-  out->refits = r.refits;
-  out->grid_resident = c->have_grid ? 1 : 0;
-  out->refit_ms = r.refit_ms;
-  out->bvh_area_ratio = (c->built & kNeedBvh) ? 1.0 : 0.0;
-  if (r.refits > 0) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, r.ev[0], r.ev[1]));
-    out->device_ms = ms;
-    if (c->built & kNeedBvh) {
-      double a[2];
-      HIPCHK(hipMemcpy(a, r.area.p, sizeof a, hipMemcpyDeviceToHost));
-      out->bvh_area_ratio = a[0] > 0.0 ? a[1] / a[0] : 1.0;  // (a tree without inner nodes cannot degrade)
-    }
-  }
-  return RTOW_OK;
 }
 
 // ---- the guarded entry points (see guarded() above) ----

@@ -30,12 +30,12 @@ Margins and bounds (each derived from the builders):
     (rtow_bvh.h build_bvh, rtow_build.hip k_bounds).  binary16 planes add one binary16 spacing at the plane (the
     directed rounding), one binary32 spacing in the frame (the device's intermediate __double2float_rd) and the
     rounding of `is` to binary32 (2^-24 of |h * is|), all in world units; saturated planes (|h| >= 65504) are skipped.
-  * records: bit for bit the scene's primitives with the precomputed terms of rtow_capi.cpp scene_upload (sphere
+  * records: bit for bit the scene's primitives with the precomputed terms of rtow_scene_records.h (sphere
     copysign(r*r, r); moving c1-c0, copysign(r*r, r), r; triangle e1 = b-a, e2 = c-a, n = e1 x e2 in its operation
     order; numpy rounds each operation like the host code built with -ffp-contract=off).  Leaf-ordered images (the
     host builder's triangle meshes, every 4-wide image) are matched as a multiset of (record bytes, material index).
   * binary32 images: the same prefix (nodes + ids, or header + cells + ids + fat lists) as their binary64 image, and
-    binary32 records = the binary64 records of the same slot rounded to nearest (rtow_capi.cpp make_image32).
+    binary32 records = the binary64 records of the same slot rounded to nearest (rtow_scene.cpp make_image32).
   * grid: every small primitive is listed in every cell its exact box, widened by MARGIN * S, touches (the host pads
     by 4e-6 * scale, rtow_grid.h grid_header); the others are in the large list; counts <= 255; fat entries match
     rtow_grid.h write_fat_entry bit for bit (k = (cx^2 + cy^2 + cz^2) - |r2|).
@@ -98,7 +98,7 @@ class Geometry:
         mats = [(m.kind, tuple(m.albedo), m.fuzz, m.ir) for m in (sc.materials[i] for i in range(sc.n_materials))]
         return cls(sph, mov, tri, np.concatenate([p.reshape(-1) for p in pm]), mats, tuple(sc.camera.origin))
 
-    # ---- the records scene_upload computes (rtow_capi.cpp), in its operation order -------------------------------
+    # ---- the records an upload computes (rtow_scene_records.h), in its operation order ---------------------------
     def sph_records(self):
         g = self.sph
         r = np.empty((self.ns, 4))

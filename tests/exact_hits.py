@@ -157,7 +157,7 @@ class Scene:
         g = self.tri
         e1, e2 = g[:, 3:6] - g[:, :3], g[:, 6:9] - g[:, :3]
         self.tri_n = np.stack([e1[:, 1] * e2[:, 2] - e2[:, 1] * e1[:, 2], e1[:, 2] * e2[:, 0] - e2[:, 2] * e1[:, 0],
-                               e1[:, 0] * e2[:, 1] - e2[:, 0] * e1[:, 1]], axis=1)  # the record's n (rtow_capi.cpp)
+                               e1[:, 0] * e2[:, 1] - e2[:, 0] * e1[:, 1]], axis=1)  # the record's n (rtow_scene_records.h)
 
     @classmethod
     def of(cls, v):

@@ -550,7 +550,7 @@ def test_half_node_walk_is_bit_identical_to_the_oracle(monkeypatch, tmp_path, sm
 
 
 def test_meshes_around_the_lds_limit_switch_node_format_and_stay_bit_identical(tmp_path):
-    """The node format of the 4-wide image is decided by its size (rtow_capi.cpp): meshes of 850 … 1,400 triangles —
+    """The node format of the 4-wide image is decided by its size (rtow_scene.cpp): meshes of 850 … 1,400 triangles —
     the first N of suzanne subdivided 2x2 — straddle the point where the binary32 image plus six stack entries per
     lane (round 5; eight before) stops fitting the 160 KB of LDS.  Each renders bit for bit like the oracle, whichever side it falls on, and
     both formats occur."""

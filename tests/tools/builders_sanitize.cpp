@@ -1,7 +1,8 @@
 // Host-side acceleration builders under AddressSanitizer / UBSan (CPU only; tests/test_host_builders.py).
 // The builders are header-only (csrc/rtow_bvh.h, rtow_bvh4.h, rtow_grid.h), so this harness compiles them
 // without HIP: SAH BVH2 -> threaded image, 4-wide image (triangle meshes), uniform grid with fat lists
-// (static and moving spheres).  Exit code 0 = every image built and validated.
+// (static and moving spheres), and the per-primitive records those builders read (csrc/rtow_scene_records.h).
+// Exit code 0 = every image built and validated.
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -14,6 +15,7 @@
 #include "../../raytracing-one-weekend_amd/csrc/rtow_bvh.h"
 #include "../../raytracing-one-weekend_amd/csrc/rtow_bvh4.h"
 #include "../../raytracing-one-weekend_amd/csrc/rtow_grid.h"
+#include "../../raytracing-one-weekend_amd/csrc/rtow_scene_records.h"
 
 static std::vector<double> load_tris(const char *path) {
   std::ifstream in(path);
@@ -157,6 +159,47 @@ int main(int argc, char **argv) {
         rtow::half_directed(-1e9, +1) != 0xfbff)
       return 97;
     std::printf("binary16 directed rounding: all %d finite values and the gaps between them\n", 2 * 0x7c00);
+  }
+  {  // the records of a small mixed scene (four spheres, one of them hollow: negative radius; two moving spheres; three
+     // triangles) against values computed inline: the sign-carrying r*r, c1 - c0, e1 x e2 in the record's operation order
+    const double sg[4][4] = {{0, -1000, 0, 1000}, {1.5, 0.25, -2, 0.5}, {-0.75, 1, 0.5, -0.45}, {3, 0.2, 1.1, 0.2}};
+    const double mg[2][8] = {{4, 0.2, 0.9, 4, 0.7, 0.9, 0.2, 0}, {-2.3, 0.3, 1.7, -2.1, 0.3, 1.2, -0.3, 0}};
+    const double tg[3][9] = {{0, 0, 0, 1, 0, 0, 0, 1, 0}, {0.1, 0.7, -0.3, 1.3, 0.2, 0.9, -0.4, 1.1, 0.6},
+                             {1e3, -2e3, 0.5, 1e3 + 0.25, -2e3, 0.75, 1e3, -2e3 + 0.125, 0.3}};
+    rtow::SceneRecords rec;
+    rtow::geometry_records(&sg[0][0], 4, &mg[0][0], 2, &tg[0][0], 3, rec);
+    if (rec.sph.size() != 16 || rec.sph_r.size() != 4 || rec.mov.size() != 16 || rec.tri.size() != 36) return 100;
+    for (int i = 0; i < 4; ++i) {
+      const double *g = sg[i], *d = &rec.sph[4 * i];
+      const double r2 = g[3] < 0 ? -(g[3] * g[3]) : g[3] * g[3];
+      if (d[0] != g[0] || d[1] != g[1] || d[2] != g[2] || d[3] != r2 || std::signbit(d[3]) != (g[3] < 0) || rec.sph_r[i] != g[3])
+        return 101;
+    }
+    for (int i = 0; i < 2; ++i) {
+      const double *g = mg[i], *d = &rec.mov[8 * i];
+      const double r2 = g[6] < 0 ? -(g[6] * g[6]) : g[6] * g[6];
+      for (int k = 0; k < 3; ++k)
+        if (d[k] != g[k] || d[3 + k] != g[3 + k] - g[k]) return 102;
+      if (d[6] != r2 || std::signbit(d[6]) != (g[6] < 0) || d[7] != g[6]) return 103;
+    }
+    for (int i = 0; i < 3; ++i) {
+      const double *g = tg[i], *d = &rec.tri[12 * i];
+      double e1[3], e2[3];
+      for (int k = 0; k < 3; ++k) {
+        e1[k] = g[3 + k] - g[k];
+        e2[k] = g[6 + k] - g[k];
+        if (d[k] != g[k] || d[3 + k] != e1[k] || d[6 + k] != e2[k]) return 104;
+      }
+      if (d[9] != e1[1] * e2[2] - e2[1] * e1[2] || d[10] != e1[2] * e2[0] - e2[2] * e1[0] ||
+          d[11] != e1[0] * e2[1] - e2[0] * e1[1])
+        return 105;
+    }
+    std::vector<double> sph, sph_r;  // the refit's routine alone: the same sphere records
+    rtow::sphere_records(&sg[0][0], 4, sph, sph_r);
+    if (sph != rec.sph || sph_r != rec.sph_r) return 106;
+    rtow::sphere_records(nullptr, 0, sph, sph_r);
+    if (!sph.empty() || !sph_r.empty()) return 107;
+    std::printf("scene records: 4 spheres (one hollow), 2 moving spheres, 3 triangles match the inline arithmetic\n");
   }
   // ---- sphere scenes: grid with fat lists, static and moving
   for (int moving = 0; moving < 2; ++moving) {

@@ -1,6 +1,6 @@
 // The host builders' scene images (csrc/rtow_bvh.h, rtow_bvh4.h, rtow_grid.h) for one scene, written to files, CPU
 // only (tests/test_accel_images_host.py checks them with tests/accel_images.py).  The per-primitive records, leaf
-// sizes and leaf order are those of rtow_capi.cpp scene_upload with the host builder; compile with -ffp-contract=off.
+// sizes and leaf order are those of rtow_scene.cpp's upload with the host builder; compile with -ffp-contract=off.
 //
 //   dump_host_images IN OUTDIR
 //   IN: int32 ns, nm, nt, n_mats; double cam[3]; double sphere[ns][4], moving[nm][8], triangle[nt][9];
@@ -17,6 +17,7 @@
 #include "../../raytracing-one-weekend_amd/csrc/rtow_bvh.h"
 #include "../../raytracing-one-weekend_amd/csrc/rtow_bvh4.h"
 #include "../../raytracing-one-weekend_amd/csrc/rtow_grid.h"
+#include "../../raytracing-one-weekend_amd/csrc/rtow_scene_records.h"
 
 static bool put(const std::string &path, const void *p, size_t n) {
   FILE *f = std::fopen(path.c_str(), "wb");
@@ -28,7 +29,7 @@ static bool put(const std::string &path, const void *p, size_t n) {
 static void frame(const rtow::Bvh4Image &img, unsigned char out[48]) {
   std::memset(out, 0, 48);
   float is[3];
-  for (int k = 0; k < 3; ++k) is[k] = (float)(1.0 / img.map_s[k]);  // rtow_capi.cpp: DevScene::b4_is
+  for (int k = 0; k < 3; ++k) is[k] = (float)(1.0 / img.map_s[k]);  // rtow_scene.cpp bvh4_set_frame: DevScene::b4_is
   const uint32_t half = img.half ? 1u : 0u;
   std::memcpy(out, img.map_c, 24);
   std::memcpy(out + 24, is, 12);
@@ -51,44 +52,17 @@ int main(int argc, char **argv) {
       std::fread(mats.data(), 1, mats.size(), f) != mats.size())
     return 5;
   std::fclose(f);
-  // records: rtow_capi.cpp scene_upload
-  std::vector<double> sph((size_t)ns * 4), sph_r(ns), mov((size_t)nm * 8), tri((size_t)nt * 12);
-  for (int i = 0; i < ns; ++i) {
-    const double *g = &gs[(size_t)i * 4];
-    for (int k = 0; k < 3; ++k) sph[(size_t)i * 4 + k] = g[k];
-    sph[(size_t)i * 4 + 3] = std::copysign(g[3] * g[3], g[3]);
-    sph_r[i] = g[3];
-  }
-  for (int i = 0; i < nm; ++i) {
-    const double *g = &gm[(size_t)i * 8];
-    double *d = &mov[(size_t)i * 8];
-    for (int k = 0; k < 3; ++k) {
-      d[k] = g[k];
-      d[3 + k] = g[3 + k] - g[k];
-    }
-    d[6] = std::copysign(g[6] * g[6], g[6]);
-    d[7] = g[6];
-  }
-  for (int i = 0; i < nt; ++i) {
-    const double *g = &gt[(size_t)i * 9];
-    double *d = &tri[(size_t)i * 12];
-    const double e1[3] = {g[3] - g[0], g[4] - g[1], g[5] - g[2]}, e2[3] = {g[6] - g[0], g[7] - g[1], g[8] - g[2]};
-    for (int k = 0; k < 3; ++k) {
-      d[k] = g[k];
-      d[3 + k] = e1[k];
-      d[6 + k] = e2[k];
-    }
-    d[9] = e1[1] * e2[2] - e2[1] * e1[2];
-    d[10] = e1[2] * e2[0] - e2[2] * e1[0];
-    d[11] = e1[0] * e2[1] - e2[0] * e1[1];
-  }
+  // records: those of a scene upload (csrc/rtow_scene_records.h)
+  rtow::SceneRecords rec;
+  rtow::geometry_records(gs.data(), ns, gm.data(), nm, gt.data(), nt, rec);
+  const std::vector<double> &sph = rec.sph, &sph_r = rec.sph_r, &mov = rec.mov, &tri = rec.tri;
   const std::string out = argv[2];
   const bool mesh = ns == 0 && nm == 0 && nt > 0;
   rtow::HostBvh bvh;
   rtow::build_bvh(sph, sph_r, mov, tri, bvh, mesh ? 2 : 4, mesh ? 1.5 : 0.0, 0.0, 1.0);
   const std::vector<int32_t> prim_order = bvh.prim;
   rtow::SceneImage img;
-  if (mesh) {  // leaf order (rtow_capi.cpp: triangle meshes with the host builder)
+  if (mesh) {  // leaf order (rtow_scene.cpp: triangle meshes with the host builder)
     std::vector<double> tri_img(tri.size());
     std::vector<int32_t> pmat_img(pmat.size());
     for (size_t sl = 0; sl < bvh.prim.size(); ++sl) {
