@@ -253,10 +253,11 @@ def test_fast_guides_against_strict(qctx, logged, name):
     """6a. The thresholds of test_gpu_parity.py::test_fast_build_within_tolerance on the eight guide values (depth divided
     by the strict depth where the pixel has hits): finite, mean |fast - strict| per sample <= 2e-3, more than 97 % of the
     pixels isclose(rtol=1e-9, atol=1e-12) in all eight.  Measured on one MI355X: mean 5.5e-14 (cover),
-    4.0e-14 (moving cover), 3.0e-17 (suzanne); close fraction 1.0000, 0.9993 (one pixel of 1,536) and 1.0000."""
+    4.0e-14 (moving cover), 3.0e-17 (suzanne); close fraction 1.0000, 0.9993 (one pixel of 1,536) and 1.0000.
+    Every pixel of the fast guides is held to its exact first hits in tests/test_gpu_exact_guides.py."""
     lg = logged[name]
     qctx.upload(lg.scene)
-    strict = guide_values(qctx.guides(lg.config(rtow.F64_STRICT))).reshape(-1, 8).copy()
+    strict =guide_values(qctx.guides(lg.config(rtow.F64_STRICT))).reshape(-1, 8).copy()
     fast = guide_values(qctx.guides(lg.config(rtow.F64_FAST))).reshape(-1, 8).copy()
     assert np.isfinite(fast).all() and np.isfinite(strict).all()
     scale = np.where(strict[:, 7] > 0, strict[:, 6], 1.0)
@@ -307,10 +308,8 @@ def test_fast_camera_rays_against_strict(qctx, logged):
         assert r <= K_CAMERA, (f, r)
 
 
-def test_after_a_refit(logged):
-    """7. The camera and the spheres moved with Context.refit: strict camera_rays and guides equal those of a fresh
-    context that uploaded the moved scene, and differ from the unmoved scene's."""
-    lg = logged["cover_moving"]
+def moved_cover():
+    """The moving cover with its spheres and its camera moved: what test_after_a_refit refits over the unmoved scene."""
     moved = cover_moving()
     sc = moved.c
     for i in range(1, sc.n_spheres):  # (sphere 0 is the ground)
@@ -322,6 +321,14 @@ def test_after_a_refit(logged):
     for k, d in enumerate((-0.75, 0.5, 0.25)):  # the camera, translated
         sc.camera.origin[k] += d
         sc.camera.lower_left_corner[k] += d
+    return moved
+
+
+def test_after_a_refit(logged):
+    """7. The camera and the spheres moved with Context.refit: strict camera_rays and guides equal those of a fresh
+    context that uploaded the moved scene, and differ from the unmoved scene's."""
+    lg = logged["cover_moving"]
+    moved = moved_cover()
     a, b = rtow.Context(0), rtow.Context(0)
     try:
         a.upload(lg.scene)
