@@ -8,7 +8,7 @@ sys.path.insert(0, str(ROOT / "raytracing-one-weekend_amd"))
 sys.path.insert(0, str(ROOT / "tests"))
 import torch
 import rtow
-from test_gpu_fuzz import random_scene
+from support_scenes import random_scene
 
 n = int(sys.argv[1]); nm = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 keep = []

@@ -142,7 +142,7 @@ class Cand:
 # ---- the scene ----------------------------------------------------------------------------------------------------
 class Scene:
     """Geometry per class and the insertion order: sph [n,4], mov [n,8], tri [n,9], kind / index / material per
-    inserted primitive (test_gpu_query.SceneView has these fields)."""
+    inserted primitive (support_scenes.SceneView has these fields)."""
 
     def __init__(self, sph, mov, tri, kind, index, prim_mat):
         self.sph = np.asarray(sph, np.float64).reshape(-1, 4)
@@ -165,7 +165,7 @@ class Scene:
 
     @classmethod
     def class_major(cls, sph, mov, tri, pmat):
-        """Insertion order = class-major order (rtow.Scene built by test_gpu_refit.scene_of); pmat class-major."""
+        """Insertion order = class-major order (rtow.Scene built by support_scenes.scene_of); pmat class-major."""
         ns, nm, nt = len(np.reshape(sph, (-1, 4))), len(np.reshape(mov, (-1, 8))), len(np.reshape(tri, (-1, 9)))
         kind = np.array([SPHERE] * ns + [MOVING] * nm + [TRIANGLE] * nt, np.int32)
         index = np.concatenate([np.arange(ns), np.arange(nm), np.arange(nt)]).astype(np.int32)

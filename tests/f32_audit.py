@@ -61,7 +61,8 @@ import exact_hits as ex
 import orc
 import rtow
 import sample_audit as sa
-from test_gpu_query import SceneView, log_rays, rays_of
+from support_oracle import log_rays, rays_of
+from support_scenes import SceneView, handmade_scene, suzanne
 
 U32 = ex.U32
 K_CAM = 6        # roundings on the camera's direction: llc (1), u = (j + ju) * inv (2), two products and sums, - from
@@ -575,7 +576,7 @@ def check_conditions(au):
 
 
 # ---- the frames ---------------------------------------------------------------------------------------------------------
-# 120 x 80 (suzanne 96 x 54), 4 samples, the seeds of test_gpu_query.LOGGED.  The cover scenes are seen from (2.6, 2.2, 2)
+# 120 x 80 (suzanne 96 x 54), 4 samples, the seeds of support_oracle.LOGGED.  The cover scenes are seen from (2.6, 2.2, 2)
 # towards (0.6, 0.2, 0.4), 40 degrees: from the scene's own camera at (13, 2, 3) the binary32 sphere test (h^2 and a c'
 # cancel to a 2500th of their size on an r = 0.2 sphere ten units away) leaves the hit point and the normal of the small
 # spheres too uncertain for layer S — 41 % and 37 % of the decided hits were left out there, against a cap of 10 %.
@@ -588,18 +589,12 @@ def _cover(moving):
 
 
 def _handmade():
-    from test_gpu_query import handmade_scene
     return with_camera(handmade_scene(), (6.0, 3.0, 5.0), (0.5, 0.8, -0.5), 40.0, 1.5)
-
-
-def _suzanne():
-    from conftest import GOLDEN
-    return rtow.HostScene.obj(GOLDEN / "suzanne.obj", 16 / 9)
 
 
 def rotated(scene, angle=0.6):
     """`scene` with every point turned about the vertical axis through the origin (a motion of
-    test_gpu_refit.motions, for the case after a refit)."""
+    support_scenes.motions, for the case after a refit)."""
     a, cam = arrays_of(scene), camera_of(scene)
     rot = np.array([[math.cos(angle), 0, math.sin(angle)], [0, 1, 0], [-math.sin(angle), 0, math.cos(angle)]])
     for k, w, cols in (("sphere_geom", 4, (0,)), ("moving_geom", 8, (0, 3)), ("triangle_geom", 9, (0, 3, 6))):
@@ -613,7 +608,7 @@ def rotated(scene, angle=0.6):
 FRAMES = {
     "cover_static": (lambda: _cover(False), 120, 80, 4, 21, False),
     "cover_moving": (lambda: _cover(True), 120, 80, 4, 22, False),
-    "suzanne": (_suzanne, 96, 54, 4, 23, False),
+    "suzanne": (suzanne, 96, 54, 4, 23, False),
     "cover0": (lambda: rtow.HostScene.cover(0, 1.5, True), 120, 80, 4, 21, True),
     "handmade": (_handmade, 120, 80, 4, 22, True),
     "cover_far": (lambda: translated(_cover(False), FAR_OFFSET), 120, 80, 4, 21, False),

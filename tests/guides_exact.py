@@ -15,7 +15,7 @@ no perturbation is added.  FAST: both rays are evaluations of
 with the same operands.  Uncontracted, the direction's terms pass u (1), u * horizontal (2), llc + (3), + v * vertical
 (4), - from (5) roundings and the origin's terms lens * px (1), cam_u * (2), + cam_v * (3), origin + (4); a contracted
 evaluation has fewer.  Each ray is therefore within 5 u S (direction) and 4 u S (origin) of the real value, S the sum of
-the magnitudes of the component's terms (test_gpu_guides.camera_ray_scales), and the two rays within
+the magnitudes of the component's terms (guides_ref.camera_ray_scales), and the two rays within
     K_CAM_D = 10 on the direction,  K_CAM_O = 8 on the origin
 of each other: twice the depth of one evaluation, because the exported ray is itself a rounded evaluation and not the
 real value (a count of 7 and 4 holds for one evaluation against the real value, with inv_wm1's own rounding counted;
@@ -93,7 +93,7 @@ class CheckError(AssertionError):
 
 
 def ray_magnitudes(s_org, s_dir, cam_origin):
-    """(omag, dmag) from test_gpu_guides.camera_ray_scales' (S_origin, S_direction): the lens offset's magnitude
+    """(omag, dmag) from guides_ref.camera_ray_scales' (S_origin, S_direction): the lens offset's magnitude
     S_origin - |camera origin| weighted LENS_W in both (the module docstring)."""
     extra = (LENS_W - 1.0) * (s_org - np.abs(np.asarray(cam_origin, np.float64))[None, :])
     assert np.all(extra >= 0)

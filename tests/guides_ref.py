@@ -1,57 +1,48 @@
-"""Helpers of test_gpu_guides.py: the oracle's ray log, bit comparison, the row partition, and the numpy statement of the
-guide fold (csrc/rtow_guides.h) — IEEE binary64, the written operand order, samples added in order from zero."""
+"""Helpers of the guide tests (test_gpu_guides.py, test_gpu_exact_guides.py, test_guides_exact_host.py): the logged
+depth-0 renders, the row partition, the numpy statement of the guide fold (csrc/rtow_guides.h) — IEEE binary64, the
+written operand order, samples added in order from zero — and what the exact checker (guides_exact.py) needs of a scene."""
 import ctypes as C
 
 import numpy as np
+import pytest
 
+import exact_hits as ex
+import guides_exact as gx
 import orc
 import rtow
-from conftest import GOLDEN
+from support_oracle import logged_render, primaries, sum_in_order
+from support_scenes import SceneView, cover, cover_moving, suzanne
 
-_pd = C.POINTER(C.c_double)
-
-
-def logged_render(scene, cfg, cap=200_000):
-    """(sums [pixels, 3], log [n, 12]) of a single-threaded oracle render; a log row is (pixel, sample, segment, o xyz,
-    d xyz, time, t_hit or inf, class index or -1)."""
-    buf = np.zeros((cap, 12))
-    L = orc.lib()
-    L.orc_set_raylog.argtypes = [_pd, C.c_uint64]
-    L.orc_set_raylog.restype = None
-    L.orc_raylog_count.restype = C.c_uint64
-    L.orc_set_raylog(buf.ctypes.data_as(_pd), cap)
-    try:
-        img, _ = orc.render(scene, cfg, orc.RNG_PHILOX, nthreads=1)
-        n = L.orc_raylog_count()
-    finally:
-        L.orc_set_raylog(None, 0)
-    assert 0 < n < cap
-    return img.reshape(-1, 3).copy(), buf[:n].copy()
+# name: (scene, width, height, spp, seed).  The cover camera has a lens (radius 0.05: the origins differ per sample), the
+# moving cover a shutter interval (the times differ per sample), suzanne is a triangle mesh.
+SCENES = {"cover": (cover, 48, 32, 4, 21), "cover_moving": (cover_moving, 48, 32, 4, 22), "suzanne": (suzanne, 48, 27, 4, 23)}
+CAP = 0.01  # the share of pixels that may hold an undecided sample
 
 
-def primaries(log):
-    """(rays, ids) of the log's segment-0 rows: the render's primaries and their Philox identities (pixel, sample)."""
-    p = log[log[:, 2] == 0]
-    r = np.empty(len(p), dtype=rtow.RAY_DTYPE)
-    r["origin"] = p[:, 3:6]
-    r["direction"] = p[:, 6:9]
-    r["time"] = p[:, 9]
-    r["tmax"] = np.inf
-    return r, p[:, 0:2].astype(np.uint32)
+class Logged:
+    """One oracle render at depth 0 with its log; `cfg` is the strict config the device calls take."""
+
+    def __init__(self, mk, w, h, spp, seed):
+        self.scene = mk() if callable(mk) else mk
+        self.w, self.h, self.spp, self.seed = w, h, spp, seed
+        self.cfg = self.config()
+        self.image, self.log = logged_render(self.scene, self.cfg)
+        assert len(self.log) == w * h * spp and np.all(self.log[:, 2] == 0)  # depth 0: every row is a primary
+        self.rays, self.ids = primaries(self.log)
+        # pixel-major, sample-minor
+        assert np.array_equal(self.ids[:, 0], np.repeat(np.arange(w * h), spp))
+        assert np.array_equal(self.ids[:, 1], np.tile(np.arange(spp), w * h))
+
+    def config(self, precision=rtow.F64_STRICT, kernel=rtow.KERNEL_AUTO, **kw):
+        kw.setdefault("nstreams", 1)
+        return rtow.make_config(self.w, self.h, kw.pop("spp", self.spp), max_child_rays=0, seed=self.seed,
+                                precision=precision, kernel=kernel, **kw)
 
 
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
-def sum_in_order(per_sample, spp):
-    """[pixels * spp, ...] -> [pixels, ...]: ((0 + c_0) + c_1) + ... over a pixel's samples."""
-    c = per_sample.reshape((-1, spp) + per_sample.shape[1:])
-    s = np.zeros((c.shape[0],) + per_sample.shape[1:])
-    for j in range(spp):
-        s = s + c[:, j]
-    return s
+@pytest.fixture(scope="module")
+def logged():
+    """name -> the three small oracle renders (computed once per importing module, never changed)."""
+    return {name: Logged(*v) for name, v in SCENES.items()}
 
 
 def row_list(cfg):
@@ -61,28 +52,6 @@ def row_list(cfg):
     rows = np.zeros(max(n, 1), dtype=np.int32)
     assert L.rtow_local_row_list(C.byref(cfg), rows.ctypes.data_as(C.POINTER(C.c_int32)), n) == n
     return rows[:n]
-
-
-def cover():
-    return rtow.HostScene.cover(11, 1.5, False)
-
-
-def cover_moving():
-    return rtow.HostScene.cover(11, 1.5, True)
-
-
-def suzanne():
-    return rtow.HostScene.obj(GOLDEN / "suzanne.obj", 16 / 9)
-
-
-def expected_kernel(scene, kernel):
-    """The render's fallbacks: BVH4 walks triangle meshes only; GRID falls back to BVH where there is no grid."""
-    mesh = scene.c.n_triangles == scene.c.n_prims
-    if kernel == rtow.KERNEL_BVH4 and not mesh:
-        return rtow.KERNEL_BVH
-    if kernel == rtow.KERNEL_GRID and mesh:
-        return None  # (a small mesh may or may not get a grid: either is the render's rule)
-    return kernel
 
 
 def attenuations(scene):
@@ -121,3 +90,57 @@ def guide_values(g):
     """[..., 8] float64 view of a GUIDE_DTYPE array: albedo, normal, depth, hits."""
     g = np.ascontiguousarray(g)
     return g.view(np.float64).reshape(g.shape + (8,))
+
+
+def camera_ray_scales(scene, rays):
+    """Per ray and component, the sum of the absolute values of the terms of Camera::get_ray: (S_origin [n, 3],
+    S_direction [n, 3], S_time [n]).  origin = o + (u rdx + v rdy); direction = llc + s horizontal + t vertical - origin;
+    time = jt (t1 - t0) + t0.  (rdx, rdy) and (s, t) are recovered from the strict ray by least squares."""
+    cam = scene.c.camera
+    o, cu, cv = (np.array(list(x)) for x in (cam.origin, cam.u, cam.v))
+    hor, ver, llc = (np.array(list(x)) for x in (cam.horizontal, cam.vertical, cam.lower_left_corner))
+    lens = (rays["origin"] - o) @ np.linalg.pinv(np.stack([cu, cv]))            # [n, 2] (rdx, rdy)
+    s_off = np.abs(lens[:, 0:1] * cu) + np.abs(lens[:, 1:2] * cv)
+    s_org = np.abs(o) + s_off
+    st = (rays["direction"] + rays["origin"] - llc) @ np.linalg.pinv(np.stack([hor, ver]))
+    s_dir = np.abs(llc) + np.abs(st[:, 0:1] * hor) + np.abs(st[:, 1:2] * ver) + s_org
+    s_time = np.abs(rays["time"] - cam.t0) + abs(cam.t0)
+    return s_org, s_dir, s_time
+
+
+def moved_cover():
+    """The moving cover with its spheres and its camera moved: what the refit tests refit over the unmoved scene."""
+    moved = cover_moving()
+    sc = moved.c
+    for i in range(1, sc.n_spheres):  # (sphere 0 is the ground)
+        sc.sphere_geom[4 * i + 0] += 0.05 * ((i % 5) - 2)
+        sc.sphere_geom[4 * i + 1] += 0.02 * (i % 3)
+    for i in range(sc.n_moving):
+        sc.moving_geom[8 * i + 1] += 0.03 * (i % 4)
+        sc.moving_geom[8 * i + 4] += 0.03 * (i % 4) + 0.1
+    for k, d in enumerate((-0.75, 0.5, 0.25)):  # the camera, translated
+        sc.camera.origin[k] += d
+        sc.camera.lower_left_corner[k] += d
+    return moved
+
+
+class Parts:
+    """What the exact checker needs of one host scene: its exact_hits.Scene and its attenuation table."""
+
+    def __init__(self, scene):
+        self.scene = scene
+        self.exact = ex.Scene.of(SceneView(scene))
+        self.att = attenuations(scene)
+
+    def reference(self, rays, ids, spp, build, unit_cut=False):
+        if build == gx.STRICT:
+            return gx.GuideReference(rays, ids, self.exact, self.att, spp, gx.STRICT)
+        s_org, s_dir, s_time = camera_ray_scales(self.scene, rays)
+        omag, dmag = gx.ray_magnitudes(s_org, s_dir, list(self.scene.c.camera.origin))
+        return gx.GuideReference(rays, ids, self.exact, self.att, spp, gx.FAST, unit_cut and len(self.exact.tri) > 0,
+                                 omag, dmag, s_time)
+
+
+def within_cap(what, stats):
+    print(gx.report(str(what), stats))
+    assert stats["undecided_pixels"] <= CAP * stats["pixels"], (what, stats)

@@ -3,7 +3,7 @@ distance (numpy and the standard library, no GPU).
 
 Records.  The device holds, per class-major primitive: sphere (c, copysign(r^2, r)), moving sphere (c0, c1 - c0,
 copysign(r^2, r), r), triangle (a, e1 = B - A, e2 = C - A, n = e1 x e2) — each an IEEE operation of the host's
-(csrc/rtow_scene_records.h, no contraction).  `records(view)` rebuilds them from a test_gpu_query.SceneView.
+(csrc/rtow_scene_records.h, no contraction).  `records(view)` rebuilds them from a support_scenes.SceneView.
 
 Mirror.  `sphere_point` / `triangle_point` are csrc/rtow_pointq.h point_sphere / point_triangle written in numpy in the
 same operation order (binary64, no contraction): the strict build's dist and point equal them bit for bit.  The radius
@@ -106,7 +106,7 @@ def make_records(sph_geom, mov_geom, tri_geom, kind=None, index=None):
 
 
 def records(view):
-    """Records of a test_gpu_query.SceneView."""
+    """Records of a support_scenes.SceneView."""
     return make_records(view.sph, view.mov, view.tri, view.kind, view.index)
 
 

@@ -40,8 +40,9 @@ import numpy as np
 import conftest  # noqa: F401  (the import paths of the package and the tests)
 import accel_images as ai
 import rtow
+from support_scenes import random_scene, suzanne_tris, to_scene
+from support_tables import BUILDERS
 
-BUILDERS = {"host": rtow.BUILDER_HOST_SAH, "device": rtow.BUILDER_DEVICE_LBVH}
 KNOBS = {"RTOW_NO_LEAF_ORDER": "1", "RTOW_NO_BVH4": "1", "RTOW_BVH_LEAF": "5"}
 BUILD_INFO_INTS = ("builder", "bvh_nodes", "bvh_image_bytes", "grid_image_bytes", "bvh4_nodes", "bvh4_image_bytes",
                    "bvh4_node_bytes")
@@ -50,8 +51,6 @@ RENDERS = {"render_grid": dict(kernel=rtow.KERNEL_GRID), "render_bvh": dict(kern
 
 
 def _mixed():
-    from test_gpu_fuzz import random_scene
-
     keep = []
     G = ai.Geometry.of_scene(random_scene(57, 23, 6, 10, keep))
     G.sph[3, 3] = -G.sph[3, 3]  # a hollow sphere
@@ -59,8 +58,6 @@ def _mixed():
 
 
 def _spheres_fat():
-    from test_gpu_fuzz import random_scene
-
     keep = []
     return ai.Geometry.of_scene(random_scene(47, 31, 0, 0, keep))
 
@@ -82,15 +79,9 @@ def _spheres_nogrid():
     return ai.sphere_geometry(geom)
 
 
-def _suzanne():
-    from test_gpu_accel_images import _suzanne_tris
-
-    return ai.mesh_geometry(_suzanne_tris(1))
-
-
 SCENES = {
     "mixed": _mixed, "spheres_fat": _spheres_fat, "spheres_plain": _spheres_plain, "spheres_nogrid": _spheres_nogrid,
-    "suzanne": _suzanne, "mesh1400": lambda: ai.mesh_geometry(ai.unit_mesh(1400, 5)),
+    "suzanne": lambda: ai.mesh_geometry(suzanne_tris(1)), "mesh1400": lambda: ai.mesh_geometry(ai.unit_mesh(1400, 5)),
     "tri1": lambda: ai.mesh_geometry(ai.unit_mesh(1, 1)), "tri2": lambda: ai.mesh_geometry(ai.unit_mesh(2, 2)),
 }
 
@@ -136,8 +127,6 @@ def _check_branch(name, ctx, G):
 
 def record_scene(name):
     """{"<name>/<builder>/<route>": {"images": {which: sha256}, "build_info": {field: int}}} for one scene."""
-    from test_gpu_accel_images import to_scene
-
     out = {}
     keep = []
     G = SCENES[name]()

@@ -4,14 +4,14 @@ image with both node formats and the uniform grid of rtow_bvh.h / rtow_bvh4.h / 
 corrupted copies of them.  tests/test_gpu_accel_images.py runs the same checks on the images resident on the GPU."""
 import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import accel_images as ai
 import rtow
-from conftest import GOLDEN, REPO
+from conftest import REPO
+from support_scenes import suzanne_tris
 
 
 @pytest.fixture(scope="module")
@@ -40,14 +40,6 @@ def host_images(exe, G, tmp_path):
     return {0: rd("image0.bin"), 1: rd("image1.bin")}, (rd("image4.bin"), rd("image5.bin")), (rd("image4h.bin"), rd("image5h.bin"))
 
 
-def _suzanne():
-    sys.path.insert(0, str(REPO / "scripts"))
-    import make_mesh
-
-    v, f = make_mesh.load(GOLDEN / "suzanne.obj")
-    return np.stack([v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]], axis=1)
-
-
 def _check_all(exe, G, tmp_path):
     images, (b4, f4), (b4h, f4h) = host_images(exe, G, tmp_path)
     info = ai.check_resident(images, G)
@@ -69,7 +61,7 @@ def test_host_images_of_the_cover_scene(dumper, tmp_path, moving):
 
 @pytest.mark.parametrize("name", ["suzanne"] + list(ai.edge_meshes()))
 def test_host_images_of_meshes(dumper, tmp_path, name):
-    G = ai.mesh_geometry(_suzanne() if name == "suzanne" else ai.edge_meshes()[name])
+    G = ai.mesh_geometry(suzanne_tris() if name == "suzanne" else ai.edge_meshes()[name])
     _check_all(dumper, G, tmp_path)
 
 
@@ -80,7 +72,7 @@ def test_host_images_of_sphere_edge_scenes(dumper, tmp_path, name):
 
 def test_the_checker_rejects_corrupted_host_images(dumper, tmp_path):
     """Each corruption of a real image fails for the reason it names (the GPU module does the same on device images)."""
-    G = ai.mesh_geometry(_suzanne())
+    G = ai.mesh_geometry(suzanne_tris())
     images, (b4, f4), (b4h, f4h) = host_images(dumper, G, tmp_path)
     bad, i = ai.bvh2_plane_inward(images[0], G)
     with pytest.raises(ai.ImageError, match=rf"node {i} .*lo plane of axis 0 .* does not enclose"):

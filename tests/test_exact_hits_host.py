@@ -11,10 +11,10 @@ import accel_images as ai
 import exact_hits as ex
 import first_hits_ref as fr
 import rtow
-import test_gpu_exact_hits as gx
-from test_gpu_query import LOGGED, SceneView, brute_force, handmade_rays, handmade_scene, log_rays, rays_of
-
-SHARE = gx.SHARE
+import exact_cases as gx
+from exact_cases import SHARE
+from support_oracle import LOGGED, brute_force, log_rays, rays_of
+from support_scenes import SceneView, handmade_rays, handmade_scene
 
 
 def _scene(sph=(), mov=(), tri=()):

@@ -1,6 +1,6 @@
 """First-k-hits queries without a GPU: the exports and constants, the argument checks that need no device, and the
 reference of tests/first_hits_ref.py — its vectorised form pinned bit for bit to the oracle's two hit tests, and its
-first entry to the closest-hit brute force of tests/test_gpu_query.py."""
+first entry to the closest-hit brute force of tests/support_oracle.py."""
 import ctypes as C
 import math
 from types import SimpleNamespace
@@ -10,7 +10,8 @@ import numpy as np
 import first_hits_ref as fr
 import orc
 import rtow
-from test_gpu_query import SceneView, brute_force, handmade_rays, handmade_scene
+from support_oracle import brute_force
+from support_scenes import SceneView, handmade_rays, handmade_scene
 
 PAIRS = 10_000
 
@@ -199,7 +200,7 @@ def test_vectorised_reference_equals_the_oracle_loop_on_the_handmade_scene():
 
 
 def test_first_entry_is_the_closest_hit_brute_force():
-    """Entry 0 equals the hittable-list brute force of test_gpu_query.py in every field (no ties for the first place
+    """Entry 0 equals the hittable-list brute force of support_oracle.py in every field (no ties for the first place
     among these rays), and every list is ascending in (t, insertion index) with distinct primitives."""
     scene = handmade_scene()
     view = SceneView(scene)

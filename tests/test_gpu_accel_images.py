@@ -5,57 +5,18 @@ every primitive that touches it, and every record must be the scene's primitive 
 cannot depend on the tree for ANY ray, not only for the rays a camera happens to send.  Each scene is uploaded with
 both builders (rtow_scene_upload builds every image), and every resident image (0-5 of rtow_debug_image) is checked.
 """
-import ctypes as C
-import sys
-
-import numpy as np
 import pytest
 
 import accel_images as ai
 import rtow
-from conftest import GOLDEN, REPO
+from conftest import GOLDEN
+from support_fixtures import mctx  # noqa: F401
+from support_scenes import random_scene, resident_images, suzanne_tris, to_scene
+from support_tables import BUILDERS as BUILDER_OF
 
 pytestmark = pytest.mark.gpu
 
-BUILDERS = [rtow.BUILDER_HOST_SAH, rtow.BUILDER_DEVICE_LBVH]
-
-
-def _make_mesh():
-    sys.path.insert(0, str(REPO / "scripts"))
-    import make_mesh
-
-    return make_mesh
-
-
-def _suzanne_tris(n_sub=1):
-    mm = _make_mesh()
-    v, f = mm.load(GOLDEN / "suzanne.obj")
-    return mm.subdivide(v, f, n_sub) if n_sub > 1 else np.stack([v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]], axis=1)
-
-
-def to_scene(G, keep):
-    """An rtow.Scene with G's exact binary64 coordinates and the cover scene's camera (shutter [0, 1])."""
-    base = rtow.HostScene.cover(0, 1.5, False)
-    sc = rtow.Scene()
-    sc.camera = base.c.camera
-    arrs = [np.ascontiguousarray(a, np.float64) for a in (G.sph, G.mov, G.tri)]
-    pm = [np.ascontiguousarray(G.pmat[a:b], np.int32) for a, b in ((0, G.ns), (G.ns, G.ns + G.nm), (G.ns + G.nm, G.np))]
-    mats = (rtow.Material * len(G.mats))()
-    for i, (kind, albedo, fuzz, ir) in enumerate(G.mats):
-        mats[i].kind, mats[i].fuzz, mats[i].ir = kind, fuzz, ir
-        mats[i].albedo = (C.c_double * 3)(*albedo)
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    sc.n_spheres, sc.sphere_geom, sc.sphere_mat = G.ns, arrs[0].ctypes.data_as(dp), pm[0].ctypes.data_as(ip)
-    sc.n_moving, sc.moving_geom, sc.moving_mat = G.nm, arrs[1].ctypes.data_as(dp), pm[1].ctypes.data_as(ip)
-    sc.n_triangles, sc.triangle_geom, sc.triangle_mat = G.nt, arrs[2].ctypes.data_as(dp), pm[2].ctypes.data_as(ip)
-    sc.n_materials, sc.materials, sc.n_prims = len(G.mats), mats, G.np
-    keep.extend([base, arrs, pm, mats])
-    G.cam = np.array(sc.camera.origin[:])
-    return sc
-
-
-def resident_images(ctx):
-    return {w: ctx.debug_image(w) for w in range(6)}
+BUILDERS = list(BUILDER_OF.values())  # (the ids below are its names)
 
 
 def upload_and_check(ctx, sc, G, builder, label=""):
@@ -80,13 +41,6 @@ def upload_and_check(ctx, sc, G, builder, label=""):
     return im, bi
 
 
-@pytest.fixture(scope="module")
-def mctx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
-
-
 # ---- sphere and mixed scenes ---------------------------------------------------------------------------------------
 def _cover(moving, keep):
     hs = rtow.HostScene.cover(11, 1.5, moving)
@@ -95,8 +49,6 @@ def _cover(moving, keep):
 
 
 def _fuzz(shape, keep):
-    from test_gpu_fuzz import random_scene
-
     return random_scene(17 + sum(shape), *shape, keep)
 
 
@@ -143,7 +95,7 @@ def test_suzanne_images_enclose_their_geometry(mctx, builder):
 @pytest.mark.parametrize("builder", BUILDERS, ids=["host", "device"])
 def test_meshes_around_the_lds_limit_images_enclose_their_geometry(mctx, builder):
     """The first 850 and 1,400 triangles of suzanne subdivided 2x2 (test_gpu_parity: both 4-wide node formats)."""
-    tris = _suzanne_tris(2)
+    tris = suzanne_tris(2)
     formats = set()
     for n in (850, 1400):
         keep = []
@@ -166,7 +118,7 @@ def test_edge_mesh_images_enclose_their_geometry(mctx, name, builder):
 @pytest.fixture(scope="module")
 def mesh100k():
     keep = []
-    G = ai.mesh_geometry(_suzanne_tris(10))
+    G = ai.mesh_geometry(suzanne_tris(10))
     assert G.nt == 96800
     return to_scene(G, keep), G, keep
 
@@ -237,7 +189,7 @@ def test_the_checker_rejects_corrupted_device_images(mctx):
     mctx.set_builder(rtow.BUILDER_DEVICE_LBVH)
     mctx.upload(hs.c)
     im = resident_images(mctx)
-    half_G = ai.mesh_geometry(_suzanne_tris(2)[:1400])
+    half_G = ai.mesh_geometry(suzanne_tris(2)[:1400])
     sc = to_scene(half_G, keep)
     mctx.upload(sc)
     imh = resident_images(mctx)

@@ -15,21 +15,16 @@ gives the reference-tree image bit for bit (tests/test_oracle_units.py, and re-c
 low-spp strip of every config).  configs[2] (500 spp over 8 GPUs + gather) is covered by the 500-spp
 strips here plus tests/test_gpu_multi_rank_bench.py (bench.py's own N-rank path, kernel behind each rank).
 """
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import orc
 import rtow
-from conftest import GOLDEN, REPO
+from conftest import GOLDEN
+from support_oracle import to8
+from support_scenes import write_mesh_obj
 
 pytestmark = pytest.mark.gpu
-
-
-def to8(img, spp):
-    return (256 * np.clip(np.sqrt(img / spp), 0.0, 0.999)).astype(np.int32)
 
 
 def check_fast(img, ref, spp, what):
@@ -43,10 +38,7 @@ def check_fast(img, ref, spp, what):
 
 @pytest.fixture(scope="module")
 def mesh_obj(tmp_path_factory):
-    obj = tmp_path_factory.mktemp("mesh") / "mesh100k.obj"
-    subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(obj), "10"], check=True,
-                   capture_output=True)
-    return obj
+    return write_mesh_obj(tmp_path_factory.mktemp("mesh"))
 
 
 # config: (W, H, spp, nstreams, bounces, strip height, strips to check)

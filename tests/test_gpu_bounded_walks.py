@@ -15,13 +15,14 @@ import pytest
 
 import rtow
 from conftest import GOLDEN
-from test_gpu_first_hits import seeded_finite_tmax
-from test_gpu_query import LOGGED, handmade_rays, handmade_scene, log_rays, rays_of
+from support_oracle import LOGGED, log_rays, rays_of, seeded_finite_tmax
+from support_scenes import handmade_rays, handmade_scene
+from support_tables import KERNELS as ALL_KERNELS
 
 pytestmark = pytest.mark.gpu
 
 S = rtow.F64_STRICT
-KERNELS = {"bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4}
+KERNELS = {k: ALL_KERNELS[k] for k in ("bvh", "grid", "bvh4")}
 QUERIES = ("occluded", "first_hits_1", "first_hits_8")
 N_LOGGED = 4099  # 64 waves and a partial one
 GOLD = json.loads((GOLDEN / "bounded_walk_counters.json").read_text())

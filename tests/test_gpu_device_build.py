@@ -7,7 +7,6 @@ validated on the device at upload (rtow_scene_upload fails otherwise).
 """
 import ctypes as C
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,7 +14,7 @@ import pytest
 import orc
 import rtow
 from conftest import GOLDEN, REPO
-from test_gpu_parity import CASES, _random_sphere_scene, make_scene
+from support_scenes import CASES, make_scene, random_sphere_scene, suzanne_tris, write_mesh_obj
 
 pytestmark = pytest.mark.gpu
 
@@ -62,10 +61,7 @@ def test_device_and_host_trees_give_the_same_image(ctx, dctx, name, w, spp):
 
 def test_device_build_mesh100k_global_image_path(dctx, tmp_path):
     """96,800 triangles (BASELINE config C5's shape): image in global memory, tree from the GPU."""
-    obj = tmp_path / "mesh.obj"
-    subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(obj), "10"], check=True,
-                   capture_output=True)
-    scene = rtow.HostScene.obj(obj, 16 / 9)
+    scene = rtow.HostScene.obj(write_mesh_obj(tmp_path), 16 / 9)
     cfg = rtow.make_config(96, 54, 2, 1, 20, seed=13, precision=rtow.F64_STRICT, kernel=rtow.KERNEL_BVH)
     img, st = dctx.render(scene, cfg)
     bi = dctx.build_info()
@@ -131,7 +127,7 @@ def test_device_build_equal_morton_keys(dctx):
 
 def test_device_build_overlapping_spheres_and_hollow(dctx):
     for hollow in (False, True):
-        sc, keep = _random_sphere_scene(hollow=hollow)
+        sc, keep = random_sphere_scene(hollow=hollow)
         imgs = []
         for kernel in (rtow.KERNEL_BRUTE, rtow.KERNEL_BVH):
             cfg = rtow.make_config(80, 40, 6, 2, 30, seed=9, precision=rtow.F64_STRICT, kernel=kernel)
@@ -177,7 +173,7 @@ def test_device_built_grid_other_scenes(ctx, dctx):
     import ctypes as C
 
     cases = [rtow.HostScene.obj(GOLDEN / "suzanne.obj", 16 / 9), rtow.HostScene.cover(3, 1.5, True)]
-    sc, keep = _random_sphere_scene(hollow=True)
+    sc, keep = random_sphere_scene(hollow=True)
     cases.append(sc)
     for scene in cases:
         ctx.set_builder(rtow.BUILDER_HOST_SAH)
@@ -229,25 +225,19 @@ def test_device_built_bvh4_image_strict_is_bit_identical_to_oracle(dctx, tmp_pat
     GPU.  Strict build against the oracle, bit for bit: suzanne (binary32 nodes, staged in LDS whole), suzanne
     subdivided 2x2 as it is and shrunk and moved off the origin (binary16 nodes in the mesh's own frame), the
     96,800-triangle mesh of BASELINE configs[4]; trip form and state-machine form of the kernel."""
-    sys.path.insert(0, str(REPO / "scripts"))
-    import make_mesh
-
     if sm:
         monkeypatch.setenv("RTOW_BVH4_SM", "1")
     c = rtow.Context(0)
     c.set_builder(rtow.BUILDER_DEVICE_LBVH)
     try:
-        v, f = make_mesh.load(GOLDEN / "suzanne.obj")
         cases = [("suzanne", GOLDEN / "suzanne.obj", 128, 968)]
-        tris = make_mesh.subdivide(v, f, 2)
+        tris = suzanne_tris(2)
         _write_obj(tmp_path / "m2.obj", tris)
         cases.append(("2x2", tmp_path / "m2.obj", 64, 3872))
         _write_obj(tmp_path / "m2off.obj", tris * 0.55 + np.array((0.3125, -0.11, 0.27)))
         cases.append(("2x2 off-origin", tmp_path / "m2off.obj", 64, 3872))
         if not sm:
-            subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(tmp_path / "m10.obj"), "10"],
-                           check=True, capture_output=True)
-            cases.append(("10x10", tmp_path / "m10.obj", 64, 96800))
+            cases.append(("10x10", write_mesh_obj(tmp_path), 64, 96800))
         for k, (name, obj, node_bytes, nt) in enumerate(cases):
             scene = rtow.HostScene.obj(obj, 16 / 9)
             assert scene.c.n_triangles == nt
@@ -282,11 +272,7 @@ def test_device_trees_radix_ploc_sah_give_the_same_image_and_the_sah_tree_is_the
     Karras' radix tree (pass 3, RTOW_PLOC_RADIUS=0: rounds 1-4).  Same image bit for bit (the
     closest hit is tree-independent), fewer node tests per segment, and the device-side validation has counted every
     triangle record in exactly one leaf (rtow_scene_upload fails otherwise)."""
-    sys.path.insert(0, str(REPO / "scripts"))
-    import make_mesh
-
-    v, f = make_mesh.load(GOLDEN / "suzanne.obj")
-    _write_obj(tmp_path / "m3.obj", make_mesh.subdivide(v, f, 3))
+    _write_obj(tmp_path / "m3.obj", suzanne_tris(3))
     for obj, nt in ((GOLDEN / "suzanne.obj", 968), (tmp_path / "m3.obj", 8712)):
         scene = rtow.HostScene.obj(obj, 16 / 9)
         out = {}
@@ -328,9 +314,7 @@ def test_auto_builder_takes_the_device_for_big_meshes(tmp_path):
     triangle tests per segment) in a third of its time — and everything else on the host (a small mesh: the device's
     two dozen launches cost more than the host's 0.4 ms; sphere scenes: the grid); rtow_scene_upload, which knows no
     config, takes the host builder.  Same image either way."""
-    subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(tmp_path / "m5.obj"), "5"], check=True,
-                   capture_output=True)
-    mesh = rtow.HostScene.obj(tmp_path / "m5.obj", 16 / 9)  # 24,200 triangles
+    mesh = rtow.HostScene.obj(write_mesh_obj(tmp_path, 5), 16 / 9)  # 24,200 triangles
     small = rtow.HostScene.obj(GOLDEN / "suzanne.obj", 16 / 9)
     cover = rtow.HostScene.cover(11, 1.5, False)
     c = rtow.Context(0)
@@ -362,11 +346,7 @@ def test_auto_builder_takes_the_device_for_big_meshes(tmp_path):
 def test_device_built_bvh4_tiny_meshes(dctx, tmp_path, n):
     """One triangle (no inner node of the radix tree), a mesh that is ONE leaf (<= 2 triangles), just above, and
     small ones: the first n triangles of suzanne, strict build against the oracle."""
-    sys.path.insert(0, str(REPO / "scripts"))
-    import make_mesh
-
-    v, f = make_mesh.load(GOLDEN / "suzanne.obj")
-    tris = make_mesh.subdivide(v, f, 1)[100:100 + n]
+    tris = suzanne_tris(1)[100:100 + n]
     _write_obj(tmp_path / "t.obj", tris)
     scene = rtow.HostScene.obj(tmp_path / "t.obj", 16 / 9)
     cfg = rtow.make_config(64, 36, 4, 2, 10, seed=n, precision=rtow.F64_STRICT, kernel=rtow.KERNEL_BVH4)
@@ -380,11 +360,7 @@ def test_device_built_bvh4_coincident_triangles(dctx, tmp_path):
     """Forty copies of one triangle and forty of another: equal Morton keys, the radix tree is decided by the index
     tie-break alone and is a chain — the deepest 4-wide tree per triangle there is.  Against the binary walk of the
     same scene (exact-t ties between coincident triangles are tree-dependent, so not against the oracle)."""
-    sys.path.insert(0, str(REPO / "scripts"))
-    import make_mesh
-
-    v, f = make_mesh.load(GOLDEN / "suzanne.obj")
-    t = make_mesh.subdivide(v, f, 1)
+    t = suzanne_tris(1)
     tris = np.concatenate([np.repeat(t[10:11], 40, axis=0), np.repeat(t[500:501], 40, axis=0), t[:60]])
     _write_obj(tmp_path / "c.obj", tris)
     scene = rtow.HostScene.obj(tmp_path / "c.obj", 16 / 9)
@@ -398,9 +374,7 @@ def test_device_built_bvh4_coincident_triangles(dctx, tmp_path):
 
 
 def test_device_builder_beyond_the_bvh4_limits_takes_the_binary_walk(dctx, tmp_path):
-    subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(tmp_path / "m17.obj"), "17"], check=True,
-                   capture_output=True)
-    big = rtow.HostScene.obj(tmp_path / "m17.obj", 16 / 9)
+    big = rtow.HostScene.obj(write_mesh_obj(tmp_path, 17), 16 / 9)
     cfg = rtow.make_config(96, 54, 8, 2, 20, seed=13, precision=rtow.F64_FAST, kernel=rtow.KERNEL_BVH4)
     a, st = dctx.render(big, cfg)
     assert st.kernel_used == rtow.KERNEL_BVH and np.isfinite(a).all() and dctx.build_info().bvh4_nodes == 0

@@ -5,49 +5,25 @@ Every call under test is checked against the fast (strict) camera_rays of the SA
 hit gives the material's attenuation, the unit normal, the depth or the sky, and a decided pixel's eight sums must be
 the in-order sums of those within the derived bounds (hits and an all-hit albedo bit for bit).  The fast build runs under
 every walk and either builder, through the queue's three batch sizes, a rank's strips with dropped border positions, a
-stream range, and after a refit.  Per case the undecided pixels (at most 1 %: CAP) and the worst error / bound ratio per
+stream range, and after a refit.  Per case the undecided pixels (at most 1 %: guides_ref.CAP) and the worst error / bound ratio per
 field are printed; DESIGN.md §4.13 records them.
 """
 import numpy as np
 import pytest
 
-import exact_hits as ex
 import guides_exact as gx
 import rtow
-from guides_ref import attenuations, expected_kernel, guide_values, row_list, same_bits
-from test_gpu_guides import BUILDERS, SCENES, Logged, camera_ray_scales, moved_cover
-from test_gpu_query import SceneView
+from guides_ref import SCENES, Logged, Parts, guide_values, logged, moved_cover, row_list, within_cap  # noqa: F401
+from support_fixtures import qctx  # noqa: F401
+from support_oracle import expected_kernel, same_bits
+from support_tables import BUILDERS, WALKS as KERNELS
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = {"brute": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4}
 PRECISION = {gx.STRICT: rtow.F64_STRICT, gx.FAST: rtow.F64_FAST}
-CAP = 0.01  # the share of pixels that may hold an undecided sample
 
 
 # ---------------------------------------------------------------------------------------------------- helpers ---
-class Parts:
-    """What the checker needs of one host scene: its exact_hits.Scene and its attenuation table."""
-
-    def __init__(self, scene):
-        self.scene = scene
-        self.exact = ex.Scene.of(SceneView(scene))
-        self.att = attenuations(scene)
-
-    def reference(self, rays, ids, spp, build, unit_cut=False):
-        if build == gx.STRICT:
-            return gx.GuideReference(rays, ids, self.exact, self.att, spp, gx.STRICT)
-        s_org, s_dir, s_time = camera_ray_scales(self.scene, rays)
-        omag, dmag = gx.ray_magnitudes(s_org, s_dir, list(self.scene.c.camera.origin))
-        return gx.GuideReference(rays, ids, self.exact, self.att, spp, gx.FAST, unit_cut and len(self.exact.tri) > 0,
-                                 omag, dmag, s_time)
-
-
-def within_cap(what, stats):
-    print(gx.report(str(what), stats))
-    assert stats["undecided_pixels"] <= CAP * stats["pixels"], (what, stats)
-
-
 _refs = {}
 
 
@@ -71,20 +47,8 @@ def checked(ctx, parts, cfg, build, key, want_kernel=None):
 
 
 @pytest.fixture(scope="module")
-def logged():
-    return {name: Logged(*v) for name, v in SCENES.items()}
-
-
-@pytest.fixture(scope="module")
 def parts(logged):
     return {name: Parts(lg.scene) for name, lg in logged.items()}
-
-
-@pytest.fixture(scope="module")
-def qctx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
 
 
 # ---------------------------------------------------------------------------------------------------- tests ---

@@ -7,7 +7,7 @@ max_dist, and in batches whose lanes mix times and max_dist values (NaN, negativ
 and for the mirror to decide 0 on a surface, the distance itself and the double below it) — on the hand-made scene, the
 cover scenes, suzanne, the edge meshes, the sphere edge scenes and the 96.8k mesh (the binary16 top of the 4-wide tree
 with the spill stack), and after translate, scale1000 and flatten refits.  The strict build must equal the mirror bit for
-bit (test_gpu_point_query.check_strict) and pass check_answers at 32 u; the fast build must pass check_answers at 64 u:
+bit (point_cases.check_strict) and pass check_answers at 32 u; the fast build must pass check_answers at 64 u:
 dist within the header's band of the exact distance of the reported primitive, point on that primitive's exact surface
 and consistent with dist, that primitive within the bands of the exact minimum, hit versus miss exact where max_dist
 decides it, the miss record, no NaN.  No query is sampled or exempted.  One line per scene and build is printed: queries,
@@ -18,44 +18,16 @@ import pytest
 import accel_images as ai
 import point_ref as pr
 import rtow
-from test_gpu_point_query import BUILDERS, KERNELS, check_strict, point_sets
-from test_gpu_query import LOGGED, SceneView, big_mesh, handmade_scene, logged  # noqa: F401
-from test_gpu_refit import motions, scene_of
+from point_cases import (EDGE_MESHES, KERNELS, REFITS, SEED, SPHERE_SCENES, check_strict, geometry_case, point_sets,
+                         small_case)
+from support_fixtures import big_mesh, logged, pctx  # noqa: F401
+from support_oracle import LOGGED
+from support_scenes import motions, scene_of
+from support_tables import BUILDERS
 
 pytestmark = pytest.mark.gpu
 
 BUILDS = {"strict": rtow.F64_STRICT, "fast": rtow.F64_FAST}
-EDGE_MESHES = ["n4", "coincident", "zero_area", "flat_z", "off_1e4", "off_1e5", "big_and_small"]
-SPHERE_SCENES = ["negative_radius", "same_centre", "far_moving"]
-SEED = 41
-
-
-@pytest.fixture(scope="module")
-def pctx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
-
-
-def geometry_case(G, keep):
-    """(scene to upload, records, material per insertion index) of an accel_images.Geometry (class-major insertion)."""
-    return scene_of(G, keep), pr.make_records(G.sph, G.mov, G.tri), G.pmat
-
-
-def small_case(name, logged, keep):
-    """(scene to upload, records, materials, near set or None, random set or None) of a small scene by name."""
-    if name == "handmade":
-        hs = handmade_scene()
-        keep.append(hs)
-        view = SceneView(hs)
-        return hs.c, pr.records(view), view.prim_mat, None, None
-    if name in LOGGED:
-        hs, view, log = logged[name]
-        rec = pr.records(view)
-        sets = point_sets(rec, log, pr.SIZES["mixed"], 7)
-        return hs.c, rec, view.prim_mat, sets["near"], sets["random"][0]
-    G = ai.mesh_geometry(ai.edge_meshes()[name]) if name in EDGE_MESHES else ai.sphere_edge_scenes()[name]
-    return geometry_case(G, keep) + (None, None)
 
 
 class Batch:
@@ -126,9 +98,6 @@ def test_big_mesh(pctx, big_mesh):
     sets = pr.all_sets(rec, SEED, ps["near"], ps["random"][0], sizes=pr.SIZES_BIG)
     assert sum(len(s[1]) for s in sets) <= 100
     run_case(pctx, "mesh96k", hs.c, rec, view.prim_mat, sets, brute=False, node_bytes=64)
-
-
-REFITS = [(n, m) for n in ("cover_moving", "suzanne") for m in ("translate", "scale1000", "flatten")]
 
 
 @pytest.mark.parametrize("name,motion", REFITS + [("mesh96k", "scale1000")])

@@ -18,10 +18,11 @@ import accel_images as ai
 import exact_hits as ex
 import first_hits_ref as fr
 import rtow
-from test_gpu_exact_hits import (BUILDERS, BUILDS, SHARE, WALKS, big_mesh, cover_tangent_rays, det_cut_rays,  # noqa: F401
-                                 edge_rays, far_case, handmade_tangent_rays, logged, magnitude_rays, mesh_case, qctx,
-                                 refit_case, surface_rays)
-from test_gpu_query import SceneView, handmade_rays, handmade_scene
+from exact_cases import (BUILDS, SHARE, big_mesh, cover_tangent_rays, det_cut_rays, edge_rays, far_case,  # noqa: F401
+                         handmade_tangent_rays, logged, magnitude_rays, mesh_case, refit_case, surface_rays)
+from support_fixtures import qctx  # noqa: F401
+from support_scenes import SceneView, handmade_rays, handmade_scene
+from support_tables import BUILDERS, WALKS
 
 pytestmark = pytest.mark.gpu
 

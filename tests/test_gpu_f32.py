@@ -27,18 +27,13 @@ import pytest
 
 import rtow
 from conftest import GOLDEN, REPO
+from support_oracle import block_means
 
 pytestmark = pytest.mark.gpu
 
 
 def shown(img, spp):
     return np.sqrt(np.clip(img / spp, 0.0, 1.0))
-
-
-def block_means(a, b=16):
-    h, w, _ = a.shape
-    h, w = h // b * b, w // b * b
-    return a[:h, :w].reshape(h // b, b, w // b, b, 3).mean(axis=(1, 3))
 
 
 def pair(ctx, scene, w, h, spp, depth, kernel, seed=5):

@@ -116,7 +116,7 @@ def test_f32_samples_with_either_builder(actx, builder):
 
 def test_f32_samples_after_a_refit(actx):
     """The moving cover scene is uploaded, then refitted to the same scene turned about the vertical axis (the `rotate`
-    motion of test_gpu_refit.motions); the audit is of the turned scene."""
+    motion of support_scenes.motions); the audit is of the turned scene."""
     run_audit(actx, "cover_refit", rtow.KERNEL_AUTO, (GRID, BVH), upload=fa.FRAMES["cover_moving"][0](),
               refit=fa.audit("cover_refit").scene)
 

@@ -14,23 +14,15 @@ import pytest
 
 import first_hits_ref as fr
 import rtow
-from test_gpu_query import (FAST_CASES, FAST_KERNELS, LOGGED, SceneView, big_mesh, expected_kernel,  # noqa: F401
-                            handmade_rays, handmade_scene, logged, rays_of)
-from test_gpu_refit import SMALL, _copy, motions, rays_for, scene_of
+from support_fixtures import big_mesh, fctx, logged  # noqa: F401
+from support_oracle import FAST_CASES, LOGGED, expected_kernel, rays_of, seeded_finite_tmax
+from support_scenes import SMALL, SceneView, _copy, handmade_rays, handmade_scene, motions, rays_for, scene_of
+from support_tables import BUILDERS, WALKS
 
 pytestmark = pytest.mark.gpu
 
-WALKS = {"brute": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4}
-BUILDERS = {"host": rtow.BUILDER_HOST_SAH, "device": rtow.BUILDER_DEVICE_LBVH}
 HIT = rtow.HIT_DTYPE.itemsize  # 72
 S = rtow.F64_STRICT
-
-
-@pytest.fixture(scope="module")
-def fctx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
 
 
 def assert_equal(got, want, what):
@@ -42,14 +34,6 @@ def assert_equal(got, want, what):
 def cut(ref8, k):
     """The reference for max_hits = k from the one for 8 (the definition: a prefix)."""
     return np.ascontiguousarray(ref8[0][:, :k]), np.minimum(ref8[1], k).astype(np.int32)
-
-
-def seeded_finite_tmax(rays, seed=11):
-    g = np.random.default_rng(seed)
-    finite = rays.copy()
-    finite["tmax"] = g.choice([0.0005, 0.3, 1.0, 2.5, 6.0, 50.0], size=len(rays)) * g.random(len(rays)) * 2.0
-    finite["tmax"][:3] = [math.nan, 0.000999, 0.001]  # (the empty interval, both ways, and its edge)
-    return finite
 
 
 # ------------------------------------------------------------------------------------------ 1. hand-made scene ---
@@ -267,8 +251,8 @@ def test_fast_agrees_with_strict(fctx, logged, big_mesh, name, kernel):
     scene, view, log = big_mesh if name == "mesh96k" else logged[name]
     fctx.upload(scene)
     rays = rays_of(log)
-    hs, cs = fctx.first_hits(rays, 4, rtow.F64_STRICT, FAST_KERNELS[kernel])
-    hf, cf = fctx.first_hits(rays, 4, rtow.F64_FAST, FAST_KERNELS[kernel])
+    hs, cs = fctx.first_hits(rays, 4, rtow.F64_STRICT, WALKS[kernel])
+    hf, cf = fctx.first_hits(rays, 4, rtow.F64_FAST, WALKS[kernel])
     agree = (cs == cf) & np.all(hs["prim"] == hf["prim"], axis=1)
     share = float(np.mean(~agree))
     used = (hs["prim"] >= 0) & agree[:, None]

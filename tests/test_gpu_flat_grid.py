@@ -6,9 +6,7 @@ oracle's bit for bit, fast and f32 images are those of RTOW_NO_FLAT and RTOW_NO_
 counters (segments, node tests = cells read, primitive tests) are those of RTOW_NO_FLAT in every build.  Knobs are read
 when a context is created: one context per setting.  Every render here goes through a synchronising entry point, which
 turns a non-zero sticky `dropped` word into RTOW_EHIP: a render that returns has dropped nothing."""
-import ctypes as C
 import functools
-import math
 import os
 
 import numpy as np
@@ -16,6 +14,7 @@ import pytest
 
 import orc
 import rtow
+from support_scenes import look_at, sphere_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -59,55 +58,6 @@ def counters(st):
 
 
 # ---- scenes ------------------------------------------------------------------------------------------------------------
-
-def look_at(lookfrom, lookat, vup, vfov=70.0, aspect=1.5):
-    """The reference's pinhole camera (lens radius 0, focus distance 1)."""
-    o, at, up = (np.asarray(a, float) for a in (lookfrom, lookat, vup))
-    vh = 2.0 * math.tan(math.radians(vfov) / 2.0)
-    w = (o - at) / np.linalg.norm(o - at)
-    u = np.cross(up, w)
-    u /= np.linalg.norm(u)
-    v = np.cross(w, u)
-    cam = rtow.Camera()
-    hor, ver = aspect * vh * u, vh * v
-    for name, val in (("origin", o), ("u", u), ("v", v), ("w", w), ("horizontal", hor), ("vertical", ver),
-                      ("lower_left_corner", o - hor / 2 - ver / 2 - w)):
-        setattr(cam, name, (C.c_double * 3)(*val))
-    cam.lens_radius, cam.t0, cam.t1 = 0.0, 0.0, 1.0
-    return cam
-
-
-def sphere_scene(centres, radius, cam, keep):
-    """A ground sphere (top at y = -1) plus small spheres of one radius; Lambertian ground, the three materials in turn."""
-    n = len(centres)
-    sph = np.zeros((n + 1, 4))
-    sph[0] = [0.0, -1001.0, 0.0, 1000.0]
-    sph[1:, :3] = centres
-    sph[1:, 3] = radius
-    mats = (rtow.Material * 4)()
-    for i, (kind, alb, fuzz) in enumerate(((rtow.MAT_LAMBERTIAN, (0.5, 0.5, 0.5), 0.0), (rtow.MAT_LAMBERTIAN, (0.8, 0.3, 0.2), 0.0),
-                                           (rtow.MAT_METAL, (0.7, 0.8, 0.9), 0.1), (rtow.MAT_DIELECTRIC, (1.0, 1.0, 1.0), 0.0))):
-        mats[i].kind, mats[i].albedo, mats[i].fuzz, mats[i].ir = kind, (C.c_double * 3)(*alb), fuzz, 1.5
-    smat = (1 + np.arange(n + 1) % 3).astype(np.int32)
-    smat[0] = 0
-    kinds, index = np.zeros(n + 1, np.int32), np.arange(n + 1, dtype=np.int32)
-    none_d, none_i = np.zeros(1), np.zeros(1, np.int32)
-    sc = rtow.Scene()
-    sc.camera = cam
-    sc.n_spheres, sc.n_moving, sc.n_triangles = n + 1, 0, 0
-    sc.sphere_geom = sph.ctypes.data_as(C.POINTER(C.c_double))
-    sc.sphere_mat = smat.ctypes.data_as(C.POINTER(C.c_int32))
-    sc.moving_geom = none_d.ctypes.data_as(C.POINTER(C.c_double))
-    sc.moving_mat = none_i.ctypes.data_as(C.POINTER(C.c_int32))
-    sc.triangle_geom = none_d.ctypes.data_as(C.POINTER(C.c_double))
-    sc.triangle_mat = none_i.ctypes.data_as(C.POINTER(C.c_int32))
-    sc.n_materials, sc.materials = 4, mats
-    sc.n_prims = n + 1
-    sc.prim_kind = kinds.ctypes.data_as(C.POINTER(C.c_int32))
-    sc.prim_index = index.ctypes.data_as(C.POINTER(C.c_int32))
-    keep.extend([sph, mats, smat, kinds, index, none_d, none_i, cam])
-    return sc
-
 
 def lattice(layers):
     """Small spheres (r = 0.2) on integer (x, z) in [-5, 5]^2, `layers` of them one unit apart in y from y = 0.2."""

@@ -6,66 +6,14 @@ structures.  The strict build must still return the same image bit for bit: the 
 not depend on the acceleration structure.  (Insertion order = class-major order here, so prim_kind /
 prim_index describe exactly the order the oracle's tree is built from.)
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import orc
 import rtow
+from support_scenes import random_scene
 
 pytestmark = pytest.mark.gpu
-
-
-def random_scene(seed, n_sph, n_mov, n_tri, keep):
-    rng = np.random.default_rng(seed)
-    base = rtow.HostScene.cover(0, 1.5, False)
-    g = 0 if (n_sph == 0 and n_mov == 0) else 1  # triangle-only scenes stay triangle-only (the BVH4 kernel's case)
-    sph = np.zeros((n_sph + g, 4))
-    if g:
-        sph[0] = [0.0, -200.5, 0.0, 200.0]  # a big ground sphere among small ones
-    sph[g:, :3] = rng.uniform(-3, 3, size=(n_sph, 3)) * [1, 0.4, 1] + [0, 0.6, 0]
-    sph[g:, 3] = rng.choice([0.05, 0.15, 0.4, 0.9], size=n_sph, p=[0.4, 0.4, 0.15, 0.05])
-    mov = np.zeros((n_mov, 8))  # c0 xyz, c1 xyz, radius, pad
-    mov[:, :3] = rng.uniform(-3, 3, size=(n_mov, 3)) * [1, 0.4, 1] + [0, 0.6, 0]
-    mov[:, 3:6] = mov[:, :3] + rng.uniform(-0.4, 0.4, size=(n_mov, 3))
-    mov[:, 6] = rng.uniform(0.05, 0.3, size=n_mov)
-    tri = np.zeros((n_tri, 9))
-    c = rng.uniform(-3, 3, size=(n_tri, 3)) * [1, 0.3, 1] + [0, 0.8, 0]
-    for k in range(3):
-        tri[:, 3 * k:3 * k + 3] = c + rng.uniform(-0.5, 0.5, size=(n_tri, 3))
-    n_mat = 8
-    mats = (rtow.Material * n_mat)()
-    for i in range(n_mat):
-        kind = [rtow.MAT_LAMBERTIAN, rtow.MAT_METAL, rtow.MAT_DIELECTRIC][i % 3]
-        mats[i].kind = kind
-        mats[i].albedo = (C.c_double * 3)(*rng.uniform(0.3, 0.95, 3))
-        mats[i].fuzz = float(rng.uniform(0, 0.5)) if kind == rtow.MAT_METAL else 0.0
-        mats[i].ir = 1.5
-    ns, nm, nt = n_sph + g, n_mov, n_tri
-    smat = rng.integers(0, n_mat, max(ns, 1)).astype(np.int32)
-    smat[0] = 0  # Lambertian ground
-    mmat = rng.integers(0, n_mat, max(nm, 1)).astype(np.int32)
-    tmat = (rng.integers(0, n_mat // 3, max(nt, 1)) * 3).astype(np.int32)  # triangles: Lambertian only
-    kinds = np.concatenate([np.zeros(ns), np.ones(nm), np.full(nt, 2)]).astype(np.int32)
-    index = np.concatenate([np.arange(ns), np.arange(nm), np.arange(nt)]).astype(np.int32)
-    sc = rtow.Scene()
-    sc.camera = base.c.camera
-    sc.n_spheres, sc.n_moving, sc.n_triangles = ns, nm, nt
-    sph_c, mov_c, tri_c = np.ascontiguousarray(sph), np.ascontiguousarray(mov), np.ascontiguousarray(tri)
-    sc.sphere_geom = sph_c.ctypes.data_as(C.POINTER(C.c_double))
-    sc.sphere_mat = smat.ctypes.data_as(C.POINTER(C.c_int32))
-    sc.moving_geom = mov_c.ctypes.data_as(C.POINTER(C.c_double))
-    sc.moving_mat = mmat.ctypes.data_as(C.POINTER(C.c_int32))
-    sc.triangle_geom = tri_c.ctypes.data_as(C.POINTER(C.c_double))
-    sc.triangle_mat = tmat.ctypes.data_as(C.POINTER(C.c_int32))
-    sc.n_materials = n_mat
-    sc.materials = mats
-    sc.n_prims = ns + nm + nt
-    sc.prim_kind = kinds.ctypes.data_as(C.POINTER(C.c_int32))
-    sc.prim_index = index.ctypes.data_as(C.POINTER(C.c_int32))
-    keep.extend([base, sph_c, mov_c, tri_c, mats, smat, mmat, tmat, kinds, index])
-    return sc
 
 
 SHAPES = [(30, 0, 0), (60, 20, 0), (0, 0, 80), (40, 10, 60), (200, 0, 0), (5, 5, 5), (120, 40, 100), (0, 0, 1500)]

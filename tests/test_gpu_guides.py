@@ -16,17 +16,14 @@ import pytest
 
 import orc
 import rtow
-from guides_ref import (attenuations, cover, cover_moving, expected_kernel, fold_guides, guide_values, logged_render,
-                        primaries, row_list, same_bits, sum_in_order, suzanne)
+from guides_ref import (SCENES, Logged, attenuations, camera_ray_scales, fold_guides, guide_values, logged,  # noqa: F401
+                        moved_cover, row_list)
+from support_fixtures import qctx  # noqa: F401
+from support_oracle import expected_kernel, same_bits, sum_in_order
+from support_scenes import cover
+from support_tables import BUILDERS, KERNELS
 
 pytestmark = pytest.mark.gpu
-
-KERNELS = {"brute": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4,
-           "reftree": rtow.KERNEL_REFTREE}
-BUILDERS = {"host": rtow.BUILDER_HOST_SAH, "device": rtow.BUILDER_DEVICE_LBVH}
-# name: (scene, width, height, spp, seed).  The cover camera has a lens (radius 0.05: the origins differ per sample), the
-# moving cover a shutter interval (the times differ per sample), suzanne is a triangle mesh.
-SCENES = {"cover": (cover, 48, 32, 4, 21), "cover_moving": (cover_moving, 48, 32, 4, 22), "suzanne": (suzanne, 48, 27, 4, 23)}
 
 # Fast camera rays against strict ones: |fast - strict| <= K_CAMERA * 2^-53 * S per component, S the sum of the absolute
 # values of the component's terms (test_fast_camera_rays_against_strict).  Measured on one MI355X over the three scenes'
@@ -36,39 +33,6 @@ SCENES = {"cover": (cover, 48, 32, 4, 21), "cover_moving": (cover_moving, 48, 32
 # origin's own term dominates S and the ratio is 1.99.  Rounded up to a power of two, 64, times 4 for other cameras and
 # image sizes.
 K_CAMERA = 256.0
-
-
-class Logged:
-    """One oracle render at depth 0 with its log; `cfg` is the strict config the device calls take."""
-
-    def __init__(self, mk, w, h, spp, seed):
-        self.scene = mk() if callable(mk) else mk
-        self.w, self.h, self.spp, self.seed = w, h, spp, seed
-        self.cfg = self.config()
-        self.image, self.log = logged_render(self.scene, self.cfg)
-        assert len(self.log) == w * h * spp and np.all(self.log[:, 2] == 0)  # depth 0: every row is a primary
-        self.rays, self.ids = primaries(self.log)
-        # pixel-major, sample-minor
-        assert np.array_equal(self.ids[:, 0], np.repeat(np.arange(w * h), spp))
-        assert np.array_equal(self.ids[:, 1], np.tile(np.arange(spp), w * h))
-
-    def config(self, precision=rtow.F64_STRICT, kernel=rtow.KERNEL_AUTO, **kw):
-        kw.setdefault("nstreams", 1)
-        return rtow.make_config(self.w, self.h, kw.pop("spp", self.spp), max_child_rays=0, seed=self.seed,
-                                precision=precision, kernel=kernel, **kw)
-
-
-@pytest.fixture(scope="module")
-def logged():
-    """name -> the three small oracle renders (computed once, never changed)."""
-    return {name: Logged(*v) for name, v in SCENES.items()}
-
-
-@pytest.fixture(scope="module")
-def qctx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")
@@ -271,22 +235,6 @@ def test_fast_guides_against_strict(qctx, logged, name):
     assert close > 0.97, close
 
 
-def camera_ray_scales(scene, rays):
-    """Per ray and component, the sum of the absolute values of the terms of Camera::get_ray: (S_origin [n, 3],
-    S_direction [n, 3], S_time [n]).  origin = o + (u rdx + v rdy); direction = llc + s horizontal + t vertical - origin;
-    time = jt (t1 - t0) + t0.  (rdx, rdy) and (s, t) are recovered from the strict ray by least squares."""
-    cam = scene.c.camera
-    o, cu, cv = (np.array(list(x)) for x in (cam.origin, cam.u, cam.v))
-    hor, ver, llc = (np.array(list(x)) for x in (cam.horizontal, cam.vertical, cam.lower_left_corner))
-    lens = (rays["origin"] - o) @ np.linalg.pinv(np.stack([cu, cv]))            # [n, 2] (rdx, rdy)
-    s_off = np.abs(lens[:, 0:1] * cu) + np.abs(lens[:, 1:2] * cv)
-    s_org = np.abs(o) + s_off
-    st = (rays["direction"] + rays["origin"] - llc) @ np.linalg.pinv(np.stack([hor, ver]))
-    s_dir = np.abs(llc) + np.abs(st[:, 0:1] * hor) + np.abs(st[:, 1:2] * ver) + s_org
-    s_time = np.abs(rays["time"] - cam.t0) + abs(cam.t0)
-    return s_org, s_dir, s_time
-
-
 def test_fast_camera_rays_against_strict(qctx, logged):
     """6b. |fast - strict| <= K_CAMERA 2^-53 S per component over the three scenes' primaries (K_CAMERA above)."""
     u = 2.0 ** -53
@@ -306,22 +254,6 @@ def test_fast_camera_rays_against_strict(qctx, logged):
     print("worst:", worst)
     for f, r in worst.items():
         assert r <= K_CAMERA, (f, r)
-
-
-def moved_cover():
-    """The moving cover with its spheres and its camera moved: what test_after_a_refit refits over the unmoved scene."""
-    moved = cover_moving()
-    sc = moved.c
-    for i in range(1, sc.n_spheres):  # (sphere 0 is the ground)
-        sc.sphere_geom[4 * i + 0] += 0.05 * ((i % 5) - 2)
-        sc.sphere_geom[4 * i + 1] += 0.02 * (i % 3)
-    for i in range(sc.n_moving):
-        sc.moving_geom[8 * i + 1] += 0.03 * (i % 4)
-        sc.moving_geom[8 * i + 4] += 0.03 * (i % 4) + 0.1
-    for k, d in enumerate((-0.75, 0.5, 0.25)):  # the camera, translated
-        sc.camera.origin[k] += d
-        sc.camera.lower_left_corner[k] += d
-    return moved
 
 
 def test_after_a_refit(logged):

@@ -13,20 +13,12 @@ import numpy as np
 import pytest
 
 import rtow
-from test_gpu_query import (LOGGED, STRICT_KERNELS, SceneView, big_mesh, handmade_rays, handmade_scene,  # noqa: F401
-                            logged, rays_of)
+from support_fixtures import big_mesh, logged, octx  # noqa: F401
+from support_oracle import LOGGED, rays_of
+from support_scenes import SceneView, handmade_rays, handmade_scene
+from support_tables import BUILDERS, KERNELS as STRICT_KERNELS, WALKS
 
 pytestmark = pytest.mark.gpu
-
-WALKS = {"brute": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4}
-BUILDERS = {"host": rtow.BUILDER_HOST_SAH, "device": rtow.BUILDER_DEVICE_LBVH}
-
-
-@pytest.fixture(scope="module")
-def octx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
 
 
 def expected_from_log(log, tmax):

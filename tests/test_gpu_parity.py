@@ -15,36 +15,14 @@ import pytest
 import orc
 import rtow
 from conftest import GOLDEN
+from support_oracle import expected_kernel, to8
+from support_scenes import CASES, make_scene, random_sphere_scene, suzanne_tris, write_mesh_obj
+from support_tables import WALKS
 
 pytestmark = pytest.mark.gpu
 
-CASES = {
-    # name: (scene kind, args, width, aspect, spp, nstreams, depth, seed) — same as make_fixtures.py
-    "c1_3spheres": ("cover", (0, 16 / 9, True), 64, 16 / 9, 8, 2, 10, 7),
-    "cover_static": ("cover", (11, 1.5, False), 60, 1.5, 4, 2, 50, 1),
-    "cover_moving": ("cover", (11, 1.5, True), 60, 1.5, 4, 1, 50, 3),
-    "suzanne": ("obj", (16 / 9,), 64, 16 / 9, 4, 2, 20, 5),
-}
-
-
-def make_scene(kind, args):
-    if kind == "cover":
-        return rtow.HostScene.cover(*args)
-    return rtow.HostScene.obj(GOLDEN / "suzanne.obj", *args)
-
-
-def to8(img, spp):
-    return (256 * np.clip(np.sqrt(img / spp), 0.0, 0.999)).astype(np.int32)
-
-
-KERNELS = {"stream": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4}
-
-
-def expected_kernel(name, kernel):
-    """BVH4 is for triangle meshes; on scenes with spheres a BVH4 request runs the binary walk."""
-    if kernel == "bvh4" and name != "suzanne":
-        return rtow.KERNEL_BVH
-    return KERNELS[kernel]
+# (the ids of this file call the brute-force walk "stream")
+KERNELS = {("stream" if k == "brute" else k): v for k, v in WALKS.items()}
 
 
 @pytest.mark.parametrize("kernel", list(KERNELS))
@@ -55,7 +33,8 @@ def test_strict_is_bit_identical_to_oracle_and_golden(ctx, name, kernel):
     cfg = rtow.make_config(w, rtow.image_height(w, aspect), spp, ns, depth, seed=seed,
                            precision=rtow.F64_STRICT, kernel=KERNELS[kernel])
     img, st = ctx.render(scene, cfg)
-    assert st.kernel_used == expected_kernel(name, kernel)
+    want = expected_kernel(scene, KERNELS[kernel])  # (None: a mesh under GRID; suzanne takes a grid)
+    assert st.kernel_used == (KERNELS[kernel] if want is None else want)
     ref, ost = orc.render(scene, cfg, orc.RNG_PHILOX, nthreads=8)
     assert img.shape == ref.shape
     assert np.array_equal(img, ref), f"{int((img != ref).sum())} of {img.size} values differ"
@@ -159,15 +138,7 @@ def test_mesh100k_global_image_path_is_bit_identical(ctx, tmp_path):
     """BASELINE config C5 shape: the synthetic 96,800-triangle mesh (scripts/make_mesh.py; the
     reference's dragon.obj is absent) does not fit LDS, so the BVH kernel walks the scene image
     in global memory.  Strict build vs oracle (which walks the REFERENCE's BVH), bit for bit."""
-    import subprocess
-    import sys
-
-    from conftest import REPO
-
-    obj = tmp_path / "mesh.obj"
-    subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(obj), "10"], check=True,
-                   capture_output=True)
-    scene = rtow.HostScene.obj(obj, 16 / 9)
+    scene = rtow.HostScene.obj(write_mesh_obj(tmp_path), 16 / 9)
     assert scene.c.n_triangles == 96800
     ref = None
     for kernel in (rtow.KERNEL_BVH, rtow.KERNEL_BVH4):  # binary walk over the global image; 4-wide walk, top of the tree in LDS
@@ -221,43 +192,9 @@ def test_rtweekend_binary_ppm_is_byte_identical_to_oracle(ctx):
     assert list(r6.stdout[len(head):]) == [int(x) for x in r.stdout.split()[4:]]
 
 
-def _random_sphere_scene(hollow):
-    import ctypes as C
-
-    n = 40
-    rng = np.random.default_rng(3)
-    geom = np.zeros((n + 3, 4))
-    geom[0] = [0, -100.5, -1, 100]
-    geom[1] = [0, 0, -1, 0.5]
-    geom[2] = [0, 0, -1, -0.45 if hollow else 0.2]  # hollow glass: negative inner radius
-    geom[3:, :3] = rng.uniform(-2, 2, size=(n, 3)) + [0, 0.5, -3]
-    geom[3:, 3] = rng.uniform(0.05, 0.3, size=n)
-    mats = (rtow.Material * (n + 3))()
-    for i in range(n + 3):
-        kind = [rtow.MAT_LAMBERTIAN, rtow.MAT_DIELECTRIC, rtow.MAT_DIELECTRIC][i] if i < 3 else int(rng.integers(0, 3))
-        mats[i].kind = kind
-        mats[i].albedo = (C.c_double * 3)(*rng.uniform(0.2, 0.9, 3))
-        mats[i].fuzz = float(rng.uniform(0, 0.4)) if kind == rtow.MAT_METAL else 0.0
-        mats[i].ir = 1.5
-    base = rtow.HostScene.cover(0, 2.0, False)
-    sc = rtow.Scene()
-    sc.camera = base.c.camera
-    keep = dict(g=np.ascontiguousarray(geom), mi=np.arange(n + 3, dtype=np.int32),
-                kinds=np.zeros(n + 3, dtype=np.int32), mats=mats)
-    sc.n_spheres = n + 3
-    sc.sphere_geom = keep["g"].ctypes.data_as(C.POINTER(C.c_double))
-    sc.sphere_mat = keep["mi"].ctypes.data_as(C.POINTER(C.c_int32))
-    sc.n_materials = n + 3
-    sc.materials = mats
-    sc.n_prims = n + 3
-    sc.prim_kind = keep["kinds"].ctypes.data_as(C.POINTER(C.c_int32))
-    sc.prim_index = keep["mi"].ctypes.data_as(C.POINTER(C.c_int32))
-    return sc, keep
-
-
 def test_overlapping_spheres_one_material_each(ctx):
     """43 overlapping spheres, a material per primitive (all three kinds); strict vs oracle."""
-    sc, keep = _random_sphere_scene(hollow=False)
+    sc, keep = random_sphere_scene(hollow=False)
     for kernel in (rtow.KERNEL_BRUTE, rtow.KERNEL_BVH, rtow.KERNEL_GRID):
         cfg = rtow.make_config(80, 40, 6, 2, 30, seed=9, precision=rtow.F64_STRICT, kernel=kernel)
         img, st = ctx.render(sc, cfg)
@@ -273,8 +210,8 @@ def test_negative_radius_hollow_sphere(ctx):
     intersects the sphere like the reference's hit test would without a BVH.  (None of the
     reference's scenes has a negative radius.)  Checked here: both device kernels agree bit for
     bit, and the hollow shell changes the image."""
-    sc, keep = _random_sphere_scene(hollow=True)
-    plain, keep2 = _random_sphere_scene(hollow=False)
+    sc, keep = random_sphere_scene(hollow=True)
+    plain, keep2 = random_sphere_scene(hollow=False)
     imgs = []
     for kernel in (rtow.KERNEL_BRUTE, rtow.KERNEL_BVH):
         cfg = rtow.make_config(80, 40, 6, 2, 30, seed=9, precision=rtow.F64_STRICT, kernel=kernel)
@@ -512,16 +449,9 @@ def test_half_node_walk_is_bit_identical_to_the_oracle(monkeypatch, tmp_path, sm
     frame (rtow_bvh4.h): boxes a little bigger, never smaller, so the closest hit — and the strict image — is what
     the oracle computes with the reference's tree.  suzanne subdivided 2x2 (3,872 triangles), as it is and shrunk and
     moved off the origin (the frame's centre and scale are then not 0 and 1), trip form and state machine."""
-    import sys
-
-    from conftest import REPO
-    sys.path.insert(0, str(REPO / "scripts"))
-    import make_mesh
-
     if sm:
         monkeypatch.setenv("RTOW_BVH4_SM", "1")
-    v, f = make_mesh.load(GOLDEN / "suzanne.obj")
-    tris = make_mesh.subdivide(v, f, 2)
+    tris = suzanne_tris(2)
     c = rtow.Context(0)
     try:
         for k, (scale, shift) in enumerate(((1.0, (0.0, 0.0, 0.0)), (0.55, (0.3125, -0.11, 0.27)))):
@@ -554,14 +484,7 @@ def test_meshes_around_the_lds_limit_switch_node_format_and_stay_bit_identical(t
     the first N of suzanne subdivided 2x2 — straddle the point where the binary32 image plus six stack entries per
     lane (round 5; eight before) stops fitting the 160 KB of LDS.  Each renders bit for bit like the oracle, whichever side it falls on, and
     both formats occur."""
-    import sys
-
-    from conftest import REPO
-    sys.path.insert(0, str(REPO / "scripts"))
-    import make_mesh
-
-    v, f = make_mesh.load(GOLDEN / "suzanne.obj")
-    tris = make_mesh.subdivide(v, f, 2)
+    tris = suzanne_tris(2)
     formats = set()
     c = rtow.Context(0)
     try:
@@ -592,14 +515,7 @@ def test_mesh_beyond_the_bvh4_limits_takes_the_binary_walk(ctx, tmp_path):
     """The 4-wide image addresses triangles with 18 bits (rtow_bvh4.h): a mesh of 279,752 triangles (suzanne
     subdivided 17x17) is rendered by the binary threaded walk instead — same surface, so the image agrees with the
     968-triangle original within Monte-Carlo noise; an explicit BVH4 request falls back, it does not fail."""
-    import subprocess
-    import sys
-
-    from conftest import REPO
-
-    obj = tmp_path / "mesh17.obj"
-    subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(obj), "17"], check=True, capture_output=True)
-    big = rtow.HostScene.obj(obj, 16 / 9)
+    big = rtow.HostScene.obj(write_mesh_obj(tmp_path, 17), 16 / 9)
     assert big.c.n_triangles == 968 * 17 * 17
     cfg = rtow.make_config(96, 54, 16, 2, 20, seed=13, precision=rtow.F64_FAST, kernel=rtow.KERNEL_BVH4)
     a, st = ctx.render(big, cfg)

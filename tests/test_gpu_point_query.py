@@ -12,56 +12,16 @@ import math
 import numpy as np
 import pytest
 
+import accel_images as ai
 import point_ref as pr
 import rtow
-from test_gpu_query import (LOGGED, SceneView, big_mesh, handmade_scene, logged, rays_of,  # noqa: F401
-                            same_bits)
+from point_cases import KERNELS, check_strict, point_sets
+from support_fixtures import big_mesh, logged, pctx  # noqa: F401
+from support_oracle import LOGGED, rays_of, same_bits
+from support_scenes import SceneView, deform, handmade_scene, scene_of, suzanne_tris
+from support_tables import BUILDERS
 
 pytestmark = pytest.mark.gpu
-
-KERNELS = {"brute": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4,
-           "auto": rtow.KERNEL_AUTO}
-BUILDERS = {"host": rtow.BUILDER_HOST_SAH, "device": rtow.BUILDER_DEVICE_LBVH}
-
-
-@pytest.fixture(scope="module")
-def pctx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
-
-
-# ---------------------------------------------------------------------------------------------------- helpers ---
-def extent_box(rec):
-    pts = [rec.tri[:, 0:3], rec.tri[:, 0:3] + rec.tri[:, 3:6], rec.tri[:, 0:3] + rec.tri[:, 6:9]]
-    small = rec.sph[np.sqrt(np.abs(rec.sph[:, 3])) < 100.0]
-    if len(small):
-        r = np.sqrt(np.abs(small[:, 3:4]))
-        pts += [small[:, 0:3] - r, small[:, 0:3] + r]
-    if rec.nm:
-        r = np.abs(rec.mov[:, 7:8])
-        pts += [rec.mov[:, 0:3] - r, rec.mov[:, 0:3] + rec.mov[:, 3:6] + r]
-    pts = np.concatenate([p for p in pts if len(p)])
-    return pts.min(0), pts.max(0)
-
-
-def point_sets(rec, log, n, seed):
-    """name -> (points, max_dist): near (logged hit points offset by up to 2 % of the extent, max_dist 5 %), volume (a
-    lattice over the box, unbounded) and random (uniform in the box, shuffled, unbounded)."""
-    g = np.random.default_rng(seed)
-    lo, hi = extent_box(rec)
-    ext = float(np.max(hi - lo))
-    out = {}
-    if log is not None:
-        hit = log[np.isfinite(log[:, 10])]
-        rows = hit[g.choice(len(hit), size=min(n, len(hit)), replace=False)]
-        p = rows[:, 3:6] + rows[:, 10:11] * rows[:, 6:9] + g.uniform(-0.02, 0.02, size=(len(rows), 3)) * ext
-        out["near"] = (p, 0.05 * ext)
-    k = max(2, round(n ** (1 / 3)))
-    ax = [np.linspace(lo[j] - 0.05 * ext, hi[j] + 0.05 * ext, k) for j in range(3)]
-    out["volume"] = (np.stack(np.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3), math.inf)
-    out["random"] = (g.uniform(lo - 0.05 * ext, hi + 0.05 * ext, size=(n, 3)), math.inf)
-    return out
 
 
 class Expected:
@@ -71,25 +31,6 @@ class Expected:
         self.rec, self.pts, self.time = rec, pts, time
         self.md = np.broadcast_to(np.asarray(md, dtype=np.float64), (len(pts),))
         self.dmin, self.ties, _ = pr.nearest(rec, pts, time, self.md)
-
-
-def check_strict(exp, view_mat, hits, what):
-    rec = exp.rec
-    assert same_bits(hits["dist"], exp.dmin), (what, int((hits["dist"].view(np.uint64) != exp.dmin.view(np.uint64)).sum()))
-    miss = ~(exp.md >= exp.dmin)
-    assert np.all(hits["prim"][miss] == -1) and np.all(hits["kind"][miss] == -1) and np.all(hits["material"][miss] == -1)
-    assert np.all(hits["point"][miss] == 0.0)
-    hit = np.nonzero(~miss)[0]
-    prim = hits["prim"][hit]
-    assert np.all(prim >= 0), what
-    cid = rec.ins2cls[prim]
-    for j, c in zip(hit, cid):
-        assert c in exp.ties[j], (what, j, c, exp.ties[j][:8])
-    time = np.broadcast_to(np.asarray(exp.time, dtype=np.float64), (len(exp.pts),))
-    d, q = pr.prim_point(rec, cid, exp.pts[hit], time[hit])
-    assert same_bits(d, hits["dist"][hit]) and same_bits(q, hits["point"][hit]), what
-    assert np.array_equal(rec.kind_of(cid), hits["kind"][hit]), what
-    assert np.array_equal(view_mat[prim], hits["material"][hit]), what
 
 
 def upload(ctx, scene, builder):
@@ -191,11 +132,7 @@ def test_max_dist_semantics(pctx, logged):
 
 
 def test_refit_equals_the_mirror_and_a_fresh_upload(pctx):
-    import accel_images as ai
-    from test_gpu_accel_images import _suzanne_tris
-    from test_gpu_refit import deform, scene_of
-
-    G = ai.mesh_geometry(_suzanne_tris(1))
+    G = ai.mesh_geometry(suzanne_tris(1))
     keep = []
     pctx.set_builder(rtow.BUILDER_HOST_SAH)
     pctx.upload(scene_of(G, keep))

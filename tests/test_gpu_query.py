@@ -7,97 +7,19 @@ test (orc_sphere_hit / orc_triangle_hit) on the returned primitive.  The fast bu
 by tolerance; hand-made rays cover the corner cases; the contracts (ordering, residency, errors, no side effect on the
 render) close the file.
 """
-import ctypes as C
-import math
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-import orc
 import rtow
-from conftest import GOLDEN, REPO
+from support_fixtures import big_mesh, logged, qctx  # noqa: F401
+from support_oracle import FAST_CASES, LOGGED, brute_force, expected_kernel, rays_of, same_bits
+from support_scenes import SceneView, handmade_rays, handmade_scene
+from support_tables import KERNELS as STRICT_KERNELS, WALKS as FAST_KERNELS
 
 pytestmark = pytest.mark.gpu
 
-STRICT_KERNELS = {"brute": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID,
-                  "bvh4": rtow.KERNEL_BVH4, "reftree": rtow.KERNEL_REFTREE}
-_pd = C.POINTER(C.c_double)
-
 
 # ---------------------------------------------------------------------------------------------------- helpers ---
-def log_rays(scene, cfg, accel=False, cap=1_500_000):
-    """Every segment of a single-threaded oracle render: [n, 12] (pixel, sample, segment, o xyz, d xyz, time, t_hit or
-    inf, class index or -1)."""
-    buf = np.zeros((cap, 12))
-    L = orc.lib()
-    L.orc_set_raylog.argtypes = [_pd, C.c_uint64]
-    L.orc_set_raylog.restype = None
-    L.orc_raylog_count.restype = C.c_uint64
-    L.orc_set_raylog(buf.ctypes.data_as(_pd), cap)
-    try:
-        orc.render(scene, cfg, orc.RNG_PHILOX, nthreads=1, accel=accel)
-        n = L.orc_raylog_count()
-    finally:
-        L.orc_set_raylog(None, 0)
-    assert 0 < n < cap
-    return buf[:n].copy()
-
-
-def rays_of(log, tmax=math.inf):
-    r = np.empty(len(log), dtype=rtow.RAY_DTYPE)
-    r["origin"] = log[:, 3:6]
-    r["direction"] = log[:, 6:9]
-    r["time"] = log[:, 9]
-    r["tmax"] = tmax
-    return r
-
-
-class SceneView:
-    """numpy copy of a flattened scene: geometry per class, insertion order, material per inserted primitive."""
-
-    def __init__(self, scene):
-        a = orc.scene_arrays(scene.c)
-        self.sph = a["sphere_geom"].reshape(-1, 4)
-        self.mov = a["moving_geom"].reshape(-1, 8)
-        self.tri = a["triangle_geom"].reshape(-1, 9)
-        self.kind = a["prim_kind"]
-        self.index = a["prim_index"]
-        mats = {rtow.PRIM_SPHERE: a["sphere_mat"], rtow.PRIM_MOVING_SPHERE: a["moving_mat"],
-                rtow.PRIM_TRIANGLE: a["triangle_mat"]}
-        self.prim_mat = np.array([mats[k][i] for k, i in zip(self.kind, self.index)], dtype=np.int32)
-
-    def oracle_hit(self, prim, o, d, time, tmin=0.001, tmax=math.inf):
-        """The oracle's hit test of inserted primitive `prim`: (t, point, normal, front) or None."""
-        L = orc.lib()
-        t = C.c_double()
-        p, n = (C.c_double * 3)(), (C.c_double * 3)()
-        ro, rd = (C.c_double * 3)(*o), (C.c_double * 3)(*d)
-        k, i = int(self.kind[prim]), int(self.index[prim])
-        if k == rtow.PRIM_TRIANGLE:
-            g = self.tri[i]
-            ok = L.orc_triangle_hit((C.c_double * 3)(*g[0:3]), (C.c_double * 3)(*g[3:6]), (C.c_double * 3)(*g[6:9]), ro,
-                                    rd, tmin, tmax, C.byref(t), p, n)
-            front = 1
-        else:
-            if k == rtow.PRIM_SPHERE:
-                c, r = self.sph[i, 0:3], self.sph[i, 3]
-            else:  # the oracle's moving_center, in numpy (binary64, no contraction)
-                g = self.mov[i]
-                c, r = g[0:3] + time * (g[3:6] - g[0:3]), g[6]
-            f = C.c_int()
-            ok = L.orc_sphere_hit((C.c_double * 3)(*c), r, ro, rd, tmin, tmax, C.byref(t), p, n, C.byref(f))
-            front = f.value
-        if not ok:
-            return None
-        return t.value, np.array(p[:]), np.array(n[:]), front
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
-
-
 def check_strict_against_log(view, log, hits, what):
     """t bitwise = the log's t_hit, class index = the log's, hit record = the oracle's hit test on that primitive."""
     t_log = log[:, 10]
@@ -118,56 +40,6 @@ def check_strict_against_log(view, log, hits, what):
         t, p, n, front = h
         assert same_bits(t, hits["t"][j]) and same_bits(p, hits["point"][j]) and same_bits(n, hits["normal"][j]), (what, j)
         assert front == hits["front_face"][j], (what, j)
-
-
-def expected_kernel(view, kernel):
-    """The render's fallbacks: BVH4 walks triangle meshes only; GRID falls back to BVH where there is no grid."""
-    mesh = bool(np.all(view.kind == rtow.PRIM_TRIANGLE))
-    if kernel == rtow.KERNEL_BVH4 and not mesh:
-        return rtow.KERNEL_BVH
-    if kernel == rtow.KERNEL_GRID and mesh:
-        return None  # (a small mesh may or may not get a grid: either is the render's rule)
-    return kernel
-
-
-# ------------------------------------------------------------------------------------------------- fixtures ---
-LOGGED = {
-    # name: (scene, width, height, spp, max_child_rays, seed)
-    "cover_static": (lambda: rtow.HostScene.cover(11, 1.5, False), 120, 80, 4, 50, 21),
-    "cover_moving": (lambda: rtow.HostScene.cover(11, 1.5, True), 120, 80, 4, 50, 22),
-    "suzanne": (lambda: rtow.HostScene.obj(GOLDEN / "suzanne.obj", 16 / 9), 96, 54, 4, 20, 23),
-}
-
-
-@pytest.fixture(scope="module")
-def logged():
-    """name -> (scene, view, log) of the three small renders."""
-    out = {}
-    for name, (mk, w, h, spp, depth, seed) in LOGGED.items():
-        scene = mk()
-        cfg = rtow.make_config(w, h, spp, 1, depth, seed=seed, precision=rtow.F64_STRICT)
-        out[name] = (scene, SceneView(scene), log_rays(scene, cfg))
-    return out
-
-
-@pytest.fixture(scope="module")
-def qctx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def big_mesh(tmp_path_factory):
-    """The 96,800-triangle mesh (scripts/make_mesh.py) and a 64x36x2 spp raylog of it (the checker's tree: the same
-    hits as the reference's tree, ~100x faster)."""
-    obj = tmp_path_factory.mktemp("mesh") / "m10.obj"
-    subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(obj), "10"], check=True,
-                   capture_output=True)
-    scene = rtow.HostScene.obj(obj, 16 / 9)
-    assert scene.c.n_triangles == 96800
-    cfg = rtow.make_config(64, 36, 2, 1, 20, seed=24, precision=rtow.F64_STRICT)
-    return scene, SceneView(scene), log_rays(scene, cfg, accel=True)
 
 
 # ---------------------------------------------------------------------------------------------------- tests ---
@@ -201,12 +73,6 @@ def test_big_mesh_strict(qctx, big_mesh, builder, kernel):
         check_strict_against_log(view, log, hits, (builder, kernel))
     finally:
         qctx.set_builder(rtow.BUILDER_AUTO)
-
-
-FAST_KERNELS = {"brute": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4}
-
-
-FAST_CASES = [(n, k) for n in list(LOGGED) + ["mesh96k"] for k in FAST_KERNELS if (n, k) != ("mesh96k", "brute")]
 
 
 @pytest.mark.parametrize("name,kernel", FAST_CASES)
@@ -255,92 +121,6 @@ def test_tmax_is_an_inclusive_bound(qctx, logged, name, kernel):
 
 
 # ---- hand-made scene and rays, against a brute force over the oracle's hit tests ----
-def handmade_scene():
-    """Ground, a glass sphere with a negative-radius inner sphere (hollow glass), a moving sphere, two triangles —
-    inserted triangles first, so insertion order and class-major order differ."""
-    sph = np.array([[0, -1000, 0, 1000], [0, 1, 0, 1.0], [0, 1, 0, -0.8], [-3, 1, 0.5, 0.7]], dtype=np.float64)
-    mov = np.array([[3, 0.5, 0, 3, 1.5, 0, 0.5, 0]], dtype=np.float64)
-    tri = np.array([[-1, 0, -2, 1, 0, -2, 0, 2, -2], [2, 0, -3, 4, 0, -3, 3, 2.5, -3]], dtype=np.float64)
-    sph_mat = np.array([0, 1, 1, 2], dtype=np.int32)
-    mov_mat = np.array([0], dtype=np.int32)
-    tri_mat = np.array([2, 0], dtype=np.int32)
-    kind = np.array([2, 0, 1, 0, 2, 0, 0], dtype=np.int32)
-    index = np.array([1, 2, 0, 0, 0, 3, 1], dtype=np.int32)
-    mats = (rtow.Material * 3)()
-    mats[0].albedo[:] = [0.5, 0.5, 0.5]
-    mats[1].kind, mats[1].ir = rtow.MAT_DIELECTRIC, 1.5
-    mats[2].kind, mats[2].fuzz = rtow.MAT_METAL, 0.1
-    mats[2].albedo[:] = [0.7, 0.6, 0.5]
-    keep = [sph, mov, tri, sph_mat, mov_mat, tri_mat, kind, index, mats]
-    s = rtow.Scene()
-    base = rtow.HostScene.cover(11, 1.5, False)  # (its camera: the queries do not use one)
-    s.camera = base.c.camera
-    pd = lambda a: a.ctypes.data_as(_pd)  # noqa: E731
-    pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
-    s.n_spheres, s.sphere_geom, s.sphere_mat = len(sph), pd(sph), pi(sph_mat)
-    s.n_moving, s.moving_geom, s.moving_mat = len(mov), pd(mov), pi(mov_mat)
-    s.n_triangles, s.triangle_geom, s.triangle_mat = len(tri), pd(tri), pi(tri_mat)
-    s.n_materials, s.materials = 3, mats
-    s.n_prims, s.prim_kind, s.prim_index = len(kind), pi(kind), pi(index)
-
-    class Held:
-        c = s
-
-    h = Held()
-    h.keep = keep
-    base.close()
-    return h
-
-
-def handmade_rays():
-    rng = np.random.default_rng(5)
-    o, d, tm = [], [], []
-    axes = [np.array(v, dtype=np.float64) for v in np.vstack([np.eye(3), -np.eye(3)])]
-    for origin in ([0, 1, 5], [0, 1, -5], [5, 1, 0], [-5, 1, 0], [0, 5, 0], [0.3, 0.9, 0.2], [3, 1, 4], [0, 1, 0],
-                   [0, 0.5, -1], [3.2, 4, -3]):
-        for ax in axes:  # axis-parallel directions: zero components, both signs
-            o.append(origin), d.append(ax), tm.append(0.5)
-    for _ in range(200):  # inside the glass shell (0.8 < r < 1): the far root of the outer sphere, front_face 0
-        u = rng.normal(size=3)
-        u /= np.linalg.norm(u)
-        o.append(np.array([0, 1, 0]) + 0.9 * u), d.append(u + 0.3 * rng.normal(size=3)), tm.append(0.0)
-    for _ in range(200):  # inside the negative-radius sphere, and from outside through the hollow glass
-        u = rng.normal(size=3)
-        o.append(np.array([0, 1, 0]) + 0.5 * u / np.linalg.norm(u)), d.append(rng.normal(size=3)), tm.append(0.0)
-        o.append(np.array([0, 1, 4.0]) + 0.3 * rng.normal(size=3)), d.append([0, 0, -1] + 0.2 * rng.normal(size=3))
-        tm.append(1.0)
-    for x in np.linspace(-2, 2, 21):  # in the plane of a triangle, parallel to it
-        o.append([x, 0.7, -2.0]), d.append([1, 0.1 * x, 0]), tm.append(0.5)
-        o.append([x, 0.5, -3.0]), d.append([0, 1, 0]), tm.append(0.5)
-    for t in (0.0, 0.5, 1.0):  # the moving sphere at three shutter times
-        for y in np.linspace(0.0, 2.2, 23):
-            o.append([3, y, 3]), d.append([0, 0, -1]), tm.append(t)
-            o.append([0, y, 0.01]), d.append([1, 0, 0]), tm.append(t)
-    for _ in range(100):  # rays that miss everything: up and away from above
-        o.append([0, 3000, 0] + rng.normal(size=3)), d.append([rng.normal(), 1.0, rng.normal()]), tm.append(0.3)
-    for _ in range(400):  # and a random cloud
-        o.append(rng.uniform(-5, 5, 3) + [0, 2, 0]), d.append(rng.normal(size=3)), tm.append(rng.uniform(0, 1))
-    r = np.empty(len(o), dtype=rtow.RAY_DTYPE)
-    r["origin"], r["direction"], r["time"], r["tmax"] = np.array(o), np.array(d), np.array(tm), math.inf
-    return r
-
-
-def brute_force(view, rays):
-    """The reference's hittable list: every primitive in insertion order, the interval shrinking to the closest hit."""
-    out = np.zeros(len(rays), dtype=rtow.HIT_DTYPE)
-    out["t"], out["prim"], out["kind"], out["material"] = math.inf, -1, -1, -1
-    for j, r in enumerate(rays):
-        best, tmax = None, math.inf
-        for p in range(len(view.kind)):
-            h = view.oracle_hit(p, r["origin"], r["direction"], r["time"], tmax=tmax)
-            if h is not None:
-                best, tmax = (p, h), h[0]
-        if best is not None:
-            p, (t, pt, n, front) = best
-            out[j] = (t, pt, n, p, view.kind[p], view.prim_mat[p], front)
-    return out
-
-
 @pytest.mark.parametrize("kernel", list(FAST_KERNELS))
 def test_handmade_rays_strict_equal_brute_force(qctx, kernel):
     """Axis-parallel rays, rays from inside the glass shell and the hollow, rays in a triangle's plane, the moving

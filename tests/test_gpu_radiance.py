@@ -13,80 +13,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import orc
 import rtow
-from conftest import GOLDEN
+from support_fixtures import qctx  # noqa: F401
+from support_oracle import expected_kernel, logged_render, primaries, same_bits, sum_in_order
+from support_scenes import cover, cover_moving, suzanne
+from support_tables import KERNELS
 
 pytestmark = pytest.mark.gpu
-
-KERNELS = {"brute": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4,
-           "reftree": rtow.KERNEL_REFTREE}
-_pd = C.POINTER(C.c_double)
-
-
-# ---------------------------------------------------------------------------------------------------- helpers ---
-def logged_render(scene, cfg, cap=200_000):
-    """(sums [pixels, 3], log [n, 12]) of a single-threaded oracle render; a log row is (pixel, sample, segment, o xyz,
-    d xyz, time, t_hit or inf, class index or -1)."""
-    buf = np.zeros((cap, 12))
-    L = orc.lib()
-    L.orc_set_raylog.argtypes = [_pd, C.c_uint64]
-    L.orc_set_raylog.restype = None
-    L.orc_raylog_count.restype = C.c_uint64
-    L.orc_set_raylog(buf.ctypes.data_as(_pd), cap)
-    try:
-        img, _ = orc.render(scene, cfg, orc.RNG_PHILOX, nthreads=1)
-        n = L.orc_raylog_count()
-    finally:
-        L.orc_set_raylog(None, 0)
-    assert 0 < n < cap
-    return img.reshape(-1, 3).copy(), buf[:n].copy()
-
-
-def primaries(log):
-    """(rays, ids) of the log's segment-0 rows: the render's primaries and their Philox identities (pixel, sample)."""
-    p = log[log[:, 2] == 0]
-    r = np.empty(len(p), dtype=rtow.RAY_DTYPE)
-    r["origin"] = p[:, 3:6]
-    r["direction"] = p[:, 6:9]
-    r["time"] = p[:, 9]
-    r["tmax"] = np.inf
-    return r, p[:, 0:2].astype(np.uint32)
-
-
-def sum_in_order(per_ray, spp):
-    """[pixels * spp, 3] -> [pixels, 3]: ((0 + c_0) + c_1) + ... over a pixel's samples, as the oracle adds them."""
-    c = per_ray.reshape(-1, spp, 3)
-    s = np.zeros((c.shape[0], 3))
-    for j in range(spp):
-        s = s + c[:, j]
-    return s
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
-
-
-def expected_kernel(scene, kernel):
-    """The render's fallbacks: BVH4 walks triangle meshes only; GRID falls back to BVH where there is no grid."""
-    mesh = scene.c.n_triangles == scene.c.n_prims
-    if kernel == rtow.KERNEL_BVH4 and not mesh:
-        return rtow.KERNEL_BVH
-    if kernel == rtow.KERNEL_GRID and mesh:
-        return None  # (a small mesh may or may not get a grid: either is the render's rule)
-    return kernel
-
-
-def cover():
-    return rtow.HostScene.cover(11, 1.5, False)
-
-
-def cover_moving():
-    return rtow.HostScene.cover(11, 1.5, True)
-
-
-def suzanne():
-    return rtow.HostScene.obj(GOLDEN / "suzanne.obj", 16 / 9)
 
 
 # ------------------------------------------------------------------------------------------------- fixtures ---
@@ -121,13 +54,6 @@ class Logged:
 def logged():
     """name -> the five small oracle renders (computed once, never changed)."""
     return {name: Logged(name) for name in RENDERS}
-
-
-@pytest.fixture(scope="module")
-def qctx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")

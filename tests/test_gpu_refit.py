@@ -7,8 +7,6 @@ oracle's render of the new scene and queries equal those after a fresh upload of
 grid presence follows the new scene; and the API contracts (shape checks, residency, ordering) hold.
 """
 import ctypes as C
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,146 +15,22 @@ import torch
 import accel_images as ai
 import orc
 import rtow
-from conftest import REPO
-from test_gpu_accel_images import _suzanne_tris, resident_images, to_scene
+from support_fixtures import fresh, rctx  # noqa: F401
+from support_oracle import assert_hits_equal, block_means
+from support_scenes import (SMALL, _copy, _set_order, motions, rays_for, resident_images, scene_of, wave,
+                            write_mesh_obj)
+from support_tables import BUILDERS, KERNELS
 
 pytestmark = pytest.mark.gpu
-
-BUILDERS = {"host": rtow.BUILDER_HOST_SAH, "device": rtow.BUILDER_DEVICE_LBVH}
-KERNELS = {"brute": rtow.KERNEL_BRUTE, "bvh": rtow.KERNEL_BVH, "grid": rtow.KERNEL_GRID, "bvh4": rtow.KERNEL_BVH4,
-           "reftree": rtow.KERNEL_REFTREE}
-
-
-@pytest.fixture(scope="module")
-def rctx():
-    c = rtow.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def fresh():
-    """A second context: the fresh uploads the refits are compared with."""
-    c = rtow.Context(0)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")
 def mesh96k(tmp_path_factory):
-    obj = tmp_path_factory.mktemp("mesh") / "m10.obj"
-    subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(obj), "10"], check=True,
-                   capture_output=True)
-    hs = rtow.HostScene.obj(obj, 16 / 9)
+    hs = rtow.HostScene.obj(write_mesh_obj(tmp_path_factory.mktemp("mesh")), 16 / 9)
     G = ai.Geometry.of_scene(hs.c)
     hs.close()
     assert G.nt == 96800
     return G
-
-
-def small_scenes():
-    """name -> Geometry: the cover scene with moving spheres, suzanne, the meshes around the LDS limit, the edge meshes
-    and the sphere edge scenes."""
-    cover = rtow.HostScene.cover(11, 1.5, True)
-    out = {"cover_moving": ai.Geometry.of_scene(cover.c), "suzanne": ai.mesh_geometry(_suzanne_tris(1))}
-    cover.close()
-    tris2 = _suzanne_tris(2)
-    for n in (850, 1400):
-        out[f"suz{n}"] = ai.mesh_geometry(tris2[:n])
-    out.update({f"edge_{k}": ai.mesh_geometry(v) for k, v in ai.edge_meshes().items()})
-    out.update({f"sph_{k}": v for k, v in ai.sphere_edge_scenes().items()})
-    return out
-
-
-SMALL = small_scenes()
-
-
-def _set_order(sc, G, keep, perm=None):
-    """prim_kind / prim_index of sc: class-major insertion order, permuted by `perm`."""
-    kind = np.array([rtow.PRIM_SPHERE] * G.ns + [rtow.PRIM_MOVING_SPHERE] * G.nm + [rtow.PRIM_TRIANGLE] * G.nt, np.int32)
-    index = np.concatenate([np.arange(G.ns), np.arange(G.nm), np.arange(G.nt)]).astype(np.int32)
-    if perm is not None:
-        kind, index = np.ascontiguousarray(kind[perm]), np.ascontiguousarray(index[perm])
-    ip = C.POINTER(C.c_int32)
-    sc.prim_kind, sc.prim_index = kind.ctypes.data_as(ip), index.ctypes.data_as(ip)
-    keep.extend([kind, index])
-    return sc
-
-
-def scene_of(G, keep, cam_shift=None, shutter=None):
-    """An rtow.Scene of G (to_scene: the cover scene's camera) with its class-major insertion order (the oracle reads
-    one), the camera translated by cam_shift and its shutter replaced; G.cam follows the camera origin."""
-    sc = _set_order(to_scene(G, keep), G, keep)
-    if cam_shift is not None:
-        for f in ("origin", "lower_left_corner"):
-            v = getattr(sc.camera, f)
-            for k in range(3):
-                v[k] += float(cam_shift[k])
-    if shutter is not None:
-        sc.camera.t0, sc.camera.t1 = shutter
-    G.cam = np.array(sc.camera.origin[:])
-    return sc
-
-
-def _copy(G):
-    return ai.Geometry(G.sph.copy(), G.mov.copy(), G.tri.copy(), G.pmat.copy(), list(G.mats), G.cam.copy())
-
-
-def _points(G):
-    """Every point of the geometry as [n][3] views' sources: (sphere centres, c0, c1, triangle vertices)."""
-    return [G.sph[:, 0:3], G.mov[:, 0:3], G.mov[:, 3:6]] + [G.tri[:, 3 * v:3 * v + 3] for v in range(3)]
-
-
-def _extent(G):
-    pts = np.concatenate([p for p in _points(G) if len(p)])
-    lo, hi = pts.min(0), pts.max(0)
-    return lo, hi, float(max(np.max(hi - lo), 1e-3))
-
-
-def deform(G, f, radius=None):
-    """A copy of G with f applied to every point ([n][3] -> [n][3]) and `radius` (|r| scale) to the radii."""
-    H = _copy(G)
-    H.sph[:, 0:3], H.mov[:, 0:3], H.mov[:, 3:6] = f(G.sph[:, 0:3]), f(G.mov[:, 0:3]), f(G.mov[:, 3:6])
-    for v in range(3):
-        H.tri[:, 3 * v:3 * v + 3] = f(G.tri[:, 3 * v:3 * v + 3])
-    if radius is not None:
-        H.sph[:, 3] *= radius
-        H.mov[:, 6] *= radius
-    return H
-
-
-def motions(G):
-    """name -> (Geometry, camera shift): the deformations every check runs."""
-    lo, hi, ext = _extent(G)
-    ctr = 0.5 * (lo + hi)
-    g = np.random.default_rng(5)
-    a = 0.6
-    rot = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
-    out = {
-        "translate": (deform(G, lambda p: p + np.array([0.7, -0.3, 0.2]) * ext), None),
-        "rotate": (deform(G, lambda p: (p - ctr) @ rot.T + ctr), None),
-        "jitter": (deform(G, lambda p: p + g.normal(scale=0.02 * ext, size=p.shape)), None),
-        "scale1000": (deform(G, lambda p: p * 1000.0, radius=1000.0), None),
-        "flatten": (deform(G, lambda p: np.c_[p[:, 0], np.full(len(p), ctr[1]), p[:, 2]]), None),
-        "camera": (_copy(G), np.array([1.5, 0.5, -2.0])),
-    }
-    if G.ns >= 2:
-        H = _copy(G)
-        H.sph[[0, G.ns - 1], 0:3] = G.sph[[G.ns - 1, 0], 0:3]
-        out["swap_spheres"] = (H, None)
-    if G.nm >= 1:
-        H = _copy(G)
-        H.mov[0, 3:6] = G.mov[0, 3:6] + np.array([0.3, 0.1, -0.2]) * ext
-        out["moving_c1"] = (H, None)
-    return out
-
-
-def wave(G, frame, frames=16, amp=0.05):
-    """A travelling sine wave along x, displacing y by amp x the extent (frame 0: unchanged)."""
-    lo, hi, ext = _extent(G)
-    ph = 2 * np.pi * frame / frames
-    return deform(G, lambda p: p + np.c_[np.zeros(len(p)), amp * ext * np.sin(2 * np.pi * (p[:, 0] - lo[0]) / ext + ph)
-                                         * (frame > 0), np.zeros(len(p))])
 
 
 def frame_of(ctx, cfg, stream=0):
@@ -165,28 +39,6 @@ def frame_of(ctx, cfg, stream=0):
     ctx.render_device(cfg, buf.data_ptr(), stream, False)
     torch.cuda.synchronize()
     return buf.cpu().numpy()
-
-
-def rays_for(G, n, seed):
-    """Camera rays toward the scene, random rays through its box, shadow rays (tmax 1) toward a light above it."""
-    lo, hi, ext = _extent(G)
-    g = np.random.default_rng(seed)
-    tgt = g.uniform(lo, hi, size=(n, 3))
-    cam = rtow.make_rays(np.repeat(G.cam[None], n, 0), tgt - G.cam, time=g.random(n))
-    o = g.uniform(lo - 0.2 * ext, hi + 0.2 * ext, size=(n, 3))
-    d = g.normal(size=(n, 3))
-    rnd = rtow.make_rays(o, d, time=g.random(n))
-    light = 0.5 * (lo + hi) + np.array([0.2, 1.5, 0.1]) * ext
-    sh = rtow.make_rays(tgt, light - tgt, time=g.random(n), tmax=1.0)
-    return np.concatenate([cam, rnd, sh])
-
-
-def assert_hits_equal(a, b, what):
-    for f in ("t", "point", "normal", "prim", "kind", "material", "front_face"):
-        x, y = a[f], b[f]
-        same = (x == y) | (np.isnan(x) & np.isnan(y)) if x.dtype.kind == "f" else x == y
-        bad = np.nonzero(~same.reshape(len(a), -1).all(axis=1))[0]
-        assert len(bad) == 0, (what, f, len(bad), bad[:5])
 
 
 # ------------------------------------------------------------------------------- 1. unchanged refit, host builder ---
@@ -486,12 +338,6 @@ def test_twenty_refits_then_the_strict_frame_equals_the_oracle(rctx, builder):
 
 
 # --------------------------------------------------------------------------------------- 9. fast and f32 builds ---
-def block_means(a, b=16):
-    h, w, _ = a.shape
-    h, w = h // b * b, w // b * b
-    return a[:h, :w].reshape(h // b, b, w // b, b, 3).mean(axis=(1, 3))
-
-
 @pytest.mark.parametrize("builder", list(BUILDERS))
 @pytest.mark.parametrize("name", ["cover_moving", "suzanne"])
 def test_fast_and_f32_after_refit_match_a_fresh_upload(rctx, fresh, name, builder):

@@ -17,7 +17,7 @@ import pytest
 
 import rtow
 import sample_audit as sa
-from test_tile_order_host import tile_order
+from support_oracle import tile_order
 
 pytestmark = pytest.mark.gpu
 

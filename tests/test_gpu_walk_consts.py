@@ -16,8 +16,7 @@ import torch
 
 import accel_images as ai
 import rtow
-from test_gpu_accel_images import to_scene
-from test_gpu_flat_grid import look_at, sphere_scene
+from support_scenes import look_at, sphere_scene, to_scene
 
 pytestmark = pytest.mark.gpu
 

@@ -1,8 +1,8 @@
 """Self-tests of the guide-buffer checker (tests/guides_exact.py), no GPU.
 
-The buffer under test is the oracle's: the logged primaries of the three guide scenes (guides_ref.logged_render /
+The buffer under test is the oracle's: the logged primaries of the three guide scenes (support_oracle.logged_render /
 primaries), the oracle's own hit test on them (the hittable list's closest hit: the log's t_hit, with the record of
-test_gpu_query.SceneView.oracle_hit; test_gpu_query.brute_force on a sample of the rays confirms the shortcut below), the
+support_scenes.SceneView.oracle_hit; support_oracle.brute_force on a sample of the rays confirms the shortcut below), the
 oracle's sky (summed, the oracle's image bit for bit), folded by guides_ref.fold_guides.  The checker must accept it under
 STRICT and under FAST with the widened band, stay inside the 1 % cap on undecided pixels, and reject every planted fault
 with the right pixel and field.
@@ -14,10 +14,9 @@ import pytest
 
 import guides_exact as gx
 import rtow
-from guides_ref import fold_guides, guide_values, same_bits, sum_in_order
-from test_gpu_exact_guides import CAP, Parts, within_cap
-from test_gpu_guides import SCENES, Logged
-from test_gpu_query import SceneView, brute_force
+from guides_ref import CAP, SCENES, Logged, Parts, fold_guides, guide_values, within_cap
+from support_oracle import brute_force, same_bits, sum_in_order
+from support_scenes import SceneView
 
 BUILDS = [gx.STRICT, gx.FAST]
 

@@ -7,6 +7,7 @@ import pytest
 
 import orc
 import rtow
+from support_scenes import write_mesh_obj
 
 _pd = C.POINTER(C.c_double)
 
@@ -228,15 +229,7 @@ def test_checker_tree_gives_the_reference_tree_image_bit_for_bit(kind):
 
 
 def test_checker_tree_on_the_subdivided_mesh(tmp_path):
-    import subprocess
-    import sys
-
-    from conftest import REPO
-
-    obj = tmp_path / "mesh.obj"
-    subprocess.run([sys.executable, str(REPO / "scripts" / "make_mesh.py"), str(obj), "10"], check=True,
-                   capture_output=True)
-    scene = orc.OrcScene.obj(obj, 16 / 9)
+    scene = orc.OrcScene.obj(write_mesh_obj(tmp_path), 16 / 9)
     assert scene.c.n_triangles == 96800
     cfg = rtow.make_config(1920, 1080, 1, 1, 20, seed=2, rank=137, nranks=540, tile_rows=2)
     a, sa = orc.render(scene, cfg, orc.RNG_PHILOX, nthreads=8)

@@ -14,10 +14,10 @@ import pytest
 import accel_images as ai
 import point_ref as pr
 import rtow
-import test_gpu_exact_points as xp
+import point_cases as xp
 from conftest import REPO
-from test_gpu_query import LOGGED, SceneView, handmade_scene, log_rays
-from test_gpu_refit import motions
+from support_oracle import LOGGED, log_rays
+from support_scenes import SceneView, handmade_scene, motions
 
 
 def test_point_query_symbols_are_exported_and_declared():
@@ -151,7 +151,7 @@ def test_bound_is_finite_for_well_shaped_triangles(prec):
 
 # ---- the checker of whole answers (point_ref.check_answers) on the scenes and point sets of test_gpu_exact_points.py ----
 class _Logged(dict):
-    """test_gpu_query's `logged` fixture, one scene at a time (the oracle renders on the CPU)."""
+    """support_fixtures' `logged` fixture, one scene at a time (the oracle renders on the CPU)."""
 
     def __missing__(self, name):
         mk, w, h, spp, depth, seed = LOGGED[name]

@@ -5,24 +5,12 @@ primitive — the table a permutation of the rank's tiles with the empty ones at
 
 The brute force is this file's own binary64 closest-hit test in numpy (spheres by the discriminant, triangles by
 Moeller-Trumbore), independent of the cones the classification uses."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import rtow
 from conftest import GOLDEN
-
-
-def tile_order(scene, cfg):
-    L = rtow.lib()
-    cap = 1 << 16
-    table, empty = (C.c_uint32 * cap)(), (C.c_ubyte * cap)()
-    ne, tw, th = C.c_int32(), C.c_int32(), C.c_int32()
-    n = L.rtow_debug_tile_order(C.byref(scene.c), C.byref(cfg), table, empty, cap, C.byref(ne), C.byref(tw), C.byref(th))
-    if n < 0:
-        rtow.check(n, "rtow_debug_tile_order")
-    return np.array(table[:n], dtype=np.int64), np.array(empty[:n], dtype=bool), ne.value, tw.value, th.value
+from support_oracle import tile_order
 
 
 def _prims(s, times):

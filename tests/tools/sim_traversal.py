@@ -10,7 +10,6 @@ trip, a lane walks its pixel's samples), and counts, per wave trip:
   per-lane : every lane walks the BVH itself; SIMT cost = max over lanes
 Test-side tooling (it uses the oracle, so it lives under tests/); it only informs DESIGN.md.
 """
-import ctypes as C
 import sys
 from pathlib import Path
 
@@ -21,19 +20,7 @@ sys.path.insert(0, str(ROOT / "tests"))
 sys.path.insert(0, str(ROOT / "raytracing-one-weekend_amd"))
 import orc  # noqa: E402
 import rtow  # noqa: E402
-
-
-def log_rays(scene, cfg, cap=4_000_000):
-    buf = np.zeros((cap, 12))
-    L = orc.lib()
-    L.orc_set_raylog.argtypes = [C.POINTER(C.c_double), C.c_uint64]
-    L.orc_set_raylog.restype = None
-    L.orc_raylog_count.restype = C.c_uint64
-    L.orc_set_raylog(buf.ctypes.data_as(C.POINTER(C.c_double)), cap)
-    orc.render(scene, cfg, orc.RNG_PHILOX, nthreads=1)
-    n = L.orc_raylog_count()
-    L.orc_set_raylog(None, 0)
-    return buf[:n].copy()
+from support_oracle import log_rays  # noqa: E402
 
 
 def build_bvh(bmin, bmax, leaf_max=4, bins=16):
@@ -165,7 +152,7 @@ def main():
         nprims, per_test = len(tri), 45
         ptest = lambda p, o, d, a, tmax: tri_t(tri[p, 0], tri[p, 1], tri[p, 2], o, d, tmax)
         stride = 45
-    rays = log_rays(scene, cfg)
+    rays = log_rays(scene, cfg, cap=4_000_000)
     print("segments logged:", len(rays))
     rows = [i for i in range(H) if (i // 8) % stride == 0]
     bvh = build_bvh(bmin, bmax)
