@@ -484,7 +484,7 @@ int rtow_first_hits(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow
  * record's r^2; triangle {a + s e1 + t e2 : s, t >= 0, s + t <= 1} with e1 = B - A, e2 = C - A rounded.  The radius is
  * R = sqrt(|r^2|) (correctly rounded), so a negative radius (hollow glass) is the same surface; the distance to a sphere is
  * | |p - c| - R |, and p at the centre reports c + (R, 0, 0).  A degenerate triangle answers as its edges do; no result
- * is ever NaN for a finite p.  Formulas: csrc/rtow_pointq.h.
+ * is ever NaN for a finite p.  Formulas: csrc/rtow_point_walks.h (the kernel: csrc/rtow_pointq.h).
  *
  *   precision  RTOW_F64_STRICT: dist and point are bit-identical to those formulas evaluated in IEEE binary64 in their
  *                               written order (tests/point_ref.py mirrors them), under every kernel and with either
@@ -546,6 +546,52 @@ int rtow_closest_point_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, 
 /* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
 int rtow_closest_point(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
                        rtow_point_hit_t *hits, rtow_stats_t *stats);
+
+/* ---- k-nearest-primitive (ordered distance) queries ------------------------------------------------------------------
+ * "What are the k nearest surfaces to this point, nearest first?" — proximity and contact candidates, blending from the
+ * few nearest faces, thickness and clearance (first and second nearest), picking near a crease — in one launch.  Queries
+ * are rtow_point_query_t and results rtow_point_hit_t, as for rtow_closest_point.
+ *
+ *   set        For query i, N is the set of primitives whose distance is <= max_dist, the distance computed by the
+ *              formulas of rtow_closest_point in the same written order (csrc/rtow_point_walks.h): ONE entry per primitive.
+ *   order      N ascending by (dist, insertion index) — the insertion index is rtow_point_hit_t::prim.  The tie rule is
+ *              part of the contract, as in rtow_first_hits: it makes the strict answer independent of kernel, builder
+ *              and scheduling, also when a tie straddles slot k.
+ *   output     counts[i] = min(|N|, k); hits[i][j] for j < counts[i] is exactly the record rtow_closest_point would write
+ *              for that primitive (dist, point, insertion index, kind, material); slots j >= counts[i] hold the miss
+ *              record (dist = +inf, point 0, prim = kind = material = -1).  All k slots of every query are written;
+ *              nothing is written beyond n * k records or beyond n counts.  d_counts may be NULL.
+ *   k          1 .. RTOW_MAX_NEAREST; outside that range: RTOW_EINVAL.  k == 1 is rtow_closest_point's answer with the
+ *              tie resolved to the lowest insertion index: the same dist always, and the same record whenever both name
+ *              the same primitive.  (rtow_closest_point may name any primitive of an exact tie, with that primitive's
+ *              point: two triangles tie exactly along a shared edge, and their points there may differ in the last
+ *              bits.  Its record is then a later entry of this query's list, at the same dist.)
+ *   max_dist   inclusive, and the walk's starting search radius; NaN or negative: count 0 without a walk; +inf:
+ *              unbounded.  Once k entries are kept, the search radius is the distance of entry k - 1, and every member of
+ *              a tie at that radius is still visited: a box is pruned only beyond (radius + sigma)^2 with the slack sigma
+ *              of the closest-point walks, which is above every rounding of a computed distance.  The radius only shrinks.
+ *   precision  RTOW_F64_STRICT: bit-identical to the definition above evaluated with the formulas' mirror
+ *                               (tests/point_ref.py, tests/nearest_ref.py) under BRUTE, BVH, BVH4 and AUTO, with GRID
+ *                               answered by BVH, with either builder, after a refit, for time in [0, 1];
+ *              RTOW_F64_FAST:   every reported (dist, prim) meets rtow_closest_point's distance band and point clauses for
+ *                               that primitive; dist is non-decreasing; the primitives are distinct; entries with
+ *                               bit-equal dist come in insertion order; and the list is complete up to the bands: for
+ *                               every unreported primitive c with exact distance D(c) and upper band up(c),
+ *                               D(c) + up(c) >= dist[k - 1] when count == k, and D(c) + up(c) >= max_dist when count < k.
+ *                               The fast answer is not promised to be the same under every kernel;
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ * Overflow, the kernel rules (AUTO, GRID answered by BVH, the BVH4 fallback, RTOW_ENOSCENE after a lean upload,
+ * RTOW_KERNEL_REFTREE: RTOW_EINVAL), the stream ordering, stats (segments = n) and errors are those of
+ * rtow_closest_point_device.  d_queries and d_hits (n * k rtow_point_hit_t) are DEVICE pointers, 16-byte aligned;
+ * d_counts: n int32_t, 4-byte aligned, or NULL.  n == 0 launches nothing.  One call in flight per context; the render
+ * path (profile ring, dropped-sample word) is not involved. */
+#define RTOW_MAX_NEAREST 8
+int rtow_nearest_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const void *d_queries, int64_t n,
+                        int32_t k, void *d_hits /* rtow_point_hit_t[n][k] */, void *d_counts /* int32_t[n] or NULL */,
+                        void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
+int rtow_nearest(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
+                 int32_t k, rtow_point_hit_t *hits, int32_t *counts /* or NULL */, rtow_stats_t *stats);
 
 /* ---- radiance queries ---------------------------------------------------------------------------------------------------
  * "How much light arrives along this ray?" — the reference's ray_color (src/render.cpp:112-129) for caller rays: light

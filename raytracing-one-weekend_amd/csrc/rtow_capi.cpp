@@ -94,6 +94,12 @@ using FirstHitsLaunchFn = int(const TraceParams &p, const void *rays, void *hits
                               int block, unsigned lds_bytes, void *stream);
 FirstHitsLaunchFn launch_first_hits_strict, launch_first_hits_fast;
 QueryOccupancyFn first_hits_occupancy_strict, first_hits_occupancy_fast;
+// csrc/rtow_nearest_{strict,fast}.hip (rtow_nearest.h): the k-nearest query — k records and one count per point
+using NearestLaunchFn = int(const TraceParams &p, const void *queries, void *hits, int32_t *counts, uint32_t n, int32_t k,
+                            const int32_t *map, unsigned long long *counters, int kernel, int grid, int block,
+                            unsigned lds_bytes, void *stream);
+NearestLaunchFn launch_nearest_strict, launch_nearest_fast;
+QueryOccupancyFn nearest_occupancy_strict, nearest_occupancy_fast;
 // csrc/rtow_radiance_{strict,fast}.hip (rtow_radiance.h): the radiance query; `p` carries the seed, max_child_rays and
 // the strict build's path stack beside the walks' fields
 using RadianceLaunchFn = int(const TraceParams &p, const void *rays, const void *ids, void *out, uint32_t n,
@@ -1288,6 +1294,62 @@ static int first_hits_host(rtow_ctx *c, int32_t precision, int32_t kernel, const
   return RTOW_OK;
 }
 
+// The k-nearest query (rtow_nearest*, csrc/rtow_nearest.h): the closest-point query's checks, strategy
+// (resolve_point_kernel), launch shape, ordering, stats and id translation around a kernel that writes k records and one
+// count per point.  k is checked before anything else is looked at.  BRUTE uses no LDS (its walk reads the class-major
+// arrays).
+static int nearest_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_queries, int64_t n, int32_t k,
+                          void *d_hits, void *d_counts, void *hip_stream, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (k < 1 || k > RTOW_MAX_NEAREST) return fail(RTOW_EINVAL, "k %d outside [1, %d]", k, RTOW_MAX_NEAREST);
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n %lld outside [0, 2^31 - 64]", (long long)n);
+  if (n > 0 && (!d_queries || !d_hits)) return fail(RTOW_EINVAL, "NULL query or hit buffer");
+  if (((uintptr_t)d_queries & 15u) != 0u) return fail(RTOW_EINVAL, "query buffer must be 16-byte aligned");
+  if (((uintptr_t)d_hits & 15u) != 0u) return fail(RTOW_EINVAL, "hit buffer must be 16-byte aligned");
+  if (((uintptr_t)d_counts & 3u) != 0u) return fail(RTOW_EINVAL, "count buffer must be 4-byte aligned");
+  QueryRun q;
+  int rc;
+  if ((rc = query_begin(c, precision, kernel_req, stats, q, true))) return rc;
+  if (n == 0) return RTOW_OK;
+
+  const int kernel = q.kernel;
+  const int32_t *map = nullptr;
+  if ((rc = query_map_for(c, kernel, &map))) return rc;
+  const int block = q.shape.block;
+  const unsigned lds = kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;
+  const int build = q.strict ? 0 : 1;
+  rtow::NearestLaunchFn *const launch[2] = {rtow::launch_nearest_strict, rtow::launch_nearest_fast};
+  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::nearest_occupancy_strict, rtow::nearest_occupancy_fast};
+  const int occ = occupancy[build](kernel, block, lds, nullptr);
+  return query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
+    return launch[build](P, d_queries, d_hits, (int32_t *)d_counts, (uint32_t)n, k, map, counters, kernel, grid, block, lds,
+                         hip_stream);
+  });
+}
+
+static int nearest_host(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
+                        int32_t k, rtow_point_hit_t *hits, int32_t *counts, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (k < 1 || k > RTOW_MAX_NEAREST) return fail(RTOW_EINVAL, "k %d outside [1, %d]", k, RTOW_MAX_NEAREST);
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n %lld outside [0, 2^31 - 64]", (long long)n);
+  if (n > 0 && (!queries || !hits)) return fail(RTOW_EINVAL, "NULL query or hit array");
+  if (n == 0) return nearest_device(c, precision, kernel, nullptr, 0, k, nullptr, nullptr, nullptr, stats);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t hit_bytes = (size_t)n * (size_t)k * sizeof(rtow_point_hit_t);
+  int rc;
+  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_point_query_t))) || (rc = c->q_khits.ensure(hit_bytes)) ||
+      (counts && (rc = c->q_kcounts.ensure((size_t)n * sizeof(int32_t)))))
+    return rc;
+  HIPCHK(hipMemcpy(c->q_rays.p, queries, (size_t)n * sizeof(rtow_point_query_t), hipMemcpyHostToDevice));
+  if ((rc = nearest_device(c, precision, kernel, c->q_rays.p, n, k, c->q_khits.p, counts ? c->q_kcounts.p : nullptr, nullptr,
+                           stats)))
+    return rc;
+  HIPCHK(hipMemcpy(hits, c->q_khits.p, hit_bytes, hipMemcpyDeviceToHost));
+  if (counts) HIPCHK(hipMemcpy(counts, c->q_kcounts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return RTOW_OK;
+}
+
 // The radiance query (rtow_radiance*, csrc/rtow_radiance.h): the ray queries' strategy, launch shape, ordering and stats
 // (query_begin / query_launch) around a kernel that traces whole paths.  The launch fills what the paths need beyond the
 // walks' fields: the Philox key, the depth and — strict build — a path stack of its own, sized for this launch's lanes.
@@ -1678,6 +1740,16 @@ int rtow_closest_point_device(rtow_ctx *c, int32_t precision, int32_t kernel, co
 int rtow_closest_point(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
                        rtow_point_hit_t *hits, rtow_stats_t *stats) {
   return guarded("rtow_closest_point", [&] { return query_host(c, kClosestPoint, precision, kernel, queries, n, hits, stats); });
+}
+int rtow_nearest_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_queries, int64_t n, int32_t k,
+                        void *d_hits, void *d_counts, void *hip_stream, rtow_stats_t *stats) {
+  return guarded("rtow_nearest_device", [&] {
+    return nearest_device(c, precision, kernel, d_queries, n, k, d_hits, d_counts, hip_stream, stats);
+  });
+}
+int rtow_nearest(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n, int32_t k,
+                 rtow_point_hit_t *hits, int32_t *counts, rtow_stats_t *stats) {
+  return guarded("rtow_nearest", [&] { return nearest_host(c, precision, kernel, queries, n, k, hits, counts, stats); });
 }
 int rtow_first_hits_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays,
                            int32_t max_hits, void *d_hits, void *d_counts, void *hip_stream, rtow_stats_t *stats) {

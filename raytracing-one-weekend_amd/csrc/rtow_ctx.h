@@ -285,7 +285,7 @@ struct rtow_ctx {
   DevBuf q_counters, q_spill, q_rays, q_hits, q_occ, q_map[3];
   DevBuf q_stack, q_ids, q_rgb;  // rtow_radiance*: the strict build's path stack (sized per launch), the host form's staging
   DevBuf q_guides;               // rtow_guides: the host form's staging (rtow_camera_rays stages in q_rays / q_ids)
-  DevBuf q_khits, q_kcounts;     // rtow_first_hits: the host form's staging (its rays go through q_rays)
+  DevBuf q_khits, q_kcounts;     // rtow_first_hits, rtow_nearest: the host forms' staging (their inputs go through q_rays)
   bool q_map_ok[3] = {false, false, false};
   hipEvent_t q_ev[4] = {};
   unsigned long long *h_qcounters = nullptr;

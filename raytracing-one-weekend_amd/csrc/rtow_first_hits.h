@@ -15,8 +15,8 @@
 // every strategy, builder and schedule.
 //
 // The list: 8 (t, walk id) pairs per lane in registers, sorted by (t, insertion index); insertion is a fully unrolled
-// compare-and-shift over eight named slots (no scratch: see HitList).  The insertion index (`map[id]`) is read only to break an
-// exact tie in t and at output.  A candidate whose primitive is already in the list is dropped: the grid lists a
+// compare-and-shift over eight named slots (no scratch: see rtow_sorted_list.h).  The insertion index (`map[id]`) is
+// read only to break an exact tie in t and at output.  A candidate whose primitive is already in the list is dropped: the grid lists a
 // primitive in every cell it overlaps (the one-entry mailbox of leaf_test catches only consecutive repeats).  A primitive
 // tested again after it was evicted is rejected by the ordering itself.  Slots at and beyond max_hits may hold entries
 // past the cut (the list always sorts 8); they are not reported.
@@ -48,6 +48,7 @@ namespace {
 #include "rtow_kernel_frame.h"
 #include "rtow_bounded_walks.h"
 #include "rtow_hit_record.h"
+#include "rtow_sorted_list.h"
 
 struct FirstHitsParams {
   TraceParams P;               // the scene (P.sc) and the walks' launch fields: spill, n_lanes, leaf_votes
@@ -60,76 +61,10 @@ struct FirstHitsParams {
   unsigned long long *counters;  // [0] primitive tests, [1] node tests
 };
 
-// ---- the per-lane list ----
-// Eight named slots, not arrays: the compiler folds a chain of selects over array elements into one dynamically indexed
-// load, which sends the whole list to scratch; named members are registers from the first pass on.
-#define RTOW_FH_SLOTS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
-struct HitList {
-  double t0, t1, t2, t3, t4, t5, t6, t7;  // ascending by (t, map[id]); an empty slot holds the ray's tmax (no kept t is above it)
-  int i0, i1, i2, i3, i4, i5, i6, i7;     // walk ids; -1 = empty slot (empty slots are a suffix)
-};
-// `tmax` in the walk's ray parameter
-__device__ __forceinline__ void list_clear(HitList &L, double tmax) {
-#define RTOW_FH_X(j) L.t##j = tmax, L.i##j = -1;
-  RTOW_FH_SLOTS(RTOW_FH_X)
-#undef RTOW_FH_X
-}
-// The culling bound: the t of slot max_hits - 1 — tmax while fewer than max_hits entries are kept (an empty slot holds
-// it, so the walk keeps no copy of tmax), then the t of the last entry that will be reported.
-__device__ __forceinline__ double list_bound(const HitList &L, int max_hits) {
-  double b = L.t7;
-#define RTOW_FH_X(j) if (max_hits == j + 1) b = L.t##j;
-  RTOW_FH_SLOTS(RTOW_FH_X)
-#undef RTOW_FH_X
-  return b;
-}
-// Entry j of the list (wave-uniform j).  (The empty asm keeps the selects a chain: left alone, the compiler parks the
-// eight t in scratch and loads slot j from there.)
-__device__ __forceinline__ void list_entry(const HitList &L, int j, double &t, int &id) {
-  t = L.t7, id = L.i7;
-#define RTOW_FH_X(k)                  \
-  if (j == k) t = L.t##k, id = L.i##k; \
-  asm volatile("" : "+v"(t), "+v"(id));
-  RTOW_FH_SLOTS(RTOW_FH_X)
-#undef RTOW_FH_X
-}
-// Inserts (t, id) in (t, map[id]) order by compare-and-shift over the eight slots; the entry pushed out of slot 7, or
-// the candidate itself, is dropped.
-// DEDUP: drop a candidate whose primitive is already kept (the grid; a tree holds every primitive once).
-template <bool DEDUP>
-__device__ __forceinline__ void list_insert(HitList &L, double t, int id, const int32_t *map) {
-  if constexpr (DEDUP) {
-    bool dup = false;
-#define RTOW_FH_X(j) dup = dup || L.i##j == id;
-    RTOW_FH_SLOTS(RTOW_FH_X)
-#undef RTOW_FH_X
-    if (dup) return;
-  }
-  // b<j>: entry j stays in front of the candidate (a prefix of the list, which is sorted); an exact tie in t is decided
-  // by the insertion index
-#define RTOW_FH_X(j)                                              \
-  bool b##j = L.t##j < t;                                         \
-  if (L.t##j == t && L.i##j >= 0) b##j = map[L.i##j] < map[id];
-  RTOW_FH_SLOTS(RTOW_FH_X)
-#undef RTOW_FH_X
-#define RTOW_FH_SHIFT(j, jm)            \
-  if (!b##j) {                          \
-    L.t##j = b##jm ? t : L.t##jm;       \
-    L.i##j = b##jm ? id : L.i##jm;      \
-  }
-  RTOW_FH_SHIFT(7, 6)
-  RTOW_FH_SHIFT(6, 5)
-  RTOW_FH_SHIFT(5, 4)
-  RTOW_FH_SHIFT(4, 3)
-  RTOW_FH_SHIFT(3, 2)
-  RTOW_FH_SHIFT(2, 1)
-  RTOW_FH_SHIFT(1, 0)
-#undef RTOW_FH_SHIFT
-  if (!b0) {
-    L.t0 = t;
-    L.i0 = id;
-  }
-}
+// ---- the per-lane list (rtow_sorted_list.h, keyed by t) ----
+// An empty slot holds the ray's tmax in the walk's ray parameter; a candidate whose primitive is already kept is dropped
+// in a grid cell (DEDUP: the grid lists a primitive in every cell it overlaps; a tree holds every primitive once).
+using HitList = SortedList8;
 // What a walk does with the outcome of one primitive's test against Closest{bound, -1}.
 template <bool DEDUP>
 __device__ __forceinline__ void list_take(HitList &L, const Closest &c, const int32_t *map, int max_hits, double &bound) {

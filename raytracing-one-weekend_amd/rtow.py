@@ -26,6 +26,7 @@ PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_TRIANGLE = 0, 1, 2
 F64_STRICT, F64_FAST, F32 = 0, 1, 2
 KERNEL_AUTO, KERNEL_BRUTE, KERNEL_BVH, KERNEL_GRID, KERNEL_BVH4, KERNEL_REFTREE = 0, 1, 2, 3, 4, 5
 MAX_HITS = 8  # RTOW_MAX_HITS: the most entries rtow_first_hits keeps per ray
+MAX_NEAREST = 8  # RTOW_MAX_NEAREST: the most entries rtow_nearest keeps per point
 SPEC_GENERIC, SPEC_STATIC_SPHERES, SPEC_MOVING_SPHERES, SPEC_FLAT_Y = 0, 1, 2, 4  # Context.last_spec()
 MODEL_OO, MODEL_VARIANT, MODEL_WORLD = 0, 1, 2  # scene models of the host scene scripts (include/rtow.h)
 BUILDER_HOST_SAH, BUILDER_DEVICE_LBVH, BUILDER_AUTO = 0, 1, 2
@@ -199,7 +200,7 @@ EXPORTS = [
     "rtow_scene_refit", "rtow_refit_info", "rtow_closest_point_device", "rtow_closest_point",
     "rtow_debug_tile_order", "rtow_radiance_device", "rtow_radiance",
     "rtow_camera_rays_device", "rtow_camera_rays", "rtow_camera_ray_count", "rtow_guides_device", "rtow_guides",
-    "rtow_debug_last_spec", "rtow_first_hits_device", "rtow_first_hits",
+    "rtow_debug_last_spec", "rtow_first_hits_device", "rtow_first_hits", "rtow_nearest_device", "rtow_nearest",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -296,6 +297,11 @@ def lib():
                                                 C.c_void_p, C.POINTER(Stats)]
         L.rtow_closest_point.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                          C.POINTER(Stats)]
+    if hasattr(L, "rtow_nearest"):
+        L.rtow_nearest_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rtow_nearest.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.POINTER(Stats)]
     if hasattr(L, "rtow_radiance"):
         L.rtow_radiance_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RadianceParams), C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
@@ -616,6 +622,30 @@ class Context:
         check(lib().rtow_closest_point_device(self._h, precision, kernel, C.c_void_p(d_q), n, C.c_void_p(d_hits),
                                               C.c_void_p(stream), C.byref(st) if st is not None else None),
               "rtow_closest_point_device")
+        return st
+
+    def nearest(self, queries, k, precision=F64_FAST, kernel=KERNEL_AUTO, want_stats=False):
+        """The `k` (1 .. MAX_NEAREST) primitives nearest to every point (a POINT_QUERY_DTYPE array, host memory) within
+        its max_dist, ordered by (dist, insertion index): (hits, counts) — an [n, k] POINT_HIT_DTYPE array whose unused
+        slots hold the miss record, and int32 [n] — plus Stats with `want_stats` (rtow_nearest)."""
+        q = np.ascontiguousarray(queries, dtype=POINT_QUERY_DTYPE).reshape(-1)
+        hits = np.empty((len(q), max(int(k), 0)), dtype=POINT_HIT_DTYPE)
+        counts = np.empty(len(q), dtype=np.int32)
+        st = Stats() if want_stats else None
+        check(lib().rtow_nearest(self._h, precision, kernel, q.ctypes.data_as(C.c_void_p), len(q), int(k),
+                                 hits.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                 C.byref(st) if st is not None else None), "rtow_nearest")
+        return (hits, counts, st) if want_stats else (hits, counts)
+
+    def nearest_device(self, d_q: int, n: int, k: int, d_hits: int, d_counts: int = 0, precision=F64_FAST,
+                       kernel=KERNEL_AUTO, stream: int = 0, want_stats=False):
+        """The same on device buffers (raw pointers: n x 48-byte queries and n x k x 48-byte hits, both 16-byte aligned,
+        n int32 counts or 0 for none), enqueued on `stream` (rtow_nearest_device); returns Stats with `want_stats` (then
+        synchronised), else None."""
+        st = Stats() if want_stats else None
+        check(lib().rtow_nearest_device(self._h, precision, kernel, C.c_void_p(d_q), n, int(k), C.c_void_p(d_hits),
+                                        C.c_void_p(d_counts) if d_counts else None, C.c_void_p(stream),
+                                        C.byref(st) if st is not None else None), "rtow_nearest_device")
         return st
 
     def radiance(self, rays, samples_per_ray=1, max_child_rays=50, seed=1, ids=None, sample_first=0, precision=F64_FAST,
