@@ -750,27 +750,40 @@ int upload_for(rtow_ctx *c, const rtow_scene_t *scene, const rtow_config_t *cfg)
 
 // Record slot of a leaf-ordered image -> class-order triangle index (which: 1 the host-built mesh BVH image, 2 the 4-wide
 // image).  The leaf-ordered images hold exact copies of the class-ordered triangle records, so a slot's triangle is found by
-// matching its 96 bytes (identical records — duplicate triangles — are paired in order: any one of them gives the same hit).
+// matching its 96 bytes AND its material word: a query reports a slot's material from the image's own per-slot table
+// (point_record, hit records), which follows the builder's permutation, so a slot is paired with a triangle equal in both —
+// coincident triangles with different materials (a decal over a wall) keep each its own.  Triangles identical in record
+// and material are paired in order: any one of them gives the same hit.  Called on the images as uploaded, while
+// c->prim_mat is still the upload's (refit_prepare runs before the refit's records stage).
 int match_slots(rtow_ctx *c, int which, std::vector<int32_t> &slot2tri) {
   const int nt = c->ds.n_tri;
   const unsigned char *img = which == 1 ? c->ds.blob + c->ds.off_tri : c->ds.blob4 + c->ds.b4_off_tri;
+  const unsigned char *img_mat = which == 1 ? c->ds.blob + c->ds.off_pmat : c->ds.blob4 + c->ds.b4_off_pmat;
   const size_t bytes = (size_t)nt * 96u;
   std::vector<unsigned char> rec_cls(bytes), rec_img(bytes);
+  std::vector<int32_t> mat_cls((size_t)nt), mat_img((size_t)nt);
   HIPCHK(hipMemcpy(rec_cls.data(), c->tri.p, bytes, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(rec_img.data(), img, bytes, hipMemcpyDeviceToHost));
+  if (nt) {
+    HIPCHK(hipMemcpy(mat_cls.data(), (const int32_t *)c->prim_mat.p + c->ds.n_sph + c->ds.n_mov, (size_t)nt * 4,
+                     hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mat_img.data(), img_mat, (size_t)nt * 4, hipMemcpyDeviceToHost));
+  }
   std::vector<int32_t> oc((size_t)nt), oi((size_t)nt);
   for (int i = 0; i < nt; ++i) oc[i] = oi[i] = i;
-  auto by_record = [](const std::vector<unsigned char> &r) {
-    return [&r](int32_t a, int32_t b) {
+  auto by_record = [](const std::vector<unsigned char> &r, const std::vector<int32_t> &mat) {
+    return [&r, &mat](int32_t a, int32_t b) {
       const int m = std::memcmp(&r[(size_t)a * 96u], &r[(size_t)b * 96u], 96);
-      return m != 0 ? m < 0 : a < b;
+      if (m != 0) return m < 0;
+      return mat[(size_t)a] != mat[(size_t)b] ? mat[(size_t)a] < mat[(size_t)b] : a < b;
     };
   };
-  std::sort(oc.begin(), oc.end(), by_record(rec_cls));
-  std::sort(oi.begin(), oi.end(), by_record(rec_img));
+  std::sort(oc.begin(), oc.end(), by_record(rec_cls, mat_cls));
+  std::sort(oi.begin(), oi.end(), by_record(rec_img, mat_img));
   slot2tri.assign((size_t)nt, -1);
   for (int k = 0; k < nt; ++k) {
-    if (std::memcmp(&rec_cls[(size_t)oc[k] * 96u], &rec_img[(size_t)oi[k] * 96u], 96) != 0)
+    if (std::memcmp(&rec_cls[(size_t)oc[k] * 96u], &rec_img[(size_t)oi[k] * 96u], 96) != 0 ||
+        mat_cls[(size_t)oc[k]] != mat_img[(size_t)oi[k]])
       return fail(RTOW_EINVAL, "internal error: the %s image's triangle records are not those of the scene",
                   which == 1 ? "BVH" : "4-wide");
     slot2tri[(size_t)oi[k]] = oc[k];

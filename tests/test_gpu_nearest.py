@@ -17,6 +17,7 @@ import accel_images as ai
 import nearest_ref as nr
 import point_ref as pr
 import rtow
+from nearest_cases import assert_strict, cut
 from point_cases import KERNELS, point_sets
 from support_fixtures import big_mesh, logged, pctx  # noqa: F401
 from support_oracle import LOGGED, rays_of, same_bits
@@ -50,8 +51,8 @@ def case(name, logged, keep):
         G = ai.mesh_geometry(suzanne_tris(1), mats=GREYS)
         perm, rec, mats = nr.permuted_records(G, 3)
         return _set_order(to_scene(G, keep), G, keep, perm), rec, mats, None, (0.0,)
-    # (the edge meshes carry one material, as everywhere: bit-identical triangles — `coincident` — are told apart by
-    # nothing but their position in the upload, and the id translation of a leaf-ordered image matches records)
+    # (the edge meshes carry one material here; bit-identical triangles with different materials are the case of
+    # test_gpu_exact_nearest.py::test_material_follows_the_primitive_on_coincident_triangles)
     G = ai.mesh_geometry(ai.edge_meshes()[name]) if name in EDGE else ai.sphere_edge_scenes()[name]
     return scene_of(G, keep), pr.make_records(G.sph, G.mov, G.tri), G.pmat, None, (0.0,)
 
@@ -61,18 +62,6 @@ def sets_of(rec, log, tm, n=400):
     sets = point_sets(rec, log, n, 7)
     sets["special"] = (pr.surface_points(rec, tm, 11), math.inf)
     return sets
-
-
-def cut(ref8, k):
-    """The strict answer for k from the one for 8: the same sorted list, cut earlier."""
-    hits, counts = ref8
-    return np.ascontiguousarray(hits[:, :k]), np.minimum(counts, k).astype(np.int32)
-
-
-def assert_strict(got, want, what):
-    (h, c), (rh, rc) = got, want
-    assert np.array_equal(c, rc), (what, "counts", np.nonzero(c != rc)[0][:4].tolist())
-    assert nr.same_answers(h, rh), (what, nr.first_difference(h, rh))
 
 
 # ---------------------------------------------------------------------------------------------------- strict ---
