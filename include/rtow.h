@@ -312,6 +312,18 @@ int rtow_debug_schedule(rtow_ctx *ctx, const rtow_config_t *cfg, uint32_t *out_p
  * RTOW_ENOSCENE before the first launch. */
 int rtow_debug_last_spec(rtow_ctx *ctx, uint32_t *out_spec);
 
+/* Diagnostic only: whether the trace kernel of the last trace launch of `ctx` counted statistics (segments, node and
+ * primitive tests): 1, or 0 for the instantiation without them, which a render that passes stats == NULL launches where
+ * the kernel has one (the GRID scene-class kernels and the BVH4 trip kernels of the binary64 builds).  RTOW_COUNT_ALWAYS=1
+ * in the environment of rtow_ctx_create keeps 1.  RTOW_ENOSCENE before the first launch. */
+int rtow_debug_last_counted(rtow_ctx *ctx, uint32_t *out_counted);
+
+/* Diagnostic only: the constants block of the GRID walk the host derived from the resident grid image (48 32-bit words;
+ * csrc/rtow_walk_consts.h, GridWalkConsts: what the scene-class trace kernels read instead of the image header and the
+ * head of its large-primitive list).  Copies min(capacity_bytes, 192) bytes to `out` and returns the block's size in
+ * *out_bytes.  All zero when no grid image is resident.  RTOW_ENOSCENE before the first upload. */
+int rtow_debug_walk_consts(rtow_ctx *ctx, void *out, int32_t capacity_bytes, int32_t *out_bytes);
+
 /* Diagnostic only (pure host arithmetic, usable without a GPU): the order in which the work queue of a render of
  * `cfg` of `scene` runs its 64-pixel tiles.  table_out[queue position] = tile (row-major over this rank's tile rows;
  * the queue is consumed from its far end, so position 0 runs LAST), empty_out[tile] = 1 when no ray the camera can

@@ -932,9 +932,13 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
   if (slot >= 0) HIPCHK(hipEventRecord(c->ev[slot][0], st));
   int launch_kernel = kernel;
   if (image_kernel && lds_bytes > 0 && c->knobs.stamps) launch_kernel = kernel + 16;  // diagnostic
-  int lrc = strict ? rtow::launch_trace_strict(P, launch_kernel, (int)grid, block, lds_bytes, st)
-            : f32  ? rtow::launch_trace_f32(P, launch_kernel, (int)grid, block, lds_bytes, st)
-                   : rtow::launch_trace_fast(P, launch_kernel, (int)grid, block, lds_bytes, st);
+  // counters[1..3] are read below only for a caller that takes statistics: every other launch runs the instantiation
+  // without them where the kernel has one (rtow_trace_body.h, COUNT; RTOW_COUNT_ALWAYS keeps the counting one)
+  const bool want_count = stats != nullptr || c->knobs.count_always;
+  bool counted = true;
+  int lrc = strict ? rtow::launch_trace_strict(P, launch_kernel, (int)grid, block, lds_bytes, st, want_count, &counted)
+            : f32  ? rtow::launch_trace_f32(P, launch_kernel, (int)grid, block, lds_bytes, st, want_count, &counted)
+                   : rtow::launch_trace_fast(P, launch_kernel, (int)grid, block, lds_bytes, st, want_count, &counted);
 #ifdef RTOW_TAILSTAT
   if (const char *path = std::getenv("RTOW_TAILSTAT_OUT")) {
     HIPCHK(hipStreamSynchronize(st));
@@ -948,6 +952,7 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
 #endif
   if (lrc != 0) return fail(RTOW_EHIP, "trace kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
   c->last_spec = (int64_t)P.spec;
+  c->last_counted = counted ? 1 : 0;
   if (slot >= 0) {
     HIPCHK(hipEventRecord(c->ev[slot][1], st));
     c->ev_count++;
@@ -1577,6 +1582,23 @@ int rtow_debug_last_spec(rtow_ctx *c, uint32_t *out_spec) {
   if (!c || !out_spec) return fail(RTOW_EINVAL, "NULL argument");
   if (c->last_spec < 0) return fail(RTOW_ENOSCENE, "no launch yet");
   *out_spec = (uint32_t)c->last_spec;
+  return RTOW_OK;
+}
+
+// Diagnostic: whether that launch's kernel was a counting instantiation (rtow_trace_body.h, COUNT).
+int rtow_debug_last_counted(rtow_ctx *c, uint32_t *out_counted) {
+  if (!c || !out_counted) return fail(RTOW_EINVAL, "NULL argument");
+  if (c->last_counted < 0) return fail(RTOW_ENOSCENE, "no launch yet");
+  *out_counted = (uint32_t)c->last_counted;
+  return RTOW_OK;
+}
+
+// Diagnostic: the GRID walk's constants block as the last upload or refit derived it (TraceParams::walk).
+int rtow_debug_walk_consts(rtow_ctx *c, void *out, int32_t capacity_bytes, int32_t *out_bytes) {
+  if (!c || !out_bytes || capacity_bytes < 0 || (!out && capacity_bytes > 0)) return fail(RTOW_EINVAL, "NULL argument");
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  *out_bytes = (int32_t)sizeof c->grid_walk;
+  if (capacity_bytes > 0) std::memcpy(out, &c->grid_walk, std::min<size_t>((size_t)capacity_bytes, sizeof c->grid_walk));
   return RTOW_OK;
 }
 

@@ -139,6 +139,8 @@ struct Knobs {
   bool no_spec = false;           // RTOW_NO_SPEC: always the generic GRID kernel (A/B against the scene-class specialisations)
   bool no_flat = false;           // RTOW_NO_FLAT: the scene-class kernels keep the 3D walk on a grid with one layer in y (A/B and
                                   //   tests against the two-axis walk, kSpecFlatY)
+  bool count_always = false;      // RTOW_COUNT_ALWAYS: a render that returns no statistics launches the counting trace kernel all
+                                  //   the same (A/B of the two instantiations in one library)
   bool tile_order = true;         // RTOW_TILE_ORDER=0: the queue keeps the row order alone (one segment); default: the tiles through
                                   //   which no camera ray can reach a primitive are traced last (tile_classify)
   int empty_levels = 3;           // RTOW_EMPTY_LEVELS: levels of a tile one atomic buys in the queue's empty-tile segment (1..16)
@@ -196,6 +198,7 @@ struct Knobs {
     empty_levels = std::min(std::max(geti("RTOW_EMPTY_LEVELS", 3), 1), 16);
     no_spec = std::getenv("RTOW_NO_SPEC") != nullptr;
     no_flat = std::getenv("RTOW_NO_FLAT") != nullptr;
+    count_always = geti("RTOW_COUNT_ALWAYS", 0) != 0;
     stream_scalar = std::getenv("RTOW_STREAM_SCALAR") != nullptr;
     if (const char *e = std::getenv("RTOW_PLOC_RADIUS")) ploc_radius = std::min(std::max(std::atoi(e), 0), 64);
     if (const char *e = std::getenv("RTOW_DEVICE_TREE"))
@@ -232,6 +235,7 @@ struct rtow_ctx {
   int32_t grid_ny = 0;           // n[1] of the resident grid image's header (0: no grid); 1 selects the two-axis walk
   GridWalkConsts grid_walk{};    // the walk's constants from that header (rtow_walk_consts.h): TraceParams::walk
   int64_t last_spec = -1;        // TraceParams::spec of the last trace launch (rtow_debug_last_spec; -1: none yet)
+  int last_counted = -1;         // whether that launch's kernel counted statistics (rtow_debug_last_counted; -1: none yet)
   bool have_grid = false;
   uint32_t blob_bytes = 0;
   long long bvh_nodes = 0;

@@ -188,12 +188,14 @@ struct ReduceParams {
 // launchers, one pair per arithmetic mode (separate translation units compiled
 // with -ffp-contract=off / -ffp-contract=fast)
 // `lds_bytes` > 0 selects the variant that stages the scene blob in LDS
+// `count` false: the caller reads no statistics (counters[1..3]), and the kernels that have an instantiation without
+// them run it (rtow_trace_body.h, COUNT); `*counted` says whether the kernel launched counts
 int launch_trace_strict(const TraceParams &p, int kernel, int grid, int block, unsigned lds_bytes,
-                        void *stream);
+                        void *stream, bool count = true, bool *counted = nullptr);
 int launch_trace_fast(const TraceParams &p, int kernel, int grid, int block, unsigned lds_bytes,
-                      void *stream);
+                      void *stream, bool count = true, bool *counted = nullptr);
 int launch_trace_f32(const TraceParams &p, int kernel, int grid, int block, unsigned lds_bytes,
-                     void *stream);
+                     void *stream, bool count = true, bool *counted = nullptr);
 int trace_occupancy_strict(int kernel, int block, unsigned lds_bytes);
 int trace_occupancy_fast(int kernel, int block, unsigned lds_bytes);
 int trace_occupancy_f32(int kernel, int block, unsigned lds_bytes);

@@ -225,11 +225,25 @@ static void bvh4_resident(rtow_ctx *c, const rtow::Bvh4Image &img4, size_t bytes
 // "The grid image in c->gblob is resident" (gimg.ok), or "there is no grid": every upload and refit, host- or
 // device-built.  What the context remembers of the image comes from its 64-byte header: n[1] == 1 selects the two-axis
 // walk; the specialised trace kernels read the walk's constants from the block derived here instead of the header.
-static void grid_resident(rtow_ctx *c, const rtow::GridImage &gimg) {
+// The block also carries the head of the image's large-primitive list (fill_large_head): read from the image itself —
+// the host builder's copy of it, or, for an image built on the device, the sixteen bytes at the list's offset copied
+// back (a blocking copy behind the build kernels; only for an image the class kernels can run on: fat cell lists).
+// n_sph: static spheres of the scene the image was built from.
+static int grid_resident(rtow_ctx *c, const rtow::GridImage &gimg, int n_sph) {
   c->have_grid = gimg.ok;
   c->grid_fat_stride = (gimg.ok && gimg.off_fat) ? gimg.fat_stride : 0u;
   c->grid_ny = gimg.ok ? gimg.n[1] : 0;
   c->grid_walk = gimg.ok ? make_grid_walk_consts(gimg.header, gimg.off_ids, gimg.off_cells) : GridWalkConsts{};
+  if (gimg.ok && c->grid_walk.n_large != 0u && gimg.off_fat != 0u) {
+    uint32_t head[kWalkLargeFast] = {};
+    const size_t n = std::min<size_t>(c->grid_walk.n_large, kWalkLargeFast) * sizeof(uint32_t);
+    const size_t off_large = (size_t)gimg.off_ids + 4u * (size_t)c->grid_walk.large_first;
+    if (gimg.blob.size() >= off_large + n)
+      std::memcpy(head, gimg.blob.data() + off_large, n);
+    else
+      HIPCHK(hipMemcpy(head, (const unsigned char *)c->gblob.p + off_large, n, hipMemcpyDeviceToHost));
+    fill_large_head(c->grid_walk, head, n_sph, gimg.off_sph);
+  }
   c->gblob_bytes = gimg.ok ? (uint32_t)gimg.total_bytes : 0u;
   rtow::DevScene &ds = c->ds;
   ds.gblob = (const unsigned char *)c->gblob.p;
@@ -243,6 +257,7 @@ static void grid_resident(rtow_ctx *c, const rtow::GridImage &gimg) {
     d->g_off_cells = gimg.off_cells;
     d->g_off_ids = gimg.off_ids;
   }
+  return RTOW_OK;
 }
 
 // The f32 build's image fields (ds32 is otherwise a copy of ds).  grid false: the BVH image, in c->blob32; true: the
@@ -653,7 +668,7 @@ static int scene_upload(rtow_ctx *c, const rtow_scene_t *s, unsigned need) {
   if ((rc = build_grid(c, s->camera, rec, need, gimg, grid_on_device))) return rc;
   const double t_grid1 = now_ms();
   if (gimg.ok && !grid_on_device && (rc = upload(c->gblob, gimg.blob))) return rc;
-  grid_resident(c, gimg);
+  if ((rc = grid_resident(c, gimg, s->n_spheres))) return rc;
   // DevScene, the f32 build's images, camera
   publish_dev_scene(c, s, trees);
   c->ds32 = c->ds;
@@ -1012,7 +1027,7 @@ static int refit_grid_images(rtow_ctx *c, const rtow_scene_t *s, rtow::SceneReco
     rec.tri.resize((size_t)nt * 12);
     if ((rc = grid_device_build(c, s->camera, rec, gimg))) return rc;
   }
-  grid_resident(c, gimg);
+  if ((rc = grid_resident(c, gimg, ns))) return rc;
   if (!(c->built & kNeedF32)) return RTOW_OK;
   if (!gimg.ok) {
     image32_resident(c->ds32, true, nullptr, nullptr, 0);

@@ -318,7 +318,12 @@ __device__ __forceinline__ bool scatter_dir(Rng &g, uint32_t k0, uint32_t k1, in
 // BVH4 kernel always uses LDS: the image or its top, and the traversal stack)
 // SPEC: scene-class specialisation (GRID kernel only; rtow_device.h kSpec*): the class in its low two bits, | kSpecFlatY
 // for the two-axis walk of a grid with one layer in y
-template <int KERNEL, bool LDS, bool STAMPS = false, int SPEC = 0>
+// COUNT: the statistics (segments, node tests, primitive tests) are counted and added to counters[1..3].  The host
+// launches a COUNT == false instantiation for a call that returns no statistics (rtow_capi.cpp: stats == NULL): the
+// three per-lane counters, their increments in the walks and the reduction at the end do not exist there.  The queue
+// head (counters[0]) and the dropped-samples words are not statistics and are kept by both.  The diagnostic builds
+// (STAMPS, RTOW_TAILSTAT) always count.
+template <int KERNEL, bool LDS, bool STAMPS = false, int SPEC = 0, bool COUNT = true>
 __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     RTOW_CAT(rtow_trace_, RTOW_SUFFIX)(const TraceParams P) {
   const DevScene &sc = P.sc;
@@ -350,7 +355,12 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
   V3 throughput = {1, 1, 1};
 #endif
   Rng g = {0, 0, 0};
-  uint32_t nseg = 0, nnode = 0, nprim = 0;
+#ifdef RTOW_TAILSTAT
+  constexpr bool kCount = true;
+#else
+  constexpr bool kCount = COUNT || STAMPS;
+#endif
+  WalkCount<kCount> nseg, nnode, nprim;
   // GRID kernel: a walk the wave stopped early continues in the next trip (rtow_trace_grid.h)
   [[maybe_unused]] float t_resume = 0.0f;
   [[maybe_unused]] uint32_t w_cur = 0x1fffffu, w_sa = 0u;  // BVH4: the same (kRefNone = no walk in progress)
@@ -880,7 +890,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       best = closest_hit_bvh<LDS, STAMPS>(im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps);
     } else if constexpr (KERNEL == 5) {
 #ifndef RTOW_FAST_MATH
-      if (tracing) best = closest_hit_reftree(sc, to_f64(ro), to_f64(rd), (double)rtime, nnode, nprim);
+      if (tracing) best = closest_hit_reftree(sc, to_f64(ro), to_f64(rd), (double)rtime, nnode.n, nprim.n);
 #endif
     } else {
       best = closest_hit_stream(sc, to_f64(ro), to_f64(rd), (double)rtime, tracing);  // (every lane: the tiled loop stages with all 64)
@@ -994,18 +1004,20 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
   }
 #endif
   // stats: one atomic per wave and counter
-  unsigned long long t0 = nseg, t1 = nprim, t2 = nnode;
+  if constexpr (kCount) {
+    unsigned long long t0 = nseg.value(), t1 = nprim.value(), t2 = nnode.value();
 #pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    t0 += __shfl_down(t0, off);
-    t1 += __shfl_down(t1, off);
-    t2 += __shfl_down(t2, off);
-  }
-  if (lane == 0) {
-    atomicAdd(&P.counters[1], t0);
-    if (KERNEL >= 2) {
-      atomicAdd(&P.counters[2], t1);
-      atomicAdd(&P.counters[3], t2);
+    for (int off = 32; off >= 1; off >>= 1) {
+      t0 += __shfl_down(t0, off);
+      t1 += __shfl_down(t1, off);
+      t2 += __shfl_down(t2, off);
+    }
+    if (lane == 0) {
+      atomicAdd(&P.counters[1], t0);
+      if (KERNEL >= 2) {
+        atomicAdd(&P.counters[2], t1);
+        atomicAdd(&P.counters[3], t2);
+      }
     }
   }
 }
@@ -1016,9 +1028,18 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 
 #include "rtow_kernel_launch.h"
 
-template <int K, bool L, bool S, int SPEC = 0>
+template <int K, bool L, bool S, int SPEC = 0, bool COUNT = true>
 static KernelVariant<TraceParams> trace_kernel(unsigned lds_bytes) {
-  return kernel_variant<RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<K, L, S, SPEC>, TraceParams>(lds_bytes);
+  return kernel_variant<RTOW_CAT(rtow_trace_, RTOW_SUFFIX)<K, L, S, SPEC, COUNT>, TraceParams>(lds_bytes);
+}
+// a kernel that has a non-counting instantiation (the binary64 builds' GRID class kernels and BVH4 trip kernels): the
+// one the launch asked for.  The binary32 build always counts.
+template <int K, bool L, int SPEC = 0>
+static KernelVariant<TraceParams> trace_kernel_by_count(unsigned lds_bytes, bool count) {
+#ifndef RTOW_REAL_F32
+  if (!count) return trace_kernel<K, L, false, SPEC, false>(lds_bytes);
+#endif
+  return trace_kernel<K, L, false, SPEC, true>(lds_bytes);
 }
 template <bool L, bool S>
 static KernelVariant<TraceParams> trace4_kernel(unsigned lds_bytes) {
@@ -1029,20 +1050,29 @@ static KernelVariant<TraceParams> trace4_kernel(unsigned lds_bytes) {
 // > 0 selects the variant that stages the image in LDS (2, 3); `spec`: the GRID kernel's scene-class specialisation.
 // BVH4: `b4_full` (binary32 nodes <=> the image staged whole) selects the full-LDS variant, `b4_trips` the
 // trip-structured form (default; RTOW_BVH4_SM selects the state machine).
+// `count`: false asks for the instantiation without statistics where there is one (`*counted` says what was chosen).
 static KernelVariant<TraceParams> trace_variant(int kernel, unsigned lds_bytes, uint32_t spec, bool b4_full,
-                                                bool b4_trips) {
+                                                bool b4_trips, bool count = true, bool *counted = nullptr) {
   const bool lds = lds_bytes > 0;
+  bool dummy;
+  bool &cnt = counted ? *counted : dummy;
+  cnt = true;
+#ifndef RTOW_REAL_F32
+  const bool has_nocount = (kernel == 3 && lds && (spec & 3u) != 0u) || (kernel == 4 && b4_trips);
+  if (has_nocount) cnt = count;
+#endif
   switch (kernel) {
     case 1: return trace_kernel<1, false, false>(lds_bytes);  // (LDS: the tiled triangle loop's per-wave tiles)
     case 2: return lds ? trace_kernel<2, true, false>(lds_bytes) : trace_kernel<2, false, false>(0);
     case 3:
-      if (lds && spec == kSpecStaticSpheres) return trace_kernel<3, true, false, 1>(lds_bytes);
-      if (lds && spec == kSpecMovingSpheres) return trace_kernel<3, true, false, 2>(lds_bytes);
-      if (lds && spec == (kSpecStaticSpheres | kSpecFlatY)) return trace_kernel<3, true, false, 1 | (int)kSpecFlatY>(lds_bytes);
-      if (lds && spec == (kSpecMovingSpheres | kSpecFlatY)) return trace_kernel<3, true, false, 2 | (int)kSpecFlatY>(lds_bytes);
+      if (lds && spec == kSpecStaticSpheres) return trace_kernel_by_count<3, true, 1>(lds_bytes, cnt);
+      if (lds && spec == kSpecMovingSpheres) return trace_kernel_by_count<3, true, 2>(lds_bytes, cnt);
+      if (lds && spec == (kSpecStaticSpheres | kSpecFlatY)) return trace_kernel_by_count<3, true, 1 | (int)kSpecFlatY>(lds_bytes, cnt);
+      if (lds && spec == (kSpecMovingSpheres | kSpecFlatY)) return trace_kernel_by_count<3, true, 2 | (int)kSpecFlatY>(lds_bytes, cnt);
+      cnt = true;  // (a spec value outside the four above: the generic kernel)
       return lds ? trace_kernel<3, true, false>(lds_bytes) : trace_kernel<3, false, false>(0);
     case 4:
-      if (b4_trips) return b4_full ? trace_kernel<4, true, false>(lds_bytes) : trace_kernel<4, false, false>(lds_bytes);
+      if (b4_trips) return b4_full ? trace_kernel_by_count<4, true>(lds_bytes, cnt) : trace_kernel_by_count<4, false>(lds_bytes, cnt);
       return b4_full ? trace4_kernel<true, false>(lds_bytes) : trace4_kernel<false, false>(lds_bytes);
     case 4 + 16:
       if (b4_trips) return b4_full ? trace_kernel<4, true, true>(lds_bytes) : trace_kernel<4, false, true>(lds_bytes);
@@ -1057,8 +1087,9 @@ static KernelVariant<TraceParams> trace_variant(int kernel, unsigned lds_bytes, 
 }
 
 int RTOW_CAT(launch_trace_, RTOW_SUFFIX)(const TraceParams &p, int kernel, int grid, int block,
-                                         unsigned lds_bytes, void *stream) {
-  const KernelVariant<TraceParams> v = trace_variant(kernel, lds_bytes, p.spec, p.sc.b4_half == 0u, p.b4_trips != 0u);
+                                         unsigned lds_bytes, void *stream, bool count, bool *counted) {
+  const KernelVariant<TraceParams> v =
+      trace_variant(kernel, lds_bytes, p.spec, p.sc.b4_half == 0u, p.b4_trips != 0u, count, counted);
   return v.fn ? v.launch(p, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
 }
 

@@ -142,10 +142,10 @@ __device__ __forceinline__ RayForms make_unit_ray_forms(V3d o, V3d du, double ti
 // GRID: the ids are a grid image's list (the large-primitive list of rtow_grid.h), read from it whatever
 // sc.leaf_direct says — that flag describes the BVH image's leaves only (a host-built mesh BVH with a triangle in the
 // grid's large list read triangle records far past the image's end).
-template <bool LDS, bool SMALL, int SPEC = 0, bool GRID = false>
+template <bool LDS, bool SMALL, int SPEC = 0, bool GRID = false, class CN = uint32_t>
 __device__ __forceinline__ void leaf_test(const Image<LDS> &im, const DevScene &sc, ImgOffsets off,
                                           uint32_t first, uint32_t count, const RayForms &ray, Closest &best,
-                                          uint32_t &nprim, int &last_id) {
+                                          CN &nprim, int &last_id) {
 #ifndef RTOW_REAL_F32
   if constexpr (SMALL) {
     if constexpr (SPEC == 1) __builtin_assume(off.fat != 0u && off.fat_stride == 48u);
@@ -264,10 +264,10 @@ __device__ __forceinline__ void leaf_test(const Image<LDS> &im, const DevScene &
   }
 }
 
-template <bool LDS, bool ST>
+template <bool LDS, bool ST, class CN = uint32_t>
 __device__ __forceinline__ Closest closest_hit_bvh(const Image<LDS> &im, const DevScene &sc, V3 o,
-                                                   V3 d, real time, bool active, uint32_t &nnode,
-                                                   uint32_t &nprim, Stamps<ST> &stamps) {
+                                                   V3 d, real time, bool active, CN &nnode,
+                                                   CN &nprim, Stamps<ST> &stamps) {
   Closest best;
   best.t = (real)__builtin_huge_val();
   best.prim = -1;

@@ -105,10 +105,10 @@ __device__ __forceinline__ Bvh4Stack bvh4_stack(const DevScene &sc) {
 // first, `tmax32` the closest hit so far rounded up to f32.
 // FOLD: the far planes use the slack-folded coefficients of the ray (the trip kernel, whose ray lives for one walk);
 // the state machine holds its ray across its whole loop and is at the register limit, so it multiplies per node.
-template <bool FULL, bool FOLD = true>
+template <bool FULL, bool FOLD = true, class CN = uint32_t>
 __device__ __forceinline__ void bvh4_step(const Bvh4Reader<FULL> &im, const TraceParams &P, const Bvh4Ray &r, float tmax32,
                                           Bvh4Stack st, uint32_t lane_g, uint32_t &cur, uint32_t &sa, uint32_t &q0,
-                                          uint32_t &q1, uint32_t &nnode) {
+                                          uint32_t &q1, CN &nnode) {
   const float tmin32 = 0.0009f;  // < RTOW_TMIN
   const float tmaxs = FOLD ? tmax32 * kBvh4Slack : tmax32;  // (FOLD: the far side of every interval below carries the slack)
   const float fix = FOLD ? r.ixs : r.ix, fiy = FOLD ? r.iys : r.iy, fiz = FOLD ? r.izs : r.iz;
@@ -198,9 +198,9 @@ __device__ __forceinline__ void bvh4_step(const Bvh4Reader<FULL> &im, const Trac
 }
 
 // The triangles of one queued leaf, with the f64 test every kernel uses (so the accepted (t, primitive) is the same).
-template <bool FULL>
+template <bool FULL, class CN = uint32_t>
 __device__ __forceinline__ void bvh4_leaf(const Bvh4Reader<FULL> &im, const DevScene &sc, uint32_t leaf, V3d o64, V3d d64,
-                                          Closest &best, uint32_t &nprim) {
+                                          Closest &best, CN &nprim) {
   const uint32_t first = (leaf & (kRefLeaf - 1u)) >> 2, count = (leaf & 3u) + 1u;
   for (uint32_t k = 0; k < count; ++k) {
     const uint32_t r = sc.b4_off_tri + 96u * (first + k);
@@ -220,10 +220,10 @@ __device__ __forceinline__ bool bvh4_busy(uint32_t cur, uint32_t q1) {
 // lanes still walking, the queued leaves are tested and the unfinished lanes keep their place — the
 // node in hand (`w_cur`, kRefNone = no walk in progress), the stack (it lives in LDS / the spill
 // array; `w_sa` is its top) and the closest hit so far — for the caller's next trip.
-template <bool FULL, bool ST>
+template <bool FULL, bool ST, class CN = uint32_t>
 __device__ __forceinline__ Closest closest_hit_bvh4(const Bvh4Reader<FULL> &im, const DevScene &sc, const TraceParams &P,
-                                                    V3 o, V3 d, real time, bool active, uint32_t lane_g, uint32_t &nnode,
-                                                    uint32_t &nprim, Stamps<ST> &stamps, Closest best, uint32_t &w_cur,
+                                                    V3 o, V3 d, real time, bool active, uint32_t lane_g, CN &nnode,
+                                                    CN &nprim, Stamps<ST> &stamps, Closest best, uint32_t &w_cur,
                                                     uint32_t &w_sa, uint32_t cap, uint32_t max_open) {
   (void)time;  // triangles do not move
   const bool resumed = w_cur != kRefNone;

@@ -30,10 +30,20 @@
 // from the same header (rtow_walk_consts.h, TraceParams::walk): adjacent words of the kernel-argument segment in the
 // order the walk consumes them, read with wide scalar loads at the walk's entry and waited for once.  Same values bit for
 // bit, so same cells, same counters, same image; the arithmetic behind the constants is the same code for both.
-template <bool LDS, bool ST, int SPEC = 0, bool FLAT = false>
+// The block also names the first (up to four) static spheres of the large-primitive list — id and byte offset of the
+// record — which are the same for every wave of every launch on a resident image.  The class-2 walk (static + moving
+// spheres) tests those from wave-uniform values: no id reads, no dependent LDS round trip in front of the record reads,
+// and none of the four per-lane `id < n_sph` tests that decide between the record formats there.  The class-1 walk keeps
+// reading the ids: it has no such tests to lose, its ids arrive in VGPRs for nothing (one ds_read_b128), and a
+// wave-uniform id costs a v_mov per accepted root (v_cndmask takes one scalar operand, and that is VCC) — measured
+// slower than the id reads on the cover scene.
+//
+// CN: the type of the statistics counters: uint32_t, or WalkCount<> of rtow_trace_hit.h (empty in the trace kernels
+// launched for a caller that takes no statistics).
+template <bool LDS, bool ST, int SPEC = 0, bool FLAT = false, class CN = uint32_t>
 __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const DevScene &sc, V3 o,
-                                                    V3 d, real time, bool active, uint32_t &nnode,
-                                                    uint32_t &nprim, Stamps<ST> &stamps, Closest best,
+                                                    V3 d, real time, bool active, CN &nnode,
+                                                    CN &nprim, Stamps<ST> &stamps, Closest best,
                                                     float &t_resume, uint32_t cap, uint32_t max_open,
                                                     uint32_t leaf_votes, const RTOW_CONST GridWalkConsts *wk = nullptr) {
   const bool resumed = t_resume > 0.0f;
@@ -63,6 +73,11 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
   int nx, ny, nxm1, nym1, nzm1, neg_nx, nxny, neg_nxny;
   [[maybe_unused]] int nz = 0;  // (the generic walk derives the far planes below, where it always did)
   uint32_t n_large, lf, cells;
+  // the class walks: the head of the large list from the block (rtow_walk_consts.h) — ids and record offsets as
+  // wave-uniform values; nf entries of the list are served from them, the rest by the generic loops below
+  constexpr bool kLargeHead = SPEC == 2;
+  [[maybe_unused]] uint32_t nf = 0u, lrec[4] = {0u, 0u, 0u, 0u};
+  [[maybe_unused]] int lid[4] = {-1, -1, -1, -1};
   if constexpr (SPEC != 0) {
     // the host's block: wave-uniform scalar loads from the kernel-argument segment (the 3D walk's five words — cy, icy,
     // ny - 1 and the z strides — are dead in the two-axis walk and not loaded there)
@@ -73,6 +88,14 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
     n_large = wk->n_large, lf = wk->large_first, cells = wk->cells;
     off.fat = wk->fat;
     off.fat_stride = wk->fat_stride;
+    if constexpr (kLargeHead) {
+      nf = wk->n_large_fast;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lrec[j] = wk->large_rec[j], lid[j] = (int)wk->large_id[j];
+      // (pinned here: left to itself the compiler sinks these loads into the list's branch, behind a wait of their own)
+      asm volatile("" : "+s"(nf), "+s"(lrec[0]), "+s"(lrec[1]), "+s"(lrec[2]), "+s"(lrec[3]), "+s"(lid[0]), "+s"(lid[1]),
+                   "+s"(lid[2]), "+s"(lid[3]));
+    }
   } else {
     // header: wave-uniform scalar loads from the global copy of the image
     const RTOW_CONST float *hf = (const RTOW_CONST float *)sc.gblob;
@@ -95,6 +118,37 @@ __device__ __forceinline__ Closest closest_hit_grid(const Image<LDS> &im, const 
   // latency and the f64 dependency chains of one test overlap the others.
   if (active && !resumed && n_large != 0u) {
     uint32_t k = 0;
+    if constexpr (kLargeHead) {
+      // Same tests, same operands and same order as the loops below run for these entries (sphere_disc of every
+      // entry, then sphere_resolve in list order): the accepted (t, primitive), nprim and last_id are theirs.
+      double dd[4], hh[4];
+      if (nf == 4u) {  // (the cover scenes: the ground and the three big spheres)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const double2 p0 = im.d2(lrec[j]), p1 = im.d2(lrec[j] + 16u);
+          dd[j] = sphere_disc<double>(ray.o64, ray.d64, ray.a64, p0.x, p0.y, p1.x, p1.y, hh[j]);
+        }
+        nprim += 4u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sphere_resolve<double>(dd[j], hh[j], ray.a64, ray.inv_a64, lid[j], ray.tmin, best);
+        last_id = lid[3];
+      } else if (nf != 0u) {  // one to three entries (wave-uniform branches)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if ((uint32_t)j < nf) {
+            const double2 p0 = im.d2(lrec[j]), p1 = im.d2(lrec[j] + 16u);
+            dd[j] = sphere_disc<double>(ray.o64, ray.d64, ray.a64, p0.x, p0.y, p1.x, p1.y, hh[j]);
+          }
+        nprim += nf;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if ((uint32_t)j < nf) {
+            sphere_resolve<double>(dd[j], hh[j], ray.a64, ray.inv_a64, lid[j], ray.tmin, best);
+            last_id = lid[j];
+          }
+      }
+      k = nf;
+    }
     for (; k + 3 < n_large; k += 4) {
       int id[4];
 #pragma unroll

@@ -7,6 +7,23 @@ struct Closest {
   int prim;  // class-major primitive id, -1 = miss
 };
 
+// The walks' statistics (segments, node tests, primitive tests) are per-lane counters.  The walks take their counter
+// type as a template parameter: uint32_t counts, WalkCount<false> is empty — no register, no instruction — for the
+// trace kernels launched by a call that returns no statistics (rtow_trace_body.h, COUNT).
+template <bool COUNT>
+struct WalkCount {
+  uint32_t n = 0;
+  __device__ __forceinline__ WalkCount &operator++() { return ++n, *this; }
+  __device__ __forceinline__ WalkCount &operator+=(uint32_t k) { return n += k, *this; }
+  __device__ __forceinline__ uint32_t value() const { return n; }
+};
+template <>
+struct WalkCount<false> {
+  __device__ __forceinline__ WalkCount &operator++() { return *this; }
+  __device__ __forceinline__ WalkCount &operator+=(uint32_t) { return *this; }
+  __device__ __forceinline__ uint32_t value() const { return 0u; }
+};
+
 // sphere_hit_helper up to the accepted root (src/common-model.cpp:70-81);
 // the hit point and normal are computed once, for the winner only.
 // `inv_a` is 1/a, used only by the fast build (one reciprocal per ray instead of two

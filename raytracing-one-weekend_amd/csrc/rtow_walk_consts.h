@@ -7,7 +7,8 @@
 // image at every entry of the walk — six scalar loads of mixed width, single-word reloads where the SGPRs ran out — and to
 // re-derive per-scene terms on the vector unit in every trip (the far planes: a conversion, a move and a fused
 // multiply-add per axis).  The block is laid out in the order the walk consumes it: the two-axis walk of a grid with one
-// layer in y takes its first 19 words (a 16-word scalar load and a short one, one wait), the 3D walk six more.
+// layer in y takes its first 19 words (a 16-word scalar load and a short one, one wait), the 3D walk six more.  Words
+// 32-40 hold the head of the image's large-primitive list (fill_large_head below): loaded with them, behind the same wait.
 //
 // Every term is the kernel's own expression on the same binary32 / 32-bit integer operands, so a walk that reads the
 // block visits the cells the header-reading walk visits: hx is fmaf((float)nx, cx, gx) in binary32, ONE rounding, as
@@ -38,8 +39,25 @@ struct alignas(64) GridWalkConsts {
   int nym1;                   // ny - 1
   int nxny, neg_nxny;         // the index stride along z, both signs
   int pad_[7];
+  // words 32-40: the head of the always-test (large-primitive) list, for the class instantiations (read by the class
+  // with moving spheres; rtow_trace_grid.h says why the class of static spheres keeps its id reads).  The ids of that list
+  // and the records they name are the same for every wave of every launch on a resident image: entry j < n_large_fast
+  // is the static sphere large_id[j], whose 32-byte record sits at byte large_rec[j] of the image.  The walk tests
+  // these entries from wave-uniform values — no read of the id section, no per-lane address arithmetic — and the rest
+  // of the list (entries from n_large_fast on) the way the generic walk does.  n_large_fast is the number of LEADING
+  // entries, four at most, that are static spheres; 0 for a block made without the id section (fill_large_head not
+  // called): the whole list then goes the generic way.
+  unsigned large_rec[4];
+  unsigned large_id[4];
+  unsigned n_large_fast;
+  int pad2_[7];
 };
-static_assert(sizeof(GridWalkConsts) == 128, "two 64-byte lines");
+static_assert(sizeof(GridWalkConsts) == 192, "three 64-byte lines");
+// (the head of the list: one aligned run of eight words, read with one wide scalar load, and the count behind it)
+static_assert(__builtin_offsetof(GridWalkConsts, large_rec) == 128 && __builtin_offsetof(GridWalkConsts, large_id) == 144 &&
+                  __builtin_offsetof(GridWalkConsts, n_large_fast) == 160,
+              "GridWalkConsts: the large list's head");
+constexpr unsigned kWalkLargeFast = 4;  // entries of the large list the block can hold
 
 // `header`: the 64 bytes at the start of the grid image (rtow_grid.h: f32 gmin[3], cell[3], inv_cell[3], i32 n[3], u32
 // n_large, off_large, off_fat, fat_stride); off_ids / off_cells: the image's section offsets (DevScene::g_off_*).
@@ -66,4 +84,17 @@ RTOW_WALK_FN GridWalkConsts make_grid_walk_consts(const unsigned char *header, u
   w.large_first = (hu[1] - off_ids) >> 2;
   w.fat = hu[2], w.fat_stride = hu[3];
   return w;
+}
+
+// The head of the large list into `w`.  `large_ids`: the first min(n_large, kWalkLargeFast) words of the list as the
+// image holds them (at header word 13, off_large); n_sph: static spheres of the scene (ids below it); off_sph: byte
+// offset of the image's static-sphere records (32 bytes each).
+RTOW_WALK_FN void fill_large_head(GridWalkConsts &w, const unsigned *large_ids, int n_sph, unsigned off_sph) {
+  const unsigned n = w.n_large < kWalkLargeFast ? w.n_large : kWalkLargeFast;
+  unsigned k = 0;
+  for (; k < n && large_ids[k] < (unsigned)n_sph; ++k) {
+    w.large_id[k] = large_ids[k];
+    w.large_rec[k] = off_sph + 32u * large_ids[k];
+  }
+  w.n_large_fast = k;
 }

@@ -201,6 +201,7 @@ EXPORTS = [
     "rtow_debug_tile_order", "rtow_radiance_device", "rtow_radiance",
     "rtow_camera_rays_device", "rtow_camera_rays", "rtow_camera_ray_count", "rtow_guides_device", "rtow_guides",
     "rtow_debug_last_spec", "rtow_first_hits_device", "rtow_first_hits", "rtow_nearest_device", "rtow_nearest",
+    "rtow_debug_last_counted", "rtow_debug_walk_consts",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -326,6 +327,10 @@ def lib():
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     if hasattr(L, "rtow_debug_last_spec"):
         L.rtow_debug_last_spec.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    if hasattr(L, "rtow_debug_last_counted"):
+        L.rtow_debug_last_counted.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    if hasattr(L, "rtow_debug_walk_consts"):
+        L.rtow_debug_walk_consts.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     ver = L.rtow_abi_version()
     if ver != RTOW_ABI_VERSION and not ("RTOW_LIB" in os.environ and ver >= 4):  # (older builds: A/B runs only)
         raise RtowError("librtow.so ABI version mismatch")
@@ -480,6 +485,22 @@ class Context:
         v = C.c_uint32()
         check(lib().rtow_debug_last_spec(self._h, C.byref(v)), "rtow_debug_last_spec")
         return int(v.value)
+
+    def last_counted(self) -> bool:
+        """Whether the last trace launch ran a kernel that counts statistics (rtow_debug_last_counted): False for the
+        instantiation a render without statistics launches where the kernel has one."""
+        v = C.c_uint32()
+        check(lib().rtow_debug_last_counted(self._h, C.byref(v)), "rtow_debug_last_counted")
+        return bool(v.value)
+
+    def walk_consts(self):
+        """The GRID walk's constants block of the resident grid image (rtow_debug_walk_consts) as 32-bit words
+        (csrc/rtow_walk_consts.h: words 16 n_large, 32-35 large_rec, 36-39 large_id, 40 n_large_fast)."""
+        n = C.c_int32()
+        check(lib().rtow_debug_walk_consts(self._h, None, 0, C.byref(n)), "rtow_debug_walk_consts")
+        buf = (C.c_uint32 * (n.value // 4))()
+        check(lib().rtow_debug_walk_consts(self._h, buf, n.value, C.byref(n)), "rtow_debug_walk_consts")
+        return np.frombuffer(bytes(buf), dtype=np.uint32)
 
     def build_info(self) -> BuildInfo:
         bi = BuildInfo()

@@ -19,3 +19,10 @@ for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s+\d+', txt, re.S):
     print(f"{short:44s} vgpr {g('vgpr_count'):>3} sgpr {g('sgpr_count'):>3} scratch {g('private_segment_fixed_size'):>4} "
           f"spill v{g('vgpr_spill_count')} s{g('sgpr_spill_count')}")
 PY
+# the GRID class kernels without statistics (the headline kernel and the moving cover's): vector instructions between
+# the s_setprio markers of the stages (scripts/isa_prio_regions.py: 2 = new-ray stage's end + the always-test list, up to
+# kPrioSetup; 3 = the walk's set-up; 4 = the DDA loop; 5 = the leaf phase; 6 = shading)
+for k in 5ELb0E 6ELb0E; do
+  echo "rtow_trace_${B}ILi3ELb1ELb0ELi$k:"
+  python3 "$ROOT/scripts/isa_prio_regions.py" /tmp/rtow_$B.s rtow_trace_${B}ILi3ELb1ELb0ELi$k || true
+done
