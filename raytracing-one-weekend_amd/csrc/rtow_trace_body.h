@@ -335,10 +335,18 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
   [[maybe_unused]] Bvh4Reader<LDS> im4;  // LDS: the whole image is staged; otherwise the top of the tree
   stage_scene<KERNEL, LDS>(sc, im, im4);
 
+  // The lanes' flags, as lane masks of the wave (rtow_trace_math.h `lanemask`): they are only ever combined, voted on
+  // and branched on, so they live in SGPR pairs and a vote on them is scalar arithmetic.  Every one is formed and
+  // updated at the top level of the trip, where the whole wave stands at the same point, from votes on the comparisons
+  // that define it; per-lane code is entered through lanes_of.  m_all: every lane of the wave.
+  //   m_done  the lane has no item and found the queue empty (or gave up at the tail bound)
+  //   m_ns    "need_sample": the lane starts a new sample (or needs an item) at the top of the next trip
+  //   m_ph    "pending_hit": the last segment ended in a hit that is scattered at the top of the next trip
+  //   m_help, m_hold  end-of-launch donation (below): the lane traces a donated sample / has finished it and keeps its
+  //           colour in `acc` until the owner adds it.  Lanes of m_hold are lanes of m_done; m_help and m_done are disjoint.
+  const lanemask m_all = vote(true);
+  lanemask m_done = 0ull, m_ns = m_all, m_ph = 0ull, m_help = 0ull, m_hold = 0ull;
   // per-lane state
-  bool done = false;
-  bool need_sample = true;
-  bool pending_hit = false;   // the last segment ended in a hit that is scattered at the top of the next trip
   int s_left = 0;             // samples left in the current item
   uint32_t item = 0xffffffffu;
   uint32_t j = 0;             // column
@@ -367,9 +375,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
   Closest best;
   best.t = 0;
   best.prim = -1;
-  // end-of-launch sample donation (see "tail" below)
-  bool helping = false;    // this lane traces a sample donated by another lane of the wave
-  bool holding = false;    // ... has finished it and keeps its colour in `acc` until the owner adds it
+  // end-of-launch sample donation (see "tail" below; the flags `helping` and `holding` are m_help and m_hold above)
   uint32_t partners = 0u;  // owner: stack of its helpers' lane ids (6 bits each, most recent lowest);
                            // helper: its owner's lane id
   int n_out = 0;           // owner: donated samples not yet added
@@ -394,24 +400,20 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 
   for (;;) {
     // ---- item bookkeeping ---------------------------------------------------
-    bool need_item = false;
-    if (!done && need_sample && s_left <= 0) {
-      if (helping) {  // a donated sample is finished: keep its colour for the owner
-        helping = false;
-        holding = true;
-        done = true;
-      } else if (n_out == 0) {
-        need_item = true;
-      }  // else: an owner waiting for donated samples
-    }
-    unsigned long long need_mask = __ballot(need_item);
+    // the lanes whose item — or donated sample — has no sample left (a lane without an item yet is one of them)
+    const lanemask m_end = m_ns & ~m_done & vote(s_left <= 0);
+    // ... of those, the helpers: a donated sample is finished, the lane keeps its colour for the owner
+    const lanemask m_handed = m_end & m_help;
+    m_help &= ~m_handed;
+    m_hold |= m_handed;
+    m_done |= m_handed;
+    // ... and the lanes that need a new item: the others, unless they are owners waiting for donated samples.  Lanes
+    // that are not done.
+    lanemask need_mask = m_end & ~m_handed & vote(n_out == 0);
     // Lanes that need a new item wait until `fetch_votes` of them do (or nothing else is left to do): with
     // 64 desynchronised lanes some lane finishes an item in almost every trip, and the fetch block — queue
     // atomic, item decode, partial-sum store — would run every trip for two or three lanes.
-    if (need_mask != 0ull && (uint32_t)__popcll(need_mask) < P.fetch_votes && __ballot(!done && !need_item) != 0ull) {
-      need_mask = 0ull;
-      need_item = false;
-    }
+    if (need_mask != 0ull && count_of(need_mask) < P.fetch_votes && (m_all & ~m_done & ~need_mask) != 0ull) need_mask = 0ull;
     if (need_mask != 0ull) {
       // The item-decoding parameters are read here from the kernel-argument segment (scalar loads)
       // instead of living in SGPRs for the whole launch: the kernel is VALU-issue-bound and ran out
@@ -419,7 +421,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       const RTOW_CONST TraceParams *kp = (const RTOW_CONST TraceParams *)__builtin_amdgcn_kernarg_segment_ptr();
       asm volatile("" : "+s"(kp));  // opaque per trip: keeps the loads from being hoisted out of the loop
       const FetchHead fh = load_fetch_head(kp);
-      if (need_item && item != 0xffffffffu) {  // the finished item goes to its partial-sum slot
+      if (lanes_of(need_mask) && item != 0xffffffffu) {  // the finished item goes to its partial-sum slot
         double *dst = fh.partials + (size_t)item * 3;
         dst[0] = acc.x;
         dst[1] = acc.y;
@@ -427,25 +429,26 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
         item = 0xffffffffu;
       }
       const unsigned long long mine = take_items(pool, need_mask, lane, n_waves, fh);
-      if (need_item) {
-        if (mine >= (unsigned long long)fh.n_items) {
-          done = true;
+      // the lanes of need_mask that found the queue empty (`mine` of a lane outside need_mask is no queue position)
+      const lanemask m_empty = need_mask & vote(mine >= (unsigned long long)fh.n_items);
+      m_done |= m_empty;
+      if (lanes_of(m_empty)) {
 #ifdef RTOW_TAILSTAT
-          if (ts_empty == 0ull) ts_empty = 1ull;  // marked; the wave-level snapshot is taken below
+        if (ts_empty == 0ull) ts_empty = 1ull;  // marked; the wave-level snapshot is taken below
 #endif
-          if constexpr (STAMPS) {
-            if (t_empty == 0ull) t_empty = __builtin_amdgcn_s_memrealtime();
-          }
-        } else {
-          const ItemPos ip = decode_item(kp, fh, (uint32_t)mine);
-          item = ip.item;
-          j = ip.j;
-          gi = ip.gi;
-          g.pixel = gi * (uint32_t)fh.W + j;
-          g.sample = ip.sample0;
-          s_left = ip.count;
-          acc = {0.0, 0.0, 0.0};
+        if constexpr (STAMPS) {
+          if (t_empty == 0ull) t_empty = __builtin_amdgcn_s_memrealtime();
         }
+      }
+      if (lanes_of(need_mask & ~m_empty)) {
+        const ItemPos ip = decode_item(kp, fh, (uint32_t)mine);
+        item = ip.item;
+        j = ip.j;
+        gi = ip.gi;
+        g.pixel = gi * (uint32_t)fh.W + j;
+        g.sample = ip.sample0;
+        s_left = ip.count;
+        acc = {0.0, 0.0, 0.0};
       }
     }
 #ifdef RTOW_TAILSTAT
@@ -453,8 +456,8 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       const bool first = __ballot(ts_empty == 1ull) != 0ull && __ballot(ts_empty > 1ull) == 0ull;
       if (first) {  // wave-uniform: the first trip in which some lane found the queue empty
         const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-        ts_live = (uint32_t)__popcll(__ballot(!done));
-        uint32_t sl = (!done && s_left > 0) ? (uint32_t)s_left : 0u;
+        ts_live = count_of(m_all & ~m_done);
+        uint32_t sl = (lanes_of(m_all & ~m_done) && s_left > 0) ? (uint32_t)s_left : 0u;
         for (int off = 32; off >= 1; off >>= 1) sl += __shfl_xor(sl, off);
         ts_left = sl;
         ts_pool = pool.end - pool.next;
@@ -475,7 +478,10 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     // the sequential one bit for bit.  Only lanes of the same wave trade (registers + ds_bpermute).
     // Measured: +0.9 % on C2.  What remains of the tail is one PATH: a trip takes ~13.7 us with four
     // waves per SIMD, so a 50-bounce path started just before the queue empties runs ~0.2-0.7 ms.
-    if (__ballot(done) != 0ull) {
+    if (m_done != 0ull) {
+      // (the block runs in the last trips of a launch only and keeps its per-lane logic: the flags it reads and writes
+      // are per-lane values from here to its end, where the masks are taken again)
+      bool done = lanes_of(m_done), need_sample = lanes_of(m_ns), helping = lanes_of(m_help), holding = lanes_of(m_hold);
 #ifdef RTOW_DONATE_R2  // (the round-2 form: at most 5 samples out per giver, lane ids on a 6-bit stack)
       // (1) owners that have finished their own samples take the next donated colour, if ready
       const bool ready = !done && need_sample && s_left <= 0 && n_out > 0;
@@ -585,12 +591,14 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       } else {
         --tail_left;
       }
+      m_done = vote(done), m_ns = vote(need_sample), m_help = vote(helping), m_hold = vote(holding);
     }
-    if (__ballot(!done || holding) == 0ull) break;
+    if (((m_all & ~m_done) | m_hold) == 0ull) break;
     stamps.mark(RG_FETCH);
 
+    // the lanes with a sample in progress or to start
     // (a lane whose fresh item has no samples — spt == 0 — goes straight back for the next one)
-    const bool live = !done && !(need_sample && s_left <= 0);
+    const lanemask m_live = m_all & ~m_done & ~(m_ns & vote(s_left <= 0));
 
     // ---- new rays ------------------------------------------------------------------------------------
     // Two kinds of lanes need a new ray before the walk: those starting a sample (pixel jitter +
@@ -600,8 +608,8 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
     // evaluation of what their two samplers share (sine, cosine, square root).  Every lane consumes exactly its own
     // requests in its own order (counter = (request, sample, pixel)), so the image does not depend on who shares a wave
     // with whom.  (Rounds 1-5a ran the reference's rejection loops here: ~6, later 3.4 block evaluations per trip.)
-    const bool do_regen = live && need_sample;
-    const bool do_scat = live && pending_hit;
+    const lanemask m_regen = m_live & m_ns, m_scat = m_live & m_ph;
+    const bool do_regen = lanes_of(m_regen), do_scat = lanes_of(m_scat);
     // (read only by the lanes of `do_scat`, here and in the two scatter blocks below: for every other lane the value
     // is unspecified — `anyv` — which spares the dozen v_mov a zero initialiser costs in every trip)
     V3 normal = anyv3();
@@ -736,7 +744,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       g.r += 1u;
     }
     if constexpr (STAMPS) {  // wave-level count of block evaluations: the first active lane reports
-      if (__ballot(do_regen || do_scat) != 0ull) stamps.blocks += 1;
+      if ((m_regen | m_scat) != 0ull) stamps.blocks += 1;
     }
     V3 dirbase = anyv3();  // bounce: direction before the fuzz term
     // Both samplers need the sine and cosine of an angle of the first quadrant and one square root (rtow_trace_rng.h):
@@ -827,11 +835,13 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 #ifdef RTOW_FAST_MATH
       throughput = {1, 1, 1};
 #endif
-      need_sample = false;
     }
+    m_ns &= ~m_regen;
+    m_ph &= ~m_scat;
+    // absorbed (src/render.cpp:120): the three differences of the Lambertian lanes' test below go out of the per-lane
+    // code and are compared at the trip's level, so that the result is a mask
+    V3 ab_d = anyv3();
     if (do_scat) {
-      pending_hit = false;
-      bool absorbed = false;
       // (the new direction is written over the old one in both branches; an absorbed path — black, src/render.cpp:120 —
       // starts a new sample in the next trip and never reads it)
       // random_unit_vector() (src/common-model.cpp:16,26,58): ball_from_block's last step — radius times direction
@@ -839,30 +849,34 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       const real s_rs = s_r * s_sq;
       const V3 rnd = V3{s_rs * s_cs, s_rs * s_sn, s_r * s_z};
       if (kind == 0) {
-        absorbed = rabs(normal.x - rnd.x) < real(1e-8) && rabs(normal.y - rnd.y) < real(1e-8) &&
-                   rabs(normal.z - rnd.z) < real(1e-8);
+        ab_d = normal - rnd;
         rd = normal + rnd;
       } else {
         rd = dirbase + m_fuzz * rnd;
       }
-      if (absorbed) {
-        need_sample = true;  // src/render.cpp:120: black (the lane starts its next sample in the next trip)
-        --s_left;
-        ++g.sample;
-      } else {
+    }
+    // (`kind` is 0 in the lanes that did not scatter: their votes are dropped by m_scat)
+    const lanemask m_absorbed = m_scat & vote(kind == 0) & vote(rabs(ab_d.x) < real(1e-8)) & vote(rabs(ab_d.y) < real(1e-8)) &
+                                vote(rabs(ab_d.z) < real(1e-8));
+    if (lanes_of(m_absorbed)) {  // src/render.cpp:120: black (the lane starts its next sample in the next trip)
+      --s_left;
+      ++g.sample;
+    }
+    m_ns |= m_absorbed;
+    if (lanes_of(m_scat & ~m_absorbed)) {
 #ifdef RTOW_FAST_MATH
-        throughput = throughput * m_att;
+      throughput = throughput * m_att;
 #else
-        P.stack[(size_t)nb * P.n_lanes + lane_g] = (uint32_t)mi;
+      P.stack[(size_t)nb * P.n_lanes + lane_g] = (uint32_t)mi;
 #endif
-        ++nb;
-        --depth;
-      }
+      ++nb;
+      --depth;
     }
     stage_prio<kPrioStage>();
-    const bool tracing = live && !need_sample;  // has a ray to advance in this trip
+    const lanemask m_tracing = m_live & ~m_ns;  // the lanes with a ray to advance in this trip
+    [[maybe_unused]] const bool tracing = lanes_of(m_tracing);
 
-    stamps.mark(RG_REGEN, __ballot(do_regen || do_scat));
+    stamps.mark(RG_REGEN, m_regen | m_scat);
     if constexpr (STAMPS) {
       stamps.trips += 1;
       if (t_empty != 0ull) trips_after_empty += 1;
@@ -873,18 +887,20 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       best.t = 0;
       best.prim = -1;
     }
+    [[maybe_unused]] lanemask m_open = 0ull;  // GRID: the lanes whose walk was stopped and continues in the next trip
     if constexpr (KERNEL == 4) {
       best = closest_hit_bvh4<LDS, STAMPS>(im4, sc, P, ro, rd, rtime, tracing, lane_g, nnode, nprim, stamps, best, w_cur, w_sa,
                                            P.walk_cap, P.walk_max_open);
     } else if constexpr (KERNEL == 3) {
-      if constexpr (STAMPS) stamps.primary = __ballot(tracing && depth == P.max_child_rays);
+      if constexpr (STAMPS) stamps.primary = m_tracing & vote(depth == P.max_child_rays);
       // (the specialised walks read their per-scene constants from TraceParams::walk, at the walk's entry: the pointer is
       // opaque per trip, so the block is neither held in SGPRs across the new-ray stage nor loaded word by word)
       const RTOW_CONST TraceParams *kw = (const RTOW_CONST TraceParams *)__builtin_amdgcn_kernarg_segment_ptr();
       if constexpr ((SPEC & 3) != 0) asm volatile("" : "+s"(kw));
       best = closest_hit_grid<LDS, STAMPS, (SPEC & 3), (SPEC & (int)kSpecFlatY) != 0>(
-          im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps, best, t_resume, P.walk_cap, P.walk_max_open, P.leaf_votes,
-          &kw->walk);
+          im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps, best, t_resume, P.walk_cap, P.walk_max_open,
+          P.leaf_votes, &kw->walk);
+      m_open = vote(t_resume > 0.0f);  // (t_resume of a lane without a ray is 0)
     } else if constexpr (KERNEL == 2) {
       // the walk uses wave votes, so every lane of the wave enters it
       best = closest_hit_bvh<LDS, STAMPS>(im, sc, ro, rd, rtime, tracing, nnode, nprim, stamps);
@@ -896,58 +912,60 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       best = closest_hit_stream(sc, to_f64(ro), to_f64(rd), (double)rtime, tracing);  // (every lane: the tiled loop stages with all 64)
     }
 
-    stamps.mark(RG_WALK, __ballot(tracing));
-    bool arrived = tracing;  // the segment's closest hit is known (a stopped GRID / BVH4 walk continues next trip)
-    if constexpr (KERNEL == 3) arrived = tracing && !(t_resume > 0.0f);
-    if constexpr (KERNEL == 4) arrived = tracing && w_cur == 0x1fffffu;
-    if (arrived) {
-      ++nseg;
-      if (best.prim >= 0) {
-        if (depth <= 0)
-          need_sample = true;  // src/render.cpp:115: black
-        else
-          pending_hit = true;  // scattered at the top of the next trip, together with the new camera rays
-      } else {
-        // ---- background + unwind of the recursion (src/render.cpp:119,122-128) --
-        const V3 unit = normalize(rd);
-        const real t = real(0.5) * (unit.y + real(+1.0));
-        V3 c = (real(1.0) - t) * V3{1, 1, 1} + t * V3{real(0.5), real(0.7), real(1.0)};
+    stamps.mark(RG_WALK, m_tracing);
+    // the lanes whose segment's closest hit is known (a stopped GRID / BVH4 walk continues next trip)
+    lanemask m_arrived = m_tracing;
+    if constexpr (KERNEL == 3) m_arrived = m_tracing & ~m_open;
+    if constexpr (KERNEL == 4) m_arrived = m_tracing & vote(w_cur == 0x1fffffu);
+    // ... a hit with no child ray left (src/render.cpp:115: black), a hit that is scattered at the top of the next trip,
+    // together with the new camera rays, and the background
+    const lanemask m_hit = m_arrived & vote(best.prim >= 0);
+    const lanemask m_black = m_hit & vote(depth <= 0);
+    const lanemask m_sky = m_arrived & ~m_hit;
+    m_ph |= m_hit & ~m_black;
+    if (lanes_of(m_arrived)) ++nseg;
+    if (lanes_of(m_sky)) {
+      // ---- background + unwind of the recursion (src/render.cpp:119,122-128) --
+      const V3 unit = normalize(rd);
+      const real t = real(0.5) * (unit.y + real(+1.0));
+      V3 c = (real(1.0) - t) * V3{1, 1, 1} + t * V3{real(0.5), real(0.7), real(1.0)};
 #ifdef RTOW_FAST_MATH
-        c = throughput * c;
+      c = throughput * c;
 #else
-        for (int q = nb - 1; q >= 0; --q) {
-          const uint32_t smi = P.stack[(size_t)q * P.n_lanes + lane_g];
-          if constexpr (KERNEL == 4) {
-            const uint32_t mr = sc.b4_off_mats + 48u * smi;
-            const vd2 a0 = im4.d2(mr), a1 = im4.d2(mr + 16u);
-            c = V3{(real)a0.x, (real)a0.y, (real)a1.x} * c;
-          } else if constexpr (KERNEL >= 2 && KERNEL <= 4) {
-            const uint32_t mr = (KERNEL == 3 ? sc.g_off_mats : sc.off_mats) + 48u * smi;
-            const double2 a0 = im.d2(mr), a1 = im.d2(mr + 16u);
-            c = V3{(real)a0.x, (real)a0.y, (real)a1.x} * c;
-          } else {
-            const DevMaterial *m = sc.mats + smi;
-            c = V3{(real)m->att[0], (real)m->att[1], (real)m->att[2]} * c;
-          }
+      for (int q = nb - 1; q >= 0; --q) {
+        const uint32_t smi = P.stack[(size_t)q * P.n_lanes + lane_g];
+        if constexpr (KERNEL == 4) {
+          const uint32_t mr = sc.b4_off_mats + 48u * smi;
+          const vd2 a0 = im4.d2(mr), a1 = im4.d2(mr + 16u);
+          c = V3{(real)a0.x, (real)a0.y, (real)a1.x} * c;
+        } else if constexpr (KERNEL >= 2 && KERNEL <= 4) {
+          const uint32_t mr = (KERNEL == 3 ? sc.g_off_mats : sc.off_mats) + 48u * smi;
+          const double2 a0 = im.d2(mr), a1 = im.d2(mr + 16u);
+          c = V3{(real)a0.x, (real)a0.y, (real)a1.x} * c;
+        } else {
+          const DevMaterial *m = sc.mats + smi;
+          c = V3{(real)m->att[0], (real)m->att[1], (real)m->att[2]} * c;
         }
-#endif
-        {
-          // never fused with the multiply that produced `c`: a donated sample (end-of-launch tail)
-          // reaches its owner as a rounded colour, so a fused multiply-add here would make the
-          // pixel sum depend on which lane traced the sample (the empty asm hides `c` from the
-          // contraction pass)
-          V3d cd = to_f64(c);
-          asm volatile("" : "+v"(cd.x), "+v"(cd.y), "+v"(cd.z));
-          acc = acc + cd;  // pixel_color += ray_color(...)
-        }
-        need_sample = true;
       }
-      if (need_sample) {
-        --s_left;
-        ++g.sample;
+#endif
+      {
+        // never fused with the multiply that produced `c`: a donated sample (end-of-launch tail)
+        // reaches its owner as a rounded colour, so a fused multiply-add here would make the
+        // pixel sum depend on which lane traced the sample (the empty asm hides `c` from the
+        // contraction pass)
+        V3d cd = to_f64(c);
+        asm volatile("" : "+v"(cd.x), "+v"(cd.y), "+v"(cd.z));
+        acc = acc + cd;  // pixel_color += ray_color(...)
       }
     }
-    stamps.mark(RG_SHADE, __ballot(arrived));
+    // the sample is over: the lane starts its next one at the top of the next trip
+    const lanemask m_over = m_black | m_sky;
+    m_ns |= m_over;
+    if (lanes_of(m_over)) {
+      --s_left;
+      ++g.sample;
+    }
+    stamps.mark(RG_SHADE, m_arrived);
   }
   if constexpr (STAMPS) {
     if (lane == 0)

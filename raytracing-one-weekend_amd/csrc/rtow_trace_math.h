@@ -35,6 +35,18 @@ __device__ __forceinline__ T anyv(T) {
   return x;
 }
 __device__ __forceinline__ V3 anyv3() { return V3{anyv(real(0)), anyv(real(0)), anyv(real(0))}; }
+// Wave votes as scalar lane masks.  A vote on a per-lane `bool` that is carried through a loop or a branch compiles to
+// a rebuild of the flag in a VGPR (v_cndmask 0, 1, mask) and a compare of that (v_cmp_ne 0): two vector instructions and
+// the wait states of a VALU write read by the scalar unit, only to intersect a lane mask the compiler already holds in an
+// SGPR pair with `exec`.  A predicate that is only ever combined and voted on is therefore kept as a `lanemask`: formed
+// by `vote` DIRECTLY from the comparison that defines it (one v_cmp into an SGPR pair), combined with scalar and / andn2
+// / or, counted with s_bcnt1, and entered as per-lane control flow through `lanes_of` (a copy into `exec`, no VALU).
+// Rules: a mask is formed where the whole wave is at the same point (a vote inside a divergent branch sees only that
+// branch's lanes; `lanes_of` is defined for a wave-uniform mask only), and every site says which lanes can be set.
+typedef unsigned long long lanemask;
+__device__ __forceinline__ lanemask vote(bool comparison) { return __builtin_amdgcn_ballot_w64(comparison); }
+__device__ __forceinline__ bool lanes_of(lanemask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+__device__ __forceinline__ uint32_t count_of(lanemask m) { return (uint32_t)__popcll(m); }
 // Issue priority of the wave by STAGE (s_setprio, 0..3; one scalar instruction).  The kernel is bound by VALU issue and a
 // SIMD's waves are each in a different stage of their trip.  Left alone, the arbiter treats them alike; told which stage
 // is latency-bound (LDS chains: highest), which is mixed (the default) and which is pure arithmetic (the random-number
