@@ -652,6 +652,72 @@ int rtow_radiance_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const
 int rtow_radiance(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params,
                   const rtow_ray_t *rays, int64_t n_rays, const uint32_t *ids, double *rgb_sums, rtow_stats_t *stats);
 
+/* ---- path-step queries: one segment per caller ray ---------------------------------------------------------------------
+ * "Where does this ray go next, and what does the surface take from it?" — ONE segment of the reference's ray_color: the
+ * closest hit, then Material::scatter (src/common-model.cpp:13-62).  It is the stage rtow_radiance keeps to itself, for
+ * callers who drive the bounces: their own lights with rtow_occluded shadow rays, Russian roulette, per-bounce AOVs,
+ * path-length statistics, another sky, compaction between bounces.  rtow_camera_rays, then rtow_path_step repeated
+ * max_child_rays + 1 times with bounce = 0, 1, ... and folded by the caller, IS rtow_radiance (bit for bit in the strict
+ * build): colour = a_0 * (a_1 * (... * a_k)) over the attenuations up to the step that ended the path — the sky's colour
+ * on a MISS, 0 on ABSORBED, and 0 by the caller's own rule for a hit at bounce == max_child_rays (src/render.cpp:115: the
+ * call knows nothing of a depth).
+ *
+ *   identity   ray i draws as (pixel, sample) = (ids[i][0], ids[i][1] + sample_first), the sum mod 2^32; without ids
+ *              (NULL) as (i, sample_first).  The scatter draws request 1 + bounce of that identity, as rtow_radiance does
+ *              for the path's segment `bounce`.  bounce is one number per call.
+ *   per ray    status[i] is one of
+ *     RTOW_STEP_SKIPPED    tmax is NaN or below 0.001: no walk.  atten = 0, hit = the miss record, next = the DEAD RAY:
+ *                          every field 0 and tmax = -1.  A dead ray fed back stays dead, so a caller can loop in place
+ *                          (d_next == d_rays) without compaction.
+ *     RTOW_STEP_MISS       no hit in [0.001, tmax] (tmax is a post-filter, exactly as in rtow_intersect_device: the walks
+ *                          are not seeded with it).  atten = the reference's background for the ray
+ *                          (src/render.cpp:122-128): (1-t)*1 + t*(0.5, 0.7, 1.0), t = 0.5*(unit(direction).y + 1);
+ *                          hit = the miss record; next = the dead ray.
+ *     RTOW_STEP_SCATTERED  hit = the record rtow_intersect_device writes for this ray; atten = the hit material's
+ *                          attenuation as uploaded; next.origin = hit.point, next.direction = what scatter returns
+ *                          (Lambertian normal + rnd, metal reflect(d, n) + fuzz*rnd, dielectric as the reference, none of
+ *                          them normalised), next.time = the ray's time, next.tmax = +inf.
+ *     RTOW_STEP_ABSORBED   a hit whose scatter returns nothing (the Lambertian near-zero direction): hit is filled,
+ *                          atten = 0, next = the dead ray.
+ *   buffers    d_rays, d_next: rtow_ray_t[n], 16-byte aligned; d_ids: uint32_t[n][2], 8-byte aligned, or NULL; d_atten:
+ *              double[n][3], 8-byte aligned; d_status: int32_t[n], 4-byte aligned; d_hits: rtow_hit_t[n], 8-byte aligned,
+ *              or NULL (no records are written).  All DEVICE pointers.  All n entries of every non-NULL output are
+ *              written and nothing beyond n.  d_next == d_rays is allowed (ray i is read before next i is written, and no
+ *              other index is touched); any other overlap is undefined.
+ *   precision  RTOW_F64_STRICT: hit is bit-identical to strict rtow_intersect on the same ray and kernel, next to the
+ *                               next segment of the oracle's path, atten on a miss to the sky strict rtow_radiance adds;
+ *              RTOW_F64_FAST:   the fast build's walks and contracted arithmetic;
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ *   kernel     as rtow_intersect_device: the same resolution, fallbacks, residency rules (RTOW_ENOSCENE after a lean
+ *              upload) and kernel_used; RTOW_KERNEL_REFTREE is strict only.  GRID walks the direction with -0.0 replaced
+ *              by +0.0; the hit record and the scatter use the caller's direction.
+ * Enqueued on hip_stream with the ordering rule of rtow_intersect_device; returns without synchronising unless stats !=
+ * NULL, which synchronises and fills segments = n_rays, prim_tests, node_tests, kernel_ms, total_ms, kernel_used.
+ * Errors: those of rtow_radiance_device, and RTOW_EINVAL for bounce < 0, a NULL d_next, d_atten or d_status with
+ * n_rays > 0, or a misaligned buffer.  n_rays == 0 returns RTOW_OK and launches nothing.  One call in flight per context.
+ * The render path is not involved: the profile ring and the dropped-sample word are untouched, and a render, an
+ * rtow_intersect or an rtow_radiance after any number of steps is bit-identical to one without them. */
+typedef struct rtow_step_params_t {  /* 16 B */
+  uint64_t seed;          /* Philox key, as rtow_config_t::seed */
+  int32_t bounce;         /* >= 0: this segment's index on its path; the scatter draws request 1 + bounce */
+  uint32_t sample_first;  /* added (mod 2^32) to every ray's sample index, as in rtow_radiance */
+} rtow_step_params_t;
+
+#define RTOW_STEP_MISS 0
+#define RTOW_STEP_SCATTERED 1
+#define RTOW_STEP_ABSORBED 2
+#define RTOW_STEP_SKIPPED 3
+
+int rtow_path_step_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_step_params_t *params,
+                          const void *d_rays, int64_t n_rays, const void *d_ids /* uint32_t[n_rays][2] or NULL */,
+                          void *d_next /* rtow_ray_t[n_rays]; may equal d_rays */, void *d_atten /* double[n_rays][3] */,
+                          void *d_status /* int32_t[n_rays] */, void *d_hits /* rtow_hit_t[n_rays] or NULL */,
+                          void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous.  hits may be NULL. */
+int rtow_path_step(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_step_params_t *params,
+                   const rtow_ray_t *rays, int64_t n_rays, const uint32_t *ids, rtow_ray_t *next, double *atten,
+                   int32_t *status, rtow_hit_t *hits, rtow_stats_t *stats);
+
 /* ---- the camera stage: primaries of the resident camera, first-hit guide buffers ----------------------------------------
  * The one piece of the render the queries above leave out: Camera::get_ray (src/render.cpp:158-159,
  * src/common-model.cpp:156-167) for the camera of the scene resident in ctx (after the last upload or refit), fed from

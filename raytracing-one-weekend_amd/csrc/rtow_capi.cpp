@@ -107,6 +107,13 @@ using RadianceLaunchFn = int(const TraceParams &p, const void *rays, const void 
                              int grid, int block, unsigned lds_bytes, void *stream);
 RadianceLaunchFn launch_radiance_strict, launch_radiance_fast;
 QueryOccupancyFn radiance_occupancy_strict, radiance_occupancy_fast;
+// csrc/rtow_step_{strict,fast}.hip (rtow_step.h): the path-step query — one segment per ray; `p` carries the seed beside
+// the walks' fields, `request` is 1 + bounce
+using StepLaunchFn = int(const TraceParams &p, const void *rays, const void *ids, void *next, void *atten, void *status,
+                         void *hits, uint32_t n, uint32_t request, uint32_t sample_first, const int32_t *map,
+                         unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
+StepLaunchFn launch_step_strict, launch_step_fast;
+QueryOccupancyFn step_occupancy_strict, step_occupancy_fast;
 // csrc/rtow_guides_{strict,fast}.hip (rtow_guides.h): the camera stage — the primaries of the resident camera and the
 // first-hit guide buffers; `p` carries the camera, the image size, the rank's rows and the seed beside the walks' fields
 using GuidesLaunchFn = int(const TraceParams &p, void *out, uint32_t n, uint32_t sample_first, int32_t samples,
@@ -173,7 +180,7 @@ void rtow_ctx_destroy(rtow_ctx *c) {
                     &c->blob32, &c->gblob32, &c->cam32_dev, &c->blob4,
                     &c->partials, &c->stack, &c->counters, &c->spill, &c->out, &c->out8, &c->rtree, &c->counters_init,
                     &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_occ, &c->q_map[0], &c->q_map[1],
-                    &c->q_map[2], &c->q_stack, &c->q_ids, &c->q_rgb, &c->q_guides, &c->q_khits, &c->q_kcounts,
+                    &c->q_map[2], &c->q_stack, &c->q_ids, &c->q_rgb, &c->q_status, &c->q_guides, &c->q_khits, &c->q_kcounts,
                     &c->rf.map2, &c->rf.map4, &c->rf.par2, &c->rf.par4, &c->rf.need4, &c->rf.flags,
                     &c->rf.nbox2, &c->rf.nbox4, &c->rf.sbox4, &c->rf.pbox, &c->rf.partials, &c->rf.area, &c->rf.g_sph,
                     &c->rf.g_mov, &c->rf.g_tri, &c->tile_table})
@@ -1425,6 +1432,78 @@ static int radiance_host(rtow_ctx *c, int32_t precision, int32_t kernel, const r
   return RTOW_OK;
 }
 
+// The path-step query (rtow_path_step*, csrc/rtow_step.h): the closest-hit query's strategy, launch shape, ordering, stats
+// and id translation (query_begin / query_launch / query_map) around a kernel that traces one segment per ray and
+// scatters it.  BRUTE reports n * n_prims primitive tests, as rtow_intersect does.
+static int step_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const rtow_step_params_t *prm, const void *d_rays,
+                       int64_t n, const void *d_ids, void *d_next, void *d_atten, void *d_status, void *d_hits,
+                       void *hip_stream, rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (!prm) return fail(RTOW_EINVAL, "params is NULL");
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
+  if (n > 0 && (!d_rays || !d_next || !d_atten || !d_status))
+    return fail(RTOW_EINVAL, "NULL ray, next-ray, attenuation or status buffer");
+  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
+  if (((uintptr_t)d_ids & 7u) != 0u) return fail(RTOW_EINVAL, "ids buffer must be 8-byte aligned");
+  if (((uintptr_t)d_next & 15u) != 0u) return fail(RTOW_EINVAL, "next-ray buffer must be 16-byte aligned");
+  if (((uintptr_t)d_atten & 7u) != 0u) return fail(RTOW_EINVAL, "attenuation buffer must be 8-byte aligned");
+  if (((uintptr_t)d_status & 3u) != 0u) return fail(RTOW_EINVAL, "status buffer must be 4-byte aligned");
+  if (((uintptr_t)d_hits & 7u) != 0u) return fail(RTOW_EINVAL, "hit buffer must be 8-byte aligned");
+  if (prm->bounce < 0) return fail(RTOW_EINVAL, "bounce %d < 0", prm->bounce);
+  QueryRun q;
+  int rc;
+  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
+  if (n == 0) return RTOW_OK;
+
+  const int kernel = q.kernel;
+  const int32_t *map = nullptr;
+  if (d_hits && (rc = query_map_for(c, kernel, &map))) return rc;
+  const int block = q.shape.block;
+  const unsigned lds = q.shape.lds_bytes;
+  const int build = q.strict ? 0 : 1;
+  rtow::StepLaunchFn *const launch[2] = {rtow::launch_step_strict, rtow::launch_step_fast};
+  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::step_occupancy_strict, rtow::step_occupancy_fast};
+  const int occ = occupancy[build](kernel, block, lds, nullptr);
+  rc = query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P0, unsigned long long *counters, int grid) {
+    rtow::TraceParams P = P0;
+    P.seed_lo = (uint32_t)(prm->seed & 0xffffffffu);
+    P.seed_hi = (uint32_t)(prm->seed >> 32);
+    return launch[build](P, d_rays, d_ids, d_next, d_atten, d_status, d_hits, (uint32_t)n, 1u + (uint32_t)prm->bounce,
+                         prm->sample_first, map, counters, kernel, grid, block, lds, hip_stream);
+  });
+  if (rc == RTOW_OK && stats && kernel == RTOW_KERNEL_BRUTE) stats->prim_tests = (uint64_t)n * (uint64_t)c->n_prims;
+  return rc;
+}
+
+// (the rays are stepped in place in q_rays; the attenuations go through the radiance query's q_rgb)
+static int step_host(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_step_params_t *prm, const rtow_ray_t *rays,
+                     int64_t n, const uint32_t *ids, rtow_ray_t *next, double *atten, int32_t *status, rtow_hit_t *hits,
+                     rtow_stats_t *stats) {
+  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
+  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
+  if (n > 0 && (!rays || !next || !atten || !status))
+    return fail(RTOW_EINVAL, "NULL ray, next-ray, attenuation or status array");
+  if (n == 0)
+    return step_device(c, precision, kernel, prm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stats);
+  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_ray_t))) || (rc = c->q_rgb.ensure((size_t)n * 24)) ||
+      (rc = c->q_status.ensure((size_t)n * sizeof(int32_t))) || (ids && (rc = c->q_ids.ensure((size_t)n * 8))) ||
+      (hits && (rc = c->q_hits.ensure((size_t)n * sizeof(rtow_hit_t)))))
+    return rc;
+  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
+  if (ids) HIPCHK(hipMemcpy(c->q_ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+  if ((rc = step_device(c, precision, kernel, prm, c->q_rays.p, n, ids ? c->q_ids.p : nullptr, c->q_rays.p, c->q_rgb.p,
+                        c->q_status.p, hits ? c->q_hits.p : nullptr, nullptr, stats)))
+    return rc;
+  HIPCHK(hipMemcpy(next, c->q_rays.p, (size_t)n * sizeof(rtow_ray_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(atten, c->q_rgb.p, (size_t)n * 24, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(status, c->q_status.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (hits) HIPCHK(hipMemcpy(hits, c->q_hits.p, (size_t)n * sizeof(rtow_hit_t), hipMemcpyDeviceToHost));
+  return RTOW_OK;
+}
+
 // The camera stage (rtow_camera_rays*, rtow_guides*, csrc/rtow_guides.h): the queries' strategy, launch shape, ordering and
 // stats (query_begin / query_launch) around kernels that generate the render's primaries themselves.  CameraCall: what a
 // render of `cfg` would trace on this rank — its rows and its sample set (level_plan's strict form: the reference's).
@@ -1789,6 +1868,20 @@ int rtow_radiance_device(rtow_ctx *c, int32_t precision, int32_t kernel, const r
                          rtow_stats_t *stats) {
   return guarded("rtow_radiance_device", [&] {
     return radiance_device(c, precision, kernel, params, d_rays, n_rays, d_ids, d_rgb_sums, hip_stream, stats);
+  });
+}
+int rtow_path_step_device(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_step_params_t *params, const void *d_rays,
+                          int64_t n_rays, const void *d_ids, void *d_next, void *d_atten, void *d_status, void *d_hits,
+                          void *hip_stream, rtow_stats_t *stats) {
+  return guarded("rtow_path_step_device", [&] {
+    return step_device(c, precision, kernel, params, d_rays, n_rays, d_ids, d_next, d_atten, d_status, d_hits, hip_stream, stats);
+  });
+}
+int rtow_path_step(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_step_params_t *params, const rtow_ray_t *rays,
+                   int64_t n_rays, const uint32_t *ids, rtow_ray_t *next, double *atten, int32_t *status, rtow_hit_t *hits,
+                   rtow_stats_t *stats) {
+  return guarded("rtow_path_step", [&] {
+    return step_host(c, precision, kernel, params, rays, n_rays, ids, next, atten, status, hits, stats);
   });
 }
 int rtow_radiance(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params, const rtow_ray_t *rays,

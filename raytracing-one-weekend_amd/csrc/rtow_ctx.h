@@ -288,6 +288,8 @@ struct rtow_ctx {
   // at the first closest-hit query that needs them after an upload (query_map)
   DevBuf q_counters, q_spill, q_rays, q_hits, q_occ, q_map[3];
   DevBuf q_stack, q_ids, q_rgb;  // rtow_radiance*: the strict build's path stack (sized per launch), the host form's staging
+  DevBuf q_status;               // rtow_path_step: the host form's status words (its rays step in place in q_rays, its
+                                 // attenuations and hits go through q_rgb and q_hits)
   DevBuf q_guides;               // rtow_guides: the host form's staging (rtow_camera_rays stages in q_rays / q_ids)
   DevBuf q_khits, q_kcounts;     // rtow_first_hits, rtow_nearest: the host forms' staging (their inputs go through q_rays)
   bool q_map_ok[3] = {false, false, false};

@@ -3,9 +3,10 @@
 //
 // What it computes: for every caller ray, the sum over its samples of the reference's ray_color (src/render.cpp:112-129)
 // — the render's per-sample work without its camera.  The walks are the trace kernels', included read-only below exactly
-// as rtow_query.h includes them; the hit record and the material fetch (rtow_trace_body.h, the `do_scat` block), the
-// scatter (scatter_dir), the sky and the unwind of the recursion are restated here expression for expression.  The
-// strict build's comparison with the oracle (tests/test_gpu_radiance.py) is what proves the copy.
+// as rtow_query.h includes them; the shading surface and the material fetch (rtow_trace_body.h, the `do_scat` block),
+// the scatter (scatter_dir) and the sky are restated expression for expression in rtow_scatter.h, which the path-step
+// query shares; the unwind of the recursion is here.  The strict build's comparison with the oracle
+// (tests/test_gpu_radiance.py) is what proves the copy.
 //
 // Philox identity: sample j of ray i is (pixel, sample) = (ids[i][0], ids[i][1] + sample_first + j), or (i, sample_first
 // + j) without ids; bounce b draws request 1 + b.  Request 0 is the render's camera block and is never drawn here.
@@ -50,6 +51,7 @@ namespace {
 #include "rtow_trace_reftree.h"
 #endif
 #include "rtow_kernel_frame.h"
+#include "rtow_scatter.h"
 
 struct RadianceParams {
   TraceParams P;               // the scene (P.sc), seed_lo / seed_hi, max_child_rays, stack, n_lanes, spill, the walk fields
@@ -61,13 +63,6 @@ struct RadianceParams {
   uint32_t sample_first;
   unsigned long long *counters;  // [0] primitive tests, [1] node tests, [2] segments, [3] queue head
 };
-
-// -0.0 -> +0.0, every other value unchanged (rtow_query.h: the grid walk's DDA takes its step direction from `d >= 0`
-// and its increments from rcp(d), which disagree for -0.0; the hit tests give the same t and primitive either way).
-__device__ __forceinline__ double plus_zero(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return __longlong_as_double((long long)(b == 0x8000000000000000ull ? 0ull : b));
-}
 
 // Rays bought per atomic on the queue head while the queue is long: 64 of 16 samples or more, and as many more of
 // shorter ones as keeps a batch near 1024 samples (up to 1024 rays).  The one counter word serves about 90 requests per
@@ -115,46 +110,6 @@ __device__ __forceinline__ unsigned long long take_rays(RayPool &pool, unsigned 
     pool.next += want;
   }
   return mine;
-}
-
-// Material::scatter (src/common-model.cpp:13-62): rtow_trace_body.h's scatter_dir, restated — the new direction, or
-// absorbed; the point of the unit ball and the dielectric coin come from the bounce's one Philox block.
-__device__ __forceinline__ bool scatter_dir(Rng &g, uint32_t k0, uint32_t k1, int kind, real m_fuzz, real m_ir, V3 rd,
-                                            V3 normal, bool front, V3 &dir) {
-  uint32_t o0, o1, o2, o3;
-  philox4x32(g.r, g.sample, g.pixel, 0u, k0, k1, o0, o1, o2, o3);
-  g.r += 1u;
-  V3 dirbase = {0, 0, 0};
-  if (kind == 2) {
-    const real ir = m_ir;
-    const V3 unit = normalize(rd);
-    const real cos_theta = dot(-unit, normal);
-    const real sin_theta = fast_sqrt(real(1.0) - cos_theta * cos_theta);
-    const real ratio = front ? fast_rcp(ir) : ir;
-    bool refl = ratio * sin_theta > real(1.0);
-    if (!refl) {  // src/common-model.cpp:53-54: the coin is drawn only if refraction is possible
-      real r0 = fast_div(real(1.0) - ratio, real(1.0) + ratio);
-      r0 = r0 * r0;
-      const real x = real(1.0) - cos_theta;
-      const real x2 = x * x;
-      const real R = r0 + (real(1.0) - r0) * (x2 * x2 * x);
-      refl = R > coin_from_block(o0, o1, o3);
-    }
-    dirbase = refl ? reflect(unit, normal) : refract(unit, normal, ratio);
-  } else if (kind == 1) {
-    dirbase = reflect(rd, normal);
-  }
-  // random_unit_vector() (random-utils.cpp:31-33): the point of the unit ball's positive octant, un-normalised
-  const V3 rnd = ball_from_block(o0, o1, o2, o3);
-  bool absorbed = false;
-  if (kind == 0) {
-    absorbed = rabs(normal.x - rnd.x) < real(1e-8) && rabs(normal.y - rnd.y) < real(1e-8) &&
-               rabs(normal.z - rnd.z) < real(1e-8);
-    dir = normal + rnd;
-  } else {
-    dir = dirbase + m_fuzz * rnd;
-  }
-  return !absorbed;
 }
 
 // KERNEL: 1 = STREAM, 2 = BVH, 3 = GRID, 4 = BVH4, 5 = REFTREE (strict build only); LDS: the scene image is staged in
@@ -243,101 +198,13 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
       need_sample = false;
     }
     if (do_scat) {
-      // the Hit of the winner (src/common-model.cpp:83-90, :121) and its material: rtow_trace_body.h, `do_scat`
-      V3 normal;
-      bool front = true;
-      int mi, kind;
-      real m_fuzz, m_ir;
-#ifdef RTOW_FAST_MATH
-      V3 m_att;
-#endif
       ro = ro + rd * best.t;  // Ray::at: the origin of the scattered ray
-      const int pid = best.prim;
-      if constexpr (KERNEL == 4) {
-        const uint32_t r = sc.b4_off_tri + 96u * (uint32_t)pid;
-        const vd2 q4 = im4.t2(r + 64u), q5 = im4.t2(r + 80u);
-        normal = {(real)q4.y, (real)q5.x, (real)q5.y};
-        mi = (int)im4.u32(sc.b4_off_pmat + 4u * (uint32_t)pid);
-        const uint32_t mr = sc.b4_off_mats + 48u * (uint32_t)mi;
-        const vd2 m1 = im4.d2(mr + 16u), m2 = im4.d2(mr + 32u);  // {att.z, fuzz}, {ir, kind|pad}
-#ifdef RTOW_FAST_MATH
-        const vd2 m0 = im4.d2(mr);  // {att.x, att.y}
-        m_att = V3{(real)m0.x, (real)m0.y, (real)m1.x};
-#endif
-        m_fuzz = (real)m1.y;
-        m_ir = (real)m2.x;
-        kind = (int)(__double_as_longlong(m2.y) & 0xffffffffll);
-      } else if constexpr (KERNEL == 2 || KERNEL == 3) {
-        const uint32_t o_sph = KERNEL == 3 ? sc.g_off_sph : sc.off_sph;
-        const uint32_t o_mov = KERNEL == 3 ? sc.g_off_mov : sc.off_mov;
-        const uint32_t o_tri = KERNEL == 3 ? sc.g_off_tri : sc.off_tri;
-        const uint32_t o_pmat = KERNEL == 3 ? sc.g_off_pmat : sc.off_pmat;
-        const uint32_t o_mats = KERNEL == 3 ? sc.g_off_mats : sc.off_mats;
-        if (pid < sc.n_sph + sc.n_mov) {
-          V3 center;
-          bool inward;  // negative radius: only the sign of the signed r*r is used here
-          if (pid < sc.n_sph) {
-            const double2 p0 = im.d2(o_sph + 32u * (uint32_t)pid), p1 = im.d2(o_sph + 32u * (uint32_t)pid + 16u);
-            center = {(real)p0.x, (real)p0.y, (real)p1.x};
-            inward = p1.y < 0.0;
-          } else {
-            const uint32_t r = o_mov + 64u * (uint32_t)(pid - sc.n_sph);
-            const double2 p0 = im.d2(r), p1 = im.d2(r + 16u), p2 = im.d2(r + 32u), p3 = im.d2(r + 48u);
-            center = {p0.x + rtime * p1.y, p0.y + rtime * p2.x, p1.x + rtime * p2.y};
-            inward = p3.x < 0.0;
-          }
-          normal = normalize(ro - center);
-          front = (dot(rd, normal) < real(0.0)) ^ inward;
-          normal = front ? normal : -normal;
-        } else {
-          const uint32_t r = o_tri + 96u * (uint32_t)(pid - sc.n_sph - sc.n_mov);
-          const double2 q4 = im.d2(r + 64u), q5 = im.d2(r + 80u);
-          normal = {q4.y, q5.x, q5.y};
-        }
-        mi = (int)im.u32(o_pmat + 4u * (uint32_t)pid);
-        const uint32_t mr = o_mats + 48u * (uint32_t)mi;
-        const double2 m1 = im.d2(mr + 16u), m2 = im.d2(mr + 32u);  // {att.z, fuzz}, {ir, kind|pad}
-#ifdef RTOW_FAST_MATH
-        const double2 m0 = im.d2(mr);  // {att.x, att.y}
-        m_att = V3{(real)m0.x, (real)m0.y, (real)m1.x};
-#endif
-        m_fuzz = (real)m1.y;
-        m_ir = (real)m2.x;
-        kind = (int)(__double_as_longlong(m2.y) & 0xffffffffll);
-      } else {
-        if (pid < sc.n_sph + sc.n_mov) {
-          V3 center;
-          bool inward;
-          if (pid < sc.n_sph) {
-            const double *q = sc.sph + 4 * (size_t)pid;
-            center = {(real)q[0], (real)q[1], (real)q[2]};
-            inward = sc.sph_r[pid] < 0.0;
-          } else {
-            const double *q = sc.mov + 8 * (size_t)(pid - sc.n_sph);
-            center = {q[0] + rtime * q[3], q[1] + rtime * q[4], q[2] + rtime * q[5]};
-            inward = q[7] < 0.0;
-          }
-          normal = normalize(ro - center);
-          front = (dot(rd, normal) < real(0.0)) ^ inward;
-          normal = front ? normal : -normal;
-        } else {
-          const double *q = sc.tri + 12 * (size_t)(pid - sc.n_sph - sc.n_mov);
-          normal = {(real)q[9], (real)q[10], (real)q[11]};
-        }
-        mi = sc.prim_mat[pid];
-        const DevMaterial *m = sc.mats + mi;
-#ifdef RTOW_FAST_MATH
-        m_att = V3{(real)m->att[0], (real)m->att[1], (real)m->att[2]};
-#endif
-        kind = m->kind;
-        m_fuzz = (real)m->fuzz;
-        m_ir = (real)m->ir;
-      }
+      const Surface sf = surface_at<KERNEL, LDS>(im, im4, sc, ro, rd, rtime, best.prim);
       pending_hit = false;
       // (the new direction is written over the old one; an absorbed path — black, src/render.cpp:120 — starts its next
       // sample in the next trip and never reads it)
       V3 dir;
-      const bool scattered = scatter_dir(g, k0, k1, kind, m_fuzz, m_ir, rd, normal, front, dir);
+      const bool scattered = scatter_dir(g, k0, k1, sf.kind, sf.fuzz, sf.ir, rd, sf.normal, sf.front, dir);
       rd = dir;
       if (!scattered) {
         need_sample = true;
@@ -345,9 +212,9 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
         ++g.sample;
       } else {
 #ifdef RTOW_FAST_MATH
-        throughput = throughput * m_att;
+        throughput = throughput * material_att<KERNEL, LDS>(im, im4, sc, (uint32_t)sf.mi);
 #else
-        P.stack[(size_t)nb * P.n_lanes + lane_g] = (uint32_t)mi;
+        P.stack[(size_t)nb * P.n_lanes + lane_g] = (uint32_t)sf.mi;
 #endif
         ++nb;
         --depth;
@@ -388,27 +255,12 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
           pending_hit = true;  // scattered at the top of the next trip
       } else {
         // ---- background + unwind of the recursion (src/render.cpp:119,122-128) ----
-        const V3 unit = normalize(rd);
-        const real t = real(0.5) * (unit.y + real(+1.0));
-        V3 c = (real(1.0) - t) * V3{1, 1, 1} + t * V3{real(0.5), real(0.7), real(1.0)};
+        V3 c = sky_color(rd);
 #ifdef RTOW_FAST_MATH
         c = throughput * c;
 #else
-        for (int q = nb - 1; q >= 0; --q) {
-          const uint32_t smi = P.stack[(size_t)q * P.n_lanes + lane_g];
-          if constexpr (KERNEL == 4) {
-            const uint32_t mr = sc.b4_off_mats + 48u * smi;
-            const vd2 a0 = im4.d2(mr), a1 = im4.d2(mr + 16u);
-            c = V3{(real)a0.x, (real)a0.y, (real)a1.x} * c;
-          } else if constexpr (KERNEL == 2 || KERNEL == 3) {
-            const uint32_t mr = (KERNEL == 3 ? sc.g_off_mats : sc.off_mats) + 48u * smi;
-            const double2 a0 = im.d2(mr), a1 = im.d2(mr + 16u);
-            c = V3{(real)a0.x, (real)a0.y, (real)a1.x} * c;
-          } else {
-            const DevMaterial *m = sc.mats + smi;
-            c = V3{(real)m->att[0], (real)m->att[1], (real)m->att[2]} * c;
-          }
-        }
+        for (int q = nb - 1; q >= 0; --q)
+          c = material_att<KERNEL, LDS>(im, im4, sc, P.stack[(size_t)q * P.n_lanes + lane_g]) * c;
 #endif
         {
           // never fused with the multiply that produced `c` (the empty asm hides it from the contraction pass): the

@@ -146,6 +146,15 @@ class RadianceParams(C.Structure):
                 ("sample_first", C.c_uint32), ("pad_", C.c_int32)]
 
 
+class StepParams(C.Structure):
+    """rtow_step_params_t (16 B): Philox key, the segment's index on its path, offset of every ray's sample index."""
+    _fields_ = [("seed", C.c_uint64), ("bounce", C.c_int32), ("sample_first", C.c_uint32)]
+
+
+# rtow_path_step*: what became of each ray (RTOW_STEP_* of include/rtow.h)
+STEP_MISS, STEP_SCATTERED, STEP_ABSORBED, STEP_SKIPPED = 0, 1, 2, 3
+
+
 # numpy views of the same layouts (arrays of rays / hits for rtow_intersect*)
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("time", "<f8"), ("direction", "<f8", (3,)), ("tmax", "<f8")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("prim", "<i4"), ("kind", "<i4"),
@@ -201,7 +210,7 @@ EXPORTS = [
     "rtow_debug_tile_order", "rtow_radiance_device", "rtow_radiance",
     "rtow_camera_rays_device", "rtow_camera_rays", "rtow_camera_ray_count", "rtow_guides_device", "rtow_guides",
     "rtow_debug_last_spec", "rtow_first_hits_device", "rtow_first_hits", "rtow_nearest_device", "rtow_nearest",
-    "rtow_debug_last_counted", "rtow_debug_walk_consts",
+    "rtow_debug_last_counted", "rtow_debug_walk_consts", "rtow_path_step_device", "rtow_path_step",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -308,6 +317,12 @@ def lib():
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rtow_radiance.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RadianceParams), C.c_void_p, C.c_int64,
                                     C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    if hasattr(L, "rtow_path_step"):
+        L.rtow_path_step_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(StepParams), C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(Stats)]
+        L.rtow_path_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(StepParams), C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     if hasattr(L, "rtow_guides"):
         L.rtow_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]
         L.rtow_camera_rays.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p]
@@ -699,6 +714,49 @@ class Context:
                                          C.c_void_p(d_ids) if d_ids else None, C.c_void_p(d_rgb), C.c_void_p(stream),
                                          C.byref(st) if st is not None else None),
               "rtow_radiance_device")
+        return st
+
+    def path_step(self, rays, bounce, seed=1, ids=None, sample_first=0, precision=F64_FAST, kernel=KERNEL_AUTO,
+                  want_stats=False, want_hits=True):
+        """One path segment per ray (a RAY_DTYPE array, host memory): the closest hit in [0.001, tmax], then the
+        reference's scatter drawn from request 1 + `bounce` of the ray's Philox identity.  Returns (status, next_rays,
+        atten, hits) — int32 [n] STEP_*, a RAY_DTYPE array (the dead ray, tmax = -1, where the path ended), [n, 3] float64
+        and a HIT_DTYPE array (None without `want_hits`) — plus Stats with `want_stats` (rtow_path_step).  `ids`: [n, 2]
+        uint32 (pixel, sample) identities; None: (i, 0)."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        n = len(r)
+        idp = None
+        if ids is not None:
+            ida = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1, 2)
+            if len(ida) != n:
+                raise ValueError("ids must be [n, 2]")
+            idp = ida.ctypes.data_as(C.c_void_p)
+        status = np.empty(n, dtype=np.int32)
+        nxt = np.empty(n, dtype=RAY_DTYPE)
+        atten = np.empty((n, 3), dtype=np.float64)
+        hits = np.empty(n, dtype=HIT_DTYPE) if want_hits else None
+        prm = StepParams(seed, bounce, sample_first)
+        st = Stats() if want_stats else None
+        check(lib().rtow_path_step(self._h, precision, kernel, C.byref(prm), r.ctypes.data_as(C.c_void_p), n, idp,
+                                   nxt.ctypes.data_as(C.c_void_p), atten.ctypes.data_as(C.c_void_p),
+                                   status.ctypes.data_as(C.c_void_p),
+                                   hits.ctypes.data_as(C.c_void_p) if hits is not None else None,
+                                   C.byref(st) if st is not None else None), "rtow_path_step")
+        return (status, nxt, atten, hits, st) if want_stats else (status, nxt, atten, hits)
+
+    def path_step_device(self, d_rays: int, n: int, d_ids: int, d_next: int, d_atten: int, d_status: int, d_hits: int = 0,
+                         bounce=0, seed=1, sample_first=0, precision=F64_FAST, kernel=KERNEL_AUTO, stream: int = 0,
+                         want_stats=False):
+        """The same on device buffers (raw pointers: n x 64-byte rays, n x 2 uint32 ids or 0, n x 64-byte next rays —
+        which may be the rays themselves —, n x 3 float64 attenuations, n int32 status words, n x 72-byte hits or 0 for
+        none), enqueued on `stream` (rtow_path_step_device); returns Stats with `want_stats` (then synchronised), else
+        None."""
+        prm = StepParams(seed, bounce, sample_first)
+        st = Stats() if want_stats else None
+        check(lib().rtow_path_step_device(self._h, precision, kernel, C.byref(prm), C.c_void_p(d_rays), n,
+                                          C.c_void_p(d_ids) if d_ids else None, C.c_void_p(d_next), C.c_void_p(d_atten),
+                                          C.c_void_p(d_status), C.c_void_p(d_hits) if d_hits else None, C.c_void_p(stream),
+                                          C.byref(st) if st is not None else None), "rtow_path_step_device")
         return st
 
     def camera_rays(self, cfg: Config):
