@@ -1420,4 +1420,41 @@ int orc_aabb_hit(const double bmin[3], const double bmax[3], const double ro[3],
   return aabb_hit(b, r, tmin, tmax) ? 1 : 0;
 }
 
+// scatter() on caller-given inputs, ray by ray: the hit (point, normal, front), the ray (direction, time), the material
+// and request `request` of the Philox identity (seed, ids[i][0], ids[i][1]).  A one-primitive world per ray carries the
+// material to scatter(); nothing of a render is touched.
+void orc_scatter(uint64_t n, const double *point, const double *normal, const int32_t *front, const double *rd,
+                 const double *time, const int32_t *mat_kind, const double *albedo, const double *fuzz,
+                 const double *ir, uint64_t seed, const uint32_t *ids, uint32_t request, int32_t *status,
+                 double *next, double *atten) {
+  World w;
+  w.prims.resize(1);
+  w.mats.resize(1);
+  w.prims[0].mat = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    w.mats[0] = Material{mat_kind[i], load3(albedo + 3 * i), fuzz[i], ir[i]};
+    const Hit hit{0, load3(point + 3 * i), 0.0, load3(normal + 3 * i), front[i] != 0};
+    const Ray rin{V3{0, 0, 0}, load3(rd + 3 * i), time[i]};
+    PhiloxDraw g;
+    g.seed = seed;
+    g.begin_sample(ids[2 * i], ids[2 * i + 1]);
+    g.r = request;
+    Scatter sc;
+    double *nx = next + 8 * i;  // rtow_ray_t: origin, time, direction, tmax
+    if (scatter(w, rin, hit, g, sc)) {
+      status[i] = RTOW_STEP_SCATTERED;
+      store3(nx, sc.r.o);
+      nx[3] = sc.r.time;
+      store3(nx + 4, sc.r.d);
+      nx[7] = std::numeric_limits<double>::infinity();
+      store3(atten + 3 * i, sc.attenuation);
+    } else {  // the dead ray
+      status[i] = RTOW_STEP_ABSORBED;
+      for (int k = 0; k < 7; ++k) nx[k] = 0.0;
+      nx[7] = -1.0;
+      store3(atten + 3 * i, V3{0, 0, 0});
+    }
+  }
+}
+
 }  // extern "C"

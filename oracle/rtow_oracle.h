@@ -84,6 +84,13 @@ int orc_triangle_hit(const double a[3], const double b[3], const double c[3], co
                      const double rd[3], double tmin, double tmax, double *t, double *p, double *n);
 int orc_aabb_hit(const double bmin[3], const double bmax[3], const double ro[3],
                  const double rd[3], double tmin, double tmax);
+/* scatter() of n caller-given hits: point, normal, rd, albedo [n][3]; front, time, mat_kind (RTOW_MAT_*), fuzz, ir [n];
+ * the Philox identity (seed, ids[i][0] = pixel, ids[i][1] = sample) and its request (1 + bounce).  Writes status [n]
+ * (RTOW_STEP_SCATTERED / RTOW_STEP_ABSORBED), next [n] rtow_ray_t (the dead ray when absorbed) and atten [n][3]. */
+void orc_scatter(uint64_t n, const double *point, const double *normal, const int32_t *front, const double *rd,
+                 const double *time, const int32_t *mat_kind, const double *albedo, const double *fuzz,
+                 const double *ir, uint64_t seed, const uint32_t *ids, uint32_t request, int32_t *status,
+                 double *next, double *atten);
 
 #ifdef __cplusplus
 }

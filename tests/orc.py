@@ -74,8 +74,41 @@ def lib():
                                  C.POINTER(C.c_int)]
     L.orc_triangle_hit.argtypes = [d3, d3, d3, d3, d3, C.c_double, C.c_double, _pd, _pd, _pd]
     L.orc_aabb_hit.argtypes = [d3, d3, d3, d3, C.c_double, C.c_double]
+    bind_scatter(L)
     _lib = L
     return L
+
+
+def bind_scatter(L):
+    """The prototype of orc_scatter on a handle of the oracle (liboracle.so or its contracted build)."""
+    pi32, pu32 = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+    L.orc_scatter.argtypes = [C.c_uint64, _pd, _pd, pi32, _pd, _pd, pi32, _pd, _pd, _pd, C.c_uint64, pu32, C.c_uint32,
+                              pi32, _pd, _pd]
+    L.orc_scatter.restype = None
+
+
+def scatter(point, normal, front, rd, time, mats, seed, ids, request, L=None):
+    """orc_scatter: the oracle's scatter() of n caller-given hits.  point, normal, rd [n, 3]; front, time [n]; mats [n, 6]
+    rows (albedo xyz, fuzz, ir, kind) as scene_arrays gives them; ids [n, 2] (pixel, sample); request = 1 + bounce.
+    Returns (status int32 [n], next RAY_DTYPE [n], atten [n, 3]).  L: the library (default liboracle.so)."""
+    L = lib() if L is None else L
+    f8 = lambda a, w: np.ascontiguousarray(np.asarray(a, np.float64).reshape((-1,) + w))  # noqa: E731
+    point, normal, rd = f8(point, (3,)), f8(normal, (3,)), f8(rd, (3,))
+    n = len(point)
+    time, mats = f8(time, ()), f8(mats, (6,))
+    front = np.ascontiguousarray(front, np.int32).reshape(-1)
+    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1, 2)
+    assert len(normal) == len(rd) == len(time) == len(mats) == len(front) == len(ids) == n
+    albedo, fuzz, ir = f8(mats[:, 0:3], (3,)), f8(mats[:, 3], ()), f8(mats[:, 4], ())
+    kind = np.ascontiguousarray(mats[:, 5], np.int32)
+    status = np.zeros(n, np.int32)
+    nxt = np.zeros(n, rtow.RAY_DTYPE)
+    atten = np.zeros((n, 3))
+    pd = lambda a: a.ctypes.data_as(_pd)  # noqa: E731
+    pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+    L.orc_scatter(n, pd(point), pd(normal), pi(front), pd(rd), pd(time), pi(kind), pd(albedo), pd(fuzz), pd(ir),
+                  int(seed), ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(request), pi(status), pd(nxt), pd(atten))
+    return status, nxt, atten
 
 
 class OrcScene:

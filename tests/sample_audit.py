@@ -155,7 +155,8 @@ _contracted = None
 
 
 def contracted_oracle():
-    """ctypes handle of oracle/liboracle_contracted.so (built on demand, like orc.lib()): orc_render_ex only."""
+    """ctypes handle of oracle/liboracle_contracted.so (built on demand, like orc.lib()): orc_render_ex and
+    orc_scatter."""
     global _contracted
     if _contracted is not None:
         return _contracted
@@ -168,6 +169,7 @@ def contracted_oracle():
     L = C.CDLL(str(CONTRACTED_LIB))
     L.orc_render_ex.argtypes = [C.POINTER(rtow.Scene), C.POINTER(rtow.Config), C.c_int, C.c_int, C.c_int, _pd,
                                 C.POINTER(orc.OrcStats)]
+    orc.bind_scatter(L)
     _contracted = L
     return L
 

@@ -117,6 +117,14 @@ def sum_in_order(per_sample, spp):
     return s
 
 
+def sky_of_strict(d):
+    """The reference's background for directions d [n, 3], operation by operation in binary64 (ray_color's last lines)."""
+    d = np.asarray(d, np.float64).reshape(-1, 3)
+    dot = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+    t = 0.5 * (d[:, 1] * (1.0 / np.sqrt(dot)) + 1.0)
+    return np.stack([(1.0 - t) * 1.0 + t * k for k in (0.5, 0.7, 1.0)], axis=1)
+
+
 def expected_kernel(scene, kernel):
     """The render's fallbacks, for a host scene or a SceneView: BVH4 walks triangle meshes only; GRID falls back to BVH
     where there is no grid."""

@@ -15,7 +15,7 @@ import pytest
 import guides_exact as gx
 import rtow
 from guides_ref import CAP, SCENES, Logged, Parts, fold_guides, guide_values, within_cap
-from support_oracle import brute_force, same_bits, sum_in_order
+from support_oracle import brute_force, same_bits, sky_of_strict, sum_in_order
 from support_scenes import SceneView
 
 BUILDS = [gx.STRICT, gx.FAST]
@@ -46,10 +46,7 @@ def oracle_hits(view, lg):
 
 def oracle_sky(rays):
     """ray_color's miss branch in binary64, the oracle's operand order: unit = d * (1 / sqrt(d.d))."""
-    d = rays["direction"]
-    unit_y = d[:, 1] * (1.0 / np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]))
-    t = 0.5 * (unit_y + 1.0)
-    return (1.0 - t)[:, None] * np.ones(3)[None, :] + t[:, None] * gx.SKY[None, :]
+    return sky_of_strict(rays["direction"])
 
 
 class Case:
