@@ -6,33 +6,17 @@
 // There is no CPU fallback: without a usable HIP device every entry point fails
 // with RTOW_ENODEV / RTOW_EHIP.
 //
-// This file renders and queries the resident scene; what makes a scene resident (upload, refit, the diagnostics
-// that read the images back) is rtow_scene.cpp.  rtow_ctx.h is what the two share.
+// This file creates the context and renders the resident scene; what makes a scene resident (upload, refit, the
+// diagnostics that read the images back) is rtow_scene.cpp, and every query over it is rtow_queries.cpp.  rtow_ctx.h is
+// what the three share.
 
 #include "rtow_ctx.h"
 
 namespace {
-
 thread_local std::string g_err;
-
-// No C++ exception crosses the C ABI (include/rtow.h): the entry points that allocate or start threads run
-// their bodies through this.
-template <class F>
-int guarded(const char *what, F &&f) noexcept {
-  try {
-    return f();
-  } catch (const std::bad_alloc &) {
-    return fail(RTOW_ENOMEM, "%s: out of host memory", what);
-  } catch (const std::exception &e) {
-    return fail(RTOW_EINVAL, "%s: %s", what, e.what());
-  } catch (...) {
-    return fail(RTOW_EINVAL, "%s: unknown C++ exception", what);
-  }
-}
-
 }  // namespace
 namespace rtow {
-// for the other translation units of the library (rtow_multi.cpp): same thread-local message
+// for the other translation units of the library (rtow_queries.cpp, rtow_multi.cpp): same thread-local message
 int set_last_error(int code, const char *fmt, ...) {
   char buf[512];
   va_list ap;
@@ -45,7 +29,6 @@ int set_last_error(int code, const char *fmt, ...) {
 }  // namespace rtow
 namespace {
 
-constexpr int kBlock = 256;      // STREAM kernel workgroup
 constexpr int kStreamTileMin = 64;  // STREAM kernel: from this many triangles on they are streamed through LDS tiles (below:
                                     //   scalar loads — the kernel's real use, scenes of <= 16 primitives)
 constexpr int kBvhBlock = 512;   // BVH kernel workgroup (one LDS scene image per workgroup)
@@ -77,53 +60,6 @@ rtow::FastDiv make_fastdiv(uint32_t d) {
 }
 
 }  // namespace
-
-namespace rtow {
-// csrc/rtow_{query,occlude,pointq}_{strict,fast}.hip (rtow_query.h, rtow_occlude.h, rtow_pointq.h): the three query kinds
-// share one launcher and one occupancy signature (`map` is unused by the occlusion query)
-using QueryLaunchFn = int(const TraceParams &p, const void *in, void *out, uint32_t n, const int32_t *map,
-                          unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
-using QueryOccupancyFn = int(int kernel, int block, unsigned lds_bytes, int *vgprs);
-QueryLaunchFn launch_query_strict, launch_query_fast, launch_occlude_strict, launch_occlude_fast, launch_pointq_strict,
-    launch_pointq_fast;
-QueryOccupancyFn query_occupancy_strict, query_occupancy_fast, occlude_occupancy_strict, occlude_occupancy_fast,
-    pointq_occupancy_strict, pointq_occupancy_fast;
-// csrc/rtow_first_hits_{strict,fast}.hip (rtow_first_hits.h): the first-k-hits query — max_hits records and one count per ray
-using FirstHitsLaunchFn = int(const TraceParams &p, const void *rays, void *hits, int32_t *counts, uint32_t n,
-                              int32_t max_hits, const int32_t *map, unsigned long long *counters, int kernel, int grid,
-                              int block, unsigned lds_bytes, void *stream);
-FirstHitsLaunchFn launch_first_hits_strict, launch_first_hits_fast;
-QueryOccupancyFn first_hits_occupancy_strict, first_hits_occupancy_fast;
-// csrc/rtow_nearest_{strict,fast}.hip (rtow_nearest.h): the k-nearest query — k records and one count per point
-using NearestLaunchFn = int(const TraceParams &p, const void *queries, void *hits, int32_t *counts, uint32_t n, int32_t k,
-                            const int32_t *map, unsigned long long *counters, int kernel, int grid, int block,
-                            unsigned lds_bytes, void *stream);
-NearestLaunchFn launch_nearest_strict, launch_nearest_fast;
-QueryOccupancyFn nearest_occupancy_strict, nearest_occupancy_fast;
-// csrc/rtow_radiance_{strict,fast}.hip (rtow_radiance.h): the radiance query; `p` carries the seed, max_child_rays and
-// the strict build's path stack beside the walks' fields
-using RadianceLaunchFn = int(const TraceParams &p, const void *rays, const void *ids, void *out, uint32_t n,
-                             int32_t samples_per_ray, uint32_t sample_first, unsigned long long *counters, int kernel,
-                             int grid, int block, unsigned lds_bytes, void *stream);
-RadianceLaunchFn launch_radiance_strict, launch_radiance_fast;
-QueryOccupancyFn radiance_occupancy_strict, radiance_occupancy_fast;
-// csrc/rtow_step_{strict,fast}.hip (rtow_step.h): the path-step query — one segment per ray; `p` carries the seed beside
-// the walks' fields, `request` is 1 + bounce
-using StepLaunchFn = int(const TraceParams &p, const void *rays, const void *ids, void *next, void *atten, void *status,
-                         void *hits, uint32_t n, uint32_t request, uint32_t sample_first, const int32_t *map,
-                         unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
-StepLaunchFn launch_step_strict, launch_step_fast;
-QueryOccupancyFn step_occupancy_strict, step_occupancy_fast;
-// csrc/rtow_guides_{strict,fast}.hip (rtow_guides.h): the camera stage — the primaries of the resident camera and the
-// first-hit guide buffers; `p` carries the camera, the image size, the rank's rows and the seed beside the walks' fields
-using GuidesLaunchFn = int(const TraceParams &p, void *out, uint32_t n, uint32_t sample_first, int32_t samples,
-                           unsigned long long *counters, int kernel, int grid, int block, unsigned lds_bytes, void *stream);
-using CameraRaysLaunchFn = int(const TraceParams &p, void *rays, void *ids, uint32_t n, uint32_t sample_first,
-                               int32_t samples, int grid, int block, void *stream);
-GuidesLaunchFn launch_guides_strict, launch_guides_fast;
-CameraRaysLaunchFn launch_camera_rays_strict, launch_camera_rays_fast;
-QueryOccupancyFn guides_occupancy_strict, guides_occupancy_fast;
-}  // namespace rtow
 
 extern "C" {
 
@@ -206,7 +142,7 @@ void rtow_ctx_destroy(rtow_ctx *c) {
   delete c;
 }
 
-static int validate_cfg(const rtow_config_t *cfg) {
+extern "C++" int rtow::validate_cfg(const rtow_config_t *cfg) {
   if (!cfg) return fail(RTOW_EINVAL, "config is NULL");
   if (cfg->image_width <= 0 || cfg->image_height <= 0)
     return fail(RTOW_EINVAL, "image size %dx%d", cfg->image_width, cfg->image_height);
@@ -621,16 +557,15 @@ static int auto_kernel(const rtow_ctx *c, int precision) {
          : bvh4_ok ? RTOW_KERNEL_BVH4 : RTOW_KERNEL_BVH;
 }
 
-static int resident_kernel(rtow_ctx *c, int precision, int kernel, bool stream_records, int *out);
 // The strategy a request resolves to, with the render's fallbacks and residency rules (shared by the render and the
 // ray queries); the first RTOW_KERNEL_REFTREE request builds the reference's tree.
-static int resolve_kernel(rtow_ctx *c, int precision, int requested, int *out) {
+extern "C++" int rtow::resolve_kernel(rtow_ctx *c, int precision, int requested, int *out) {
   return resident_kernel(c, precision, requested == RTOW_KERNEL_AUTO ? auto_kernel(c, precision) : requested, true, out);
 }
 
 // The fallbacks and residency rules of a chosen strategy.  stream_records: BRUTE reads the STREAM kernel's triangle
 // records (the render and the ray queries; the point query reads the class records every upload keeps).
-static int resident_kernel(rtow_ctx *c, int precision, int kernel, bool stream_records, int *out) {
+extern "C++" int rtow::resident_kernel(rtow_ctx *c, int precision, int kernel, bool stream_records, int *out) {
   const bool strict = precision == RTOW_F64_STRICT;
   const bool f32 = precision == RTOW_F32;
   const bool bvh4_ok = c->have_bvh4 && !f32;  // triangle mesh, host builder, binary64 build
@@ -675,16 +610,8 @@ static int resident_kernel(rtow_ctx *c, int precision, int kernel, bool stream_r
   return RTOW_OK;
 }
 
-// Launch shape of a strategy on the resident scene (shared by the render and the ray queries): workgroup size, LDS
-// bytes and the DevScene fields that go with them (STREAM tiles; BVH4: what is staged, the stack's place and depth).
-struct LaunchShape {
-  rtow::DevScene scene;
-  int block = 0;
-  unsigned lds_bytes = 0;
-  int stack_bound = 0;  // BVH4: traversal stack entries a lane may need (3 x depth + 1)
-  bool image_kernel = false;
-};
-static int launch_shape(rtow_ctx *c, int kernel, bool f32, LaunchShape &s) {
+// Launch shape of a strategy on the resident scene (LaunchShape, rtow_ctx.h; shared by the render and the queries).
+extern "C++" int rtow::launch_shape(rtow_ctx *c, int kernel, bool f32, LaunchShape &s) {
   s.scene = f32 ? c->ds32 : c->ds;
   rtow::DevScene &scene = s.scene;
   int &block = s.block;
@@ -1014,637 +941,6 @@ static int render_levels(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb_sums
   return RTOW_OK;
 }
 
-// ---- ray queries (rtow_intersect / rtow_intersect_device) -------------------------------------------------------------
-constexpr int64_t kMaxQueryRays = (1ll << 31) - 64;  // include/rtow.h
-
-// Walk-order primitive id -> insertion index (the uploaded scene's prim_kind / prim_index order; class-major order when
-// the scene came without one).  which: 0 class-major ids (STREAM, GRID, REFTREE walks and a device-built BVH image),
-// 1 the record slots of a host-built mesh BVH image (ds.leaf_direct), 2 the record slots of the 4-wide image (match_slots).
-// Built on the host at the first query that needs the table after an upload or a refit; both drop them.
-static int query_map(rtow_ctx *c, int which, const int32_t **out) {
-  if (c->q_map_ok[which]) {
-    *out = (const int32_t *)c->q_map[which].p;
-    return RTOW_OK;
-  }
-  const int ns = c->ds.n_sph, nm = c->ds.n_mov, nt = c->ds.n_tri, np = c->n_prims;
-  const rtow_ctx::HostSceneCopy &h = c->host_scene;
-  std::vector<int32_t> cls2ins((size_t)np);
-  for (int i = 0; i < np; ++i) cls2ins[i] = i;
-  if (h.have_order)
-    for (int i = 0; i < np; ++i) {
-      const int k = h.pk[i];
-      const int base = k == RTOW_PRIM_SPHERE ? 0 : (k == RTOW_PRIM_MOVING_SPHERE ? ns : ns + nm);
-      cls2ins[(size_t)base + h.pi[i]] = i;
-    }
-  std::vector<int32_t> table;
-  if (which == 0) {
-    table.swap(cls2ins);
-  } else {
-    // after a refit the records have moved: the maps its first call derived from the images as uploaded
-    std::vector<int32_t> matched;
-    if (!c->rf.ready)
-      if (int rc = match_slots(c, which, matched)) return rc;
-    const std::vector<int32_t> &slot2tri = c->rf.ready ? c->rf.slot2tri[which - 1] : matched;
-    table.assign((size_t)nt, -1);
-    for (int k = 0; k < nt; ++k) table[(size_t)k] = cls2ins[(size_t)ns + nm + slot2tri[(size_t)k]];
-  }
-  DevBuf &b = c->q_map[which];
-  if (int rc = b.ensure(std::max<size_t>(table.size() * sizeof(int32_t), 4))) return rc;
-  if (!table.empty()) HIPCHK(hipMemcpy(b.p, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  c->q_map_ok[which] = true;
-  *out = (const int32_t *)b.p;
-  return RTOW_OK;
-}
-
-// The table the hits of `kernel`'s walk need: the 4-wide image's record slots, a leaf-ordered binary image's, or class-major ids
-static int query_map_for(rtow_ctx *c, int kernel, const int32_t **out) {
-  return query_map(c, kernel == RTOW_KERNEL_BVH4 ? 2 : (kernel == RTOW_KERNEL_BVH && c->ds.leaf_direct ? 1 : 0), out);
-}
-
-// What the three queries (rtow_intersect*, rtow_occluded*, rtow_closest_point*) share around their kernels.  QueryKind:
-// what tells them apart on the host.  query_begin: the argument checks after the buffers', the strategy (the render's
-// resolution and residency rules), the launch shape, the stats header.  query_launch: the grid from the kernel's
-// occupancy, the BVH4 spill, the walk fields, and the launch between events on the caller's stream (ordered behind the
-// last upload); with stats, the counters and times.  query_device / query_host: the two entry forms.
-struct QueryKind {
-  size_t in_bytes, out_bytes;                // record sizes (include/rtow.h)
-  unsigned in_align, out_align;              // alignment required of the device buffers
-  const char *count, *in_name, *out_name;    // the words of the error texts
-  bool mapped;                               // results name primitives by insertion index: needs query_map
-  bool point;                                // point walks: resolve_point_kernel, and BRUTE stages no triangle tiles
-  bool brute_tests_all;                      // its STREAM walk tests every primitive uncounted: prim_tests = n * n_prims
-  DevBuf rtow_ctx::*out_buf;                 // the host form's device result buffer (its input goes through q_rays)
-  rtow::QueryLaunchFn *launch[2];            // [0] strict, [1] fast
-  rtow::QueryOccupancyFn *occupancy[2];
-};
-// closest hit
-static const QueryKind kIntersect = {
-    .in_bytes = sizeof(rtow_ray_t), .out_bytes = sizeof(rtow_hit_t), .in_align = 16, .out_align = 8,
-    .count = "n_rays", .in_name = "ray", .out_name = "hit", .mapped = true, .point = false, .brute_tests_all = true,
-    .out_buf = &rtow_ctx::q_hits, .launch = {rtow::launch_query_strict, rtow::launch_query_fast},
-    .occupancy = {rtow::query_occupancy_strict, rtow::query_occupancy_fast}};
-// any hit: the closest-hit query's contract without its hit records (so no query_map: nothing to translate)
-static const QueryKind kOccluded = {
-    .in_bytes = sizeof(rtow_ray_t), .out_bytes = 1, .in_align = 16, .out_align = 1,
-    .count = "n_rays", .in_name = "ray", .out_name = "result", .mapped = false, .point = false, .brute_tests_all = false,
-    .out_buf = &rtow_ctx::q_occ, .launch = {rtow::launch_occlude_strict, rtow::launch_occlude_fast},
-    .occupancy = {rtow::occlude_occupancy_strict, rtow::occlude_occupancy_fast}};
-// closest point: the closest-hit query's contract (arguments, ordering, stats, query_map) with the point walks
-static const QueryKind kClosestPoint = {
-    .in_bytes = sizeof(rtow_point_query_t), .out_bytes = sizeof(rtow_point_hit_t), .in_align = 16, .out_align = 16,
-    .count = "n", .in_name = "query", .out_name = "hit", .mapped = true, .point = true, .brute_tests_all = false,
-    .out_buf = &rtow_ctx::q_hits, .launch = {rtow::launch_pointq_strict, rtow::launch_pointq_fast},
-    .occupancy = {rtow::pointq_occupancy_strict, rtow::pointq_occupancy_fast}};
-
-constexpr size_t kQueryCounters = 4;  // [0] primitive tests, [1] node tests; the radiance query: [2] segments, [3] queue head
-struct QueryRun {
-  int kernel = 0;
-  bool strict = false;
-  LaunchShape shape;
-  int block_cap = 0;  // > 0: at most this many workgroups (the radiance query's test knob)
-};
-// The point query's strategy: AUTO takes the best resident tree (BVH4, else BVH, else BRUTE: it never fails on a resident
-// scene); GRID has no point walk and is answered by the binary BVH; then the render's fallbacks and residency rules.
-static int resolve_point_kernel(rtow_ctx *c, int precision, int requested, int *out) {
-  int kernel = requested;
-  if (kernel == RTOW_KERNEL_REFTREE) return fail(RTOW_EINVAL, "point queries: RTOW_KERNEL_REFTREE has no point walk");
-  if (kernel == RTOW_KERNEL_AUTO)
-    kernel = c->have_bvh4 ? RTOW_KERNEL_BVH4 : (c->built & kNeedBvh) ? RTOW_KERNEL_BVH : RTOW_KERNEL_BRUTE;
-  if (kernel == RTOW_KERNEL_GRID) kernel = RTOW_KERNEL_BVH;
-  return resident_kernel(c, precision, kernel, false, out);
-}
-
-// walk = false (rtow_camera_rays*: a kernel that reads the camera alone): the request is checked but no strategy is
-// resolved — q.kernel stays 0, and a lean upload, which built one strategy's structures only, is as good as a full one
-static int query_begin(rtow_ctx *c, int32_t precision, int32_t kernel_req, rtow_stats_t *stats, QueryRun &q,
-                       bool point = false, bool walk = true) {
-  if (precision == RTOW_F32) return fail(RTOW_EINVAL, "ray queries: RTOW_F32 is not supported (binary64 builds only)");
-  if (precision != RTOW_F64_STRICT && precision != RTOW_F64_FAST) return fail(RTOW_EINVAL, "unknown precision %d", precision);
-  if (kernel_req < RTOW_KERNEL_AUTO || kernel_req > RTOW_KERNEL_REFTREE) return fail(RTOW_EINVAL, "unknown kernel %d", kernel_req);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  int rc;
-  if (!walk) {
-    q.kernel = 0;
-    q.shape.block = kBlock;
-  } else {
-    if ((rc = point ? resolve_point_kernel(c, precision, kernel_req, &q.kernel) : resolve_kernel(c, precision, kernel_req, &q.kernel)))
-      return rc;
-    if ((rc = launch_shape(c, q.kernel, false, q.shape))) return rc;
-  }
-  q.strict = precision == RTOW_F64_STRICT;
-  if (stats) {
-    std::memset(stats, 0, sizeof *stats);
-    stats->kernel_used = q.kernel;
-  }
-  return RTOW_OK;
-}
-
-// occ: workgroups per CU of the query's kernel (<= 0: the occupancy query failed); launch(P, counters, grid): enqueue
-// the kernel on `st`, returning 0 or a hipError_t
-extern "C++" template <class Launch>
-static int query_launch(rtow_ctx *c, const QueryRun &q, int64_t n_rays, int occ, void *hip_stream, rtow_stats_t *stats,
-                        Launch &&launch) {
-  const int kernel = q.kernel;
-  if (occ <= 0) return fail(RTOW_EHIP, "query occupancy failed (kernel %d, %u B of LDS)", kernel, q.shape.lds_bytes);
-  occ = std::min(occ, 8);
-  const int block = q.shape.block;
-  long long grid = (long long)c->num_cus * occ;
-  const long long need_blocks = (n_rays + block - 1) / block;
-  grid = std::max(std::min(grid, need_blocks), 1ll);
-  if (q.block_cap > 0) grid = std::min(grid, (long long)q.block_cap);
-  const unsigned long long n_lanes = (unsigned long long)grid * block;
-  int rc;
-  if ((rc = c->q_counters.ensure(kQueryCounters * sizeof(unsigned long long)))) return rc;
-  if (kernel == RTOW_KERNEL_BVH4) {
-    const int extra = std::max(q.shape.stack_bound - (int)q.shape.scene.b4_stack_k, 0);
-    if ((rc = c->q_spill.ensure(std::max<size_t>((size_t)extra * (size_t)n_lanes * sizeof(uint32_t), 16)))) return rc;
-  }
-  rtow::TraceParams P;
-  std::memset(&P, 0, sizeof P);
-  P.sc = q.shape.scene;
-  P.n_lanes = (uint32_t)n_lanes;
-  P.spill = (uint32_t *)c->q_spill.p;
-  // every walk runs to completion (cap 0xffffffff); the leaf-phase quorum is the render's
-  const bool b4 = kernel == RTOW_KERNEL_BVH4;
-  P.walk_cap = 0xffffffffu;
-  P.walk_max_open = 64u;
-  P.leaf_votes = (uint32_t)(c->knobs.leaf_votes > 0 ? c->knobs.leaf_votes : (b4 ? 28 : 16));
-
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (stats && !c->q_ev[0]) {
-    for (hipEvent_t &e : c->q_ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipHostMalloc((void **)&c->h_qcounters, kQueryCounters * sizeof(unsigned long long), hipHostMallocDefault));
-  }
-  if (st != nullptr) HIPCHK(hipStreamWaitEvent(st, c->upload_ev, 0));  // the scene upload was queued on the null stream
-  if (stats) HIPCHK(hipEventRecord(c->q_ev[0], st));
-  HIPCHK(hipMemsetAsync(c->q_counters.p, 0, kQueryCounters * sizeof(unsigned long long), st));
-  if (stats) HIPCHK(hipEventRecord(c->q_ev[1], st));
-  auto *counters = (unsigned long long *)c->q_counters.p;
-  const int lrc = launch(P, counters, (int)grid);
-  if (lrc != 0) return fail(RTOW_EHIP, "query kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  if (stats) {
-    HIPCHK(hipEventRecord(c->q_ev[2], st));
-    HIPCHK(hipMemcpyAsync(c->h_qcounters, counters, kQueryCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(c->q_ev[3], st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->q_ev[1], c->q_ev[2]));
-    stats->kernel_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, c->q_ev[0], c->q_ev[3]));
-    stats->total_ms = ms;
-    stats->segments = (uint64_t)n_rays;
-    stats->prim_tests = c->h_qcounters[0];
-    stats->node_tests = kernel == RTOW_KERNEL_BRUTE ? 0u : c->h_qcounters[1];
-  }
-  return RTOW_OK;
-}
-
-static int query_device(rtow_ctx *c, const QueryKind &k, int32_t precision, int32_t kernel_req, const void *d_in, int64_t n,
-                        void *d_out, void *hip_stream, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "%s %lld outside [0, 2^31 - 64]", k.count, (long long)n);
-  if (n > 0 && (!d_in || !d_out)) return fail(RTOW_EINVAL, "NULL %s or %s buffer", k.in_name, k.out_name);
-  if (((uintptr_t)d_in & (k.in_align - 1u)) != 0u)
-    return fail(RTOW_EINVAL, "%s buffer must be %u-byte aligned", k.in_name, k.in_align);
-  if (((uintptr_t)d_out & (k.out_align - 1u)) != 0u)
-    return fail(RTOW_EINVAL, "%s buffer must be %u-byte aligned", k.out_name, k.out_align);
-  QueryRun q;
-  int rc;
-  if ((rc = query_begin(c, precision, kernel_req, stats, q, k.point))) return rc;
-  if (n == 0) return RTOW_OK;
-
-  const int kernel = q.kernel;
-  const int32_t *map = nullptr;
-  if (k.mapped && (rc = query_map_for(c, kernel, &map))) return rc;
-  const int block = q.shape.block;
-  const unsigned lds = k.point && kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;
-  const int build = q.strict ? 0 : 1;
-  const int occ = k.occupancy[build](kernel, block, lds, nullptr);
-  rc = query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
-    return k.launch[build](P, d_in, d_out, (uint32_t)n, map, counters, kernel, grid, block, lds, hip_stream);
-  });
-  if (rc == RTOW_OK && stats && k.brute_tests_all && kernel == RTOW_KERNEL_BRUTE)
-    stats->prim_tests = (uint64_t)n * (uint64_t)c->n_prims;
-  return rc;
-}
-
-static int query_host(rtow_ctx *c, const QueryKind &k, int32_t precision, int32_t kernel, const void *in, int64_t n, void *out,
-                      rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "%s %lld outside [0, 2^31 - 64]", k.count, (long long)n);
-  if (n > 0 && (!in || !out)) return fail(RTOW_EINVAL, "NULL %s or %s array", k.in_name, k.out_name);
-  if (n == 0) return query_device(c, k, precision, kernel, nullptr, 0, nullptr, nullptr, stats);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  DevBuf &d_out = c->*k.out_buf;
-  int rc;
-  if ((rc = c->q_rays.ensure((size_t)n * k.in_bytes)) || (rc = d_out.ensure((size_t)n * k.out_bytes))) return rc;
-  HIPCHK(hipMemcpy(c->q_rays.p, in, (size_t)n * k.in_bytes, hipMemcpyHostToDevice));
-  if ((rc = query_device(c, k, precision, kernel, c->q_rays.p, n, d_out.p, nullptr, stats))) return rc;
-  HIPCHK(hipMemcpy(out, d_out.p, (size_t)n * k.out_bytes, hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-
-// The first-k-hits query (rtow_first_hits*, csrc/rtow_first_hits.h): the closest-hit query's checks, strategy, launch
-// shape, ordering, stats and id translation (query_begin / query_launch / query_map) around a kernel that writes max_hits
-// records and one count per ray.  REFTREE is refused (the reference's tree misses hits by design: no multi-hit meaning).
-// BRUTE uses no LDS (its walk reads the class-major arrays) and counts the tests it ran.
-static int first_hits_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_rays, int64_t n,
-                             int32_t max_hits, void *d_hits, void *d_counts, void *hip_stream, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
-  if (max_hits < 1 || max_hits > RTOW_MAX_HITS)
-    return fail(RTOW_EINVAL, "max_hits %d outside [1, %d]", max_hits, RTOW_MAX_HITS);
-  if (n > 0 && (!d_rays || !d_hits)) return fail(RTOW_EINVAL, "NULL ray or hit buffer");
-  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
-  if (((uintptr_t)d_hits & 7u) != 0u) return fail(RTOW_EINVAL, "hit buffer must be 8-byte aligned");
-  if (((uintptr_t)d_counts & 3u) != 0u) return fail(RTOW_EINVAL, "count buffer must be 4-byte aligned");
-  if (kernel_req == RTOW_KERNEL_REFTREE)
-    return fail(RTOW_EINVAL, "first-hits queries: RTOW_KERNEL_REFTREE has no multi-hit meaning");
-  QueryRun q;
-  int rc;
-  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
-  if (n == 0) return RTOW_OK;
-
-  const int kernel = q.kernel;
-  const int32_t *map = nullptr;
-  if ((rc = query_map_for(c, kernel, &map))) return rc;
-  const int block = q.shape.block;
-  const unsigned lds = kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;
-  const int build = q.strict ? 0 : 1;
-  rtow::FirstHitsLaunchFn *const launch[2] = {rtow::launch_first_hits_strict, rtow::launch_first_hits_fast};
-  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::first_hits_occupancy_strict, rtow::first_hits_occupancy_fast};
-  const int occ = occupancy[build](kernel, block, lds, nullptr);
-  return query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
-    return launch[build](P, d_rays, d_hits, (int32_t *)d_counts, (uint32_t)n, max_hits, map, counters, kernel, grid, block,
-                         lds, hip_stream);
-  });
-}
-
-static int first_hits_host(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n,
-                           int32_t max_hits, rtow_hit_t *hits, int32_t *counts, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
-  if (max_hits < 1 || max_hits > RTOW_MAX_HITS)
-    return fail(RTOW_EINVAL, "max_hits %d outside [1, %d]", max_hits, RTOW_MAX_HITS);
-  if (n > 0 && (!rays || !hits)) return fail(RTOW_EINVAL, "NULL ray or hit array");
-  if (n == 0) return first_hits_device(c, precision, kernel, nullptr, 0, max_hits, nullptr, nullptr, nullptr, stats);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  const size_t hit_bytes = (size_t)n * (size_t)max_hits * sizeof(rtow_hit_t);
-  int rc;
-  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_ray_t))) || (rc = c->q_khits.ensure(hit_bytes)) ||
-      (counts && (rc = c->q_kcounts.ensure((size_t)n * sizeof(int32_t)))))
-    return rc;
-  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
-  if ((rc = first_hits_device(c, precision, kernel, c->q_rays.p, n, max_hits, c->q_khits.p, counts ? c->q_kcounts.p : nullptr,
-                              nullptr, stats)))
-    return rc;
-  HIPCHK(hipMemcpy(hits, c->q_khits.p, hit_bytes, hipMemcpyDeviceToHost));
-  if (counts) HIPCHK(hipMemcpy(counts, c->q_kcounts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-
-// The k-nearest query (rtow_nearest*, csrc/rtow_nearest.h): the closest-point query's checks, strategy
-// (resolve_point_kernel), launch shape, ordering, stats and id translation around a kernel that writes k records and one
-// count per point.  k is checked before anything else is looked at.  BRUTE uses no LDS (its walk reads the class-major
-// arrays).
-static int nearest_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const void *d_queries, int64_t n, int32_t k,
-                          void *d_hits, void *d_counts, void *hip_stream, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (k < 1 || k > RTOW_MAX_NEAREST) return fail(RTOW_EINVAL, "k %d outside [1, %d]", k, RTOW_MAX_NEAREST);
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n %lld outside [0, 2^31 - 64]", (long long)n);
-  if (n > 0 && (!d_queries || !d_hits)) return fail(RTOW_EINVAL, "NULL query or hit buffer");
-  if (((uintptr_t)d_queries & 15u) != 0u) return fail(RTOW_EINVAL, "query buffer must be 16-byte aligned");
-  if (((uintptr_t)d_hits & 15u) != 0u) return fail(RTOW_EINVAL, "hit buffer must be 16-byte aligned");
-  if (((uintptr_t)d_counts & 3u) != 0u) return fail(RTOW_EINVAL, "count buffer must be 4-byte aligned");
-  QueryRun q;
-  int rc;
-  if ((rc = query_begin(c, precision, kernel_req, stats, q, true))) return rc;
-  if (n == 0) return RTOW_OK;
-
-  const int kernel = q.kernel;
-  const int32_t *map = nullptr;
-  if ((rc = query_map_for(c, kernel, &map))) return rc;
-  const int block = q.shape.block;
-  const unsigned lds = kernel == RTOW_KERNEL_BRUTE ? 0u : q.shape.lds_bytes;
-  const int build = q.strict ? 0 : 1;
-  rtow::NearestLaunchFn *const launch[2] = {rtow::launch_nearest_strict, rtow::launch_nearest_fast};
-  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::nearest_occupancy_strict, rtow::nearest_occupancy_fast};
-  const int occ = occupancy[build](kernel, block, lds, nullptr);
-  return query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P, unsigned long long *counters, int grid) {
-    return launch[build](P, d_queries, d_hits, (int32_t *)d_counts, (uint32_t)n, k, map, counters, kernel, grid, block, lds,
-                         hip_stream);
-  });
-}
-
-static int nearest_host(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
-                        int32_t k, rtow_point_hit_t *hits, int32_t *counts, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (k < 1 || k > RTOW_MAX_NEAREST) return fail(RTOW_EINVAL, "k %d outside [1, %d]", k, RTOW_MAX_NEAREST);
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n %lld outside [0, 2^31 - 64]", (long long)n);
-  if (n > 0 && (!queries || !hits)) return fail(RTOW_EINVAL, "NULL query or hit array");
-  if (n == 0) return nearest_device(c, precision, kernel, nullptr, 0, k, nullptr, nullptr, nullptr, stats);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  const size_t hit_bytes = (size_t)n * (size_t)k * sizeof(rtow_point_hit_t);
-  int rc;
-  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_point_query_t))) || (rc = c->q_khits.ensure(hit_bytes)) ||
-      (counts && (rc = c->q_kcounts.ensure((size_t)n * sizeof(int32_t)))))
-    return rc;
-  HIPCHK(hipMemcpy(c->q_rays.p, queries, (size_t)n * sizeof(rtow_point_query_t), hipMemcpyHostToDevice));
-  if ((rc = nearest_device(c, precision, kernel, c->q_rays.p, n, k, c->q_khits.p, counts ? c->q_kcounts.p : nullptr, nullptr,
-                           stats)))
-    return rc;
-  HIPCHK(hipMemcpy(hits, c->q_khits.p, hit_bytes, hipMemcpyDeviceToHost));
-  if (counts) HIPCHK(hipMemcpy(counts, c->q_kcounts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-
-// The radiance query (rtow_radiance*, csrc/rtow_radiance.h): the ray queries' strategy, launch shape, ordering and stats
-// (query_begin / query_launch) around a kernel that traces whole paths.  The launch fills what the paths need beyond the
-// walks' fields: the Philox key, the depth and — strict build — a path stack of its own, sized for this launch's lanes.
-static int radiance_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const rtow_radiance_params_t *prm,
-                           const void *d_rays, int64_t n, const void *d_ids, void *d_out, void *hip_stream,
-                           rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (!prm) return fail(RTOW_EINVAL, "params is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
-  if (n > 0 && (!d_rays || !d_out)) return fail(RTOW_EINVAL, "NULL ray or result buffer");
-  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
-  if (((uintptr_t)d_ids & 7u) != 0u) return fail(RTOW_EINVAL, "ids buffer must be 8-byte aligned");
-  if (((uintptr_t)d_out & 7u) != 0u) return fail(RTOW_EINVAL, "result buffer must be 8-byte aligned");
-  if (prm->samples_per_ray < 1) return fail(RTOW_EINVAL, "samples_per_ray %d < 1", prm->samples_per_ray);
-  if (prm->max_child_rays < 0) return fail(RTOW_EINVAL, "max_child_rays %d < 0", prm->max_child_rays);
-  QueryRun q;
-  int rc;
-  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
-  if (n == 0) return RTOW_OK;
-  q.block_cap = c->knobs.radiance_blocks;
-
-  const int kernel = q.kernel;
-  const int block = q.shape.block;
-  const unsigned lds = q.shape.lds_bytes;
-  const int build = q.strict ? 0 : 1;
-  rtow::RadianceLaunchFn *const launch[2] = {rtow::launch_radiance_strict, rtow::launch_radiance_fast};
-  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::radiance_occupancy_strict, rtow::radiance_occupancy_fast};
-  const int occ = occupancy[build](kernel, block, lds, nullptr);
-  int stack_rc = RTOW_OK;
-  rc = query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P0, unsigned long long *counters, int grid) {
-    rtow::TraceParams P = P0;
-    P.seed_lo = (uint32_t)(prm->seed & 0xffffffffu);
-    P.seed_hi = (uint32_t)(prm->seed >> 32);
-    P.max_child_rays = prm->max_child_rays;
-    if (q.strict) {  // [bounce][lane] material indices
-      const size_t words = (size_t)prm->max_child_rays * (size_t)P.n_lanes;
-      if ((stack_rc = c->q_stack.ensure(std::max<size_t>(words * sizeof(uint32_t), 16)))) return (int)hipErrorOutOfMemory;
-      P.stack = (uint32_t *)c->q_stack.p;
-    }
-    return launch[build](P, d_rays, d_ids, d_out, (uint32_t)n, prm->samples_per_ray, prm->sample_first, counters, kernel, grid,
-                         block, lds, hip_stream);
-  });
-  if (stack_rc != RTOW_OK) return stack_rc;
-  if (rc == RTOW_OK && stats) {
-    stats->samples = (uint64_t)n * (uint64_t)prm->samples_per_ray;
-    stats->segments = c->h_qcounters[2];
-  }
-  return rc;
-}
-
-static int radiance_host(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_radiance_params_t *prm,
-                         const rtow_ray_t *rays, int64_t n, const uint32_t *ids, double *out, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
-  if (n > 0 && (!rays || !out)) return fail(RTOW_EINVAL, "NULL ray or result array");
-  if (n == 0) return radiance_device(c, precision, kernel, prm, nullptr, 0, nullptr, nullptr, nullptr, stats);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  int rc;
-  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_ray_t))) || (rc = c->q_rgb.ensure((size_t)n * 24)) ||
-      (ids && (rc = c->q_ids.ensure((size_t)n * 8))))
-    return rc;
-  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
-  if (ids) HIPCHK(hipMemcpy(c->q_ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
-  if ((rc = radiance_device(c, precision, kernel, prm, c->q_rays.p, n, ids ? c->q_ids.p : nullptr, c->q_rgb.p, nullptr, stats)))
-    return rc;
-  HIPCHK(hipMemcpy(out, c->q_rgb.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-
-// The path-step query (rtow_path_step*, csrc/rtow_step.h): the closest-hit query's strategy, launch shape, ordering, stats
-// and id translation (query_begin / query_launch / query_map) around a kernel that traces one segment per ray and
-// scatters it.  BRUTE reports n * n_prims primitive tests, as rtow_intersect does.
-static int step_device(rtow_ctx *c, int32_t precision, int32_t kernel_req, const rtow_step_params_t *prm, const void *d_rays,
-                       int64_t n, const void *d_ids, void *d_next, void *d_atten, void *d_status, void *d_hits,
-                       void *hip_stream, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (!prm) return fail(RTOW_EINVAL, "params is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
-  if (n > 0 && (!d_rays || !d_next || !d_atten || !d_status))
-    return fail(RTOW_EINVAL, "NULL ray, next-ray, attenuation or status buffer");
-  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
-  if (((uintptr_t)d_ids & 7u) != 0u) return fail(RTOW_EINVAL, "ids buffer must be 8-byte aligned");
-  if (((uintptr_t)d_next & 15u) != 0u) return fail(RTOW_EINVAL, "next-ray buffer must be 16-byte aligned");
-  if (((uintptr_t)d_atten & 7u) != 0u) return fail(RTOW_EINVAL, "attenuation buffer must be 8-byte aligned");
-  if (((uintptr_t)d_status & 3u) != 0u) return fail(RTOW_EINVAL, "status buffer must be 4-byte aligned");
-  if (((uintptr_t)d_hits & 7u) != 0u) return fail(RTOW_EINVAL, "hit buffer must be 8-byte aligned");
-  if (prm->bounce < 0) return fail(RTOW_EINVAL, "bounce %d < 0", prm->bounce);
-  QueryRun q;
-  int rc;
-  if ((rc = query_begin(c, precision, kernel_req, stats, q))) return rc;
-  if (n == 0) return RTOW_OK;
-
-  const int kernel = q.kernel;
-  const int32_t *map = nullptr;
-  if (d_hits && (rc = query_map_for(c, kernel, &map))) return rc;
-  const int block = q.shape.block;
-  const unsigned lds = q.shape.lds_bytes;
-  const int build = q.strict ? 0 : 1;
-  rtow::StepLaunchFn *const launch[2] = {rtow::launch_step_strict, rtow::launch_step_fast};
-  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::step_occupancy_strict, rtow::step_occupancy_fast};
-  const int occ = occupancy[build](kernel, block, lds, nullptr);
-  rc = query_launch(c, q, n, occ, hip_stream, stats, [&](const rtow::TraceParams &P0, unsigned long long *counters, int grid) {
-    rtow::TraceParams P = P0;
-    P.seed_lo = (uint32_t)(prm->seed & 0xffffffffu);
-    P.seed_hi = (uint32_t)(prm->seed >> 32);
-    return launch[build](P, d_rays, d_ids, d_next, d_atten, d_status, d_hits, (uint32_t)n, 1u + (uint32_t)prm->bounce,
-                         prm->sample_first, map, counters, kernel, grid, block, lds, hip_stream);
-  });
-  if (rc == RTOW_OK && stats && kernel == RTOW_KERNEL_BRUTE) stats->prim_tests = (uint64_t)n * (uint64_t)c->n_prims;
-  return rc;
-}
-
-// (the rays are stepped in place in q_rays; the attenuations go through the radiance query's q_rgb)
-static int step_host(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_step_params_t *prm, const rtow_ray_t *rays,
-                     int64_t n, const uint32_t *ids, rtow_ray_t *next, double *atten, int32_t *status, rtow_hit_t *hits,
-                     rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  if (n < 0 || n > kMaxQueryRays) return fail(RTOW_EINVAL, "n_rays %lld outside [0, 2^31 - 64]", (long long)n);
-  if (n > 0 && (!rays || !next || !atten || !status))
-    return fail(RTOW_EINVAL, "NULL ray, next-ray, attenuation or status array");
-  if (n == 0)
-    return step_device(c, precision, kernel, prm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stats);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  int rc;
-  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_ray_t))) || (rc = c->q_rgb.ensure((size_t)n * 24)) ||
-      (rc = c->q_status.ensure((size_t)n * sizeof(int32_t))) || (ids && (rc = c->q_ids.ensure((size_t)n * 8))) ||
-      (hits && (rc = c->q_hits.ensure((size_t)n * sizeof(rtow_hit_t)))))
-    return rc;
-  HIPCHK(hipMemcpy(c->q_rays.p, rays, (size_t)n * sizeof(rtow_ray_t), hipMemcpyHostToDevice));
-  if (ids) HIPCHK(hipMemcpy(c->q_ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
-  if ((rc = step_device(c, precision, kernel, prm, c->q_rays.p, n, ids ? c->q_ids.p : nullptr, c->q_rays.p, c->q_rgb.p,
-                        c->q_status.p, hits ? c->q_hits.p : nullptr, nullptr, stats)))
-    return rc;
-  HIPCHK(hipMemcpy(next, c->q_rays.p, (size_t)n * sizeof(rtow_ray_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(atten, c->q_rgb.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(status, c->q_status.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (hits) HIPCHK(hipMemcpy(hits, c->q_hits.p, (size_t)n * sizeof(rtow_hit_t), hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-
-// The camera stage (rtow_camera_rays*, rtow_guides*, csrc/rtow_guides.h): the queries' strategy, launch shape, ordering and
-// stats (query_begin / query_launch) around kernels that generate the render's primaries themselves.  CameraCall: what a
-// render of `cfg` would trace on this rank — its rows and its sample set (level_plan's strict form: the reference's).
-struct CameraCall {
-  int rows = 0;
-  long long npix = 0;         // rows * W
-  uint32_t sample_first = 0;  // stream_first * (spp / nstreams)
-  long long samples = 0;      // (spp / nstreams) * streams of the call
-};
-static int camera_call(const rtow_config_t *cfg, CameraCall &k) {
-  int rc = validate_cfg(cfg);
-  if (rc) return rc;
-  if (cfg->precision == RTOW_F32) return fail(RTOW_EINVAL, "camera rays / guides: RTOW_F32 is not supported (binary64 builds only)");
-  const long long spt = cfg->samples_per_pixel / cfg->nstreams;  // src/render.cpp:174
-  const long long streams_now = cfg->stream_count > 0 ? cfg->stream_count : cfg->nstreams;
-  if (spt * ((long long)cfg->stream_first + streams_now) > 0xffffffffLL) return fail(RTOW_EINVAL, "sample index beyond 32 bits");
-  k.rows = rtow_local_rows(cfg);
-  k.npix = (long long)k.rows * cfg->image_width;
-  k.sample_first = (uint32_t)((long long)cfg->stream_first * spt);
-  k.samples = spt * streams_now;
-  if (k.samples > 0x7fffffffLL) return fail(RTOW_EINVAL, "%lld samples per pixel in one call", k.samples);
-  return RTOW_OK;
-}
-// the camera's share of the launch parameters: what render_levels sets for the new-ray stage
-static void camera_params(const rtow_ctx *c, const rtow_config_t *cfg, const CameraCall &k, rtow::TraceParams &P) {
-  P.cam = (const rtow::DevCamera *)c->cam_dev.p;
-  P.W = cfg->image_width;
-  P.H = cfg->image_height;
-  P.inv_wm1 = 1.0 / (double)(cfg->image_width - 1);
-  P.inv_hm1 = 1.0 / (double)(cfg->image_height - 1);
-  P.rank = cfg->rank;
-  P.nranks = cfg->nranks;
-  P.tile_rows = cfg->tile_rows;
-  P.local_rows = k.rows;
-  P.seed_lo = (uint32_t)cfg->seed;
-  P.seed_hi = (uint32_t)(cfg->seed >> 32);
-}
-
-static int camera_rays_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_rays, void *d_ids, void *hip_stream) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  CameraCall k;
-  int rc;
-  if ((rc = camera_call(cfg, k))) return rc;
-  const long long n = k.npix * k.samples;  // (< 2^62)
-  if (n > kMaxQueryRays) return fail(RTOW_EINVAL, "rows * width * samples = %lld beyond 2^31 - 64", n);
-  if (n > 0 && !d_rays) return fail(RTOW_EINVAL, "NULL ray buffer");
-  if (((uintptr_t)d_rays & 15u) != 0u) return fail(RTOW_EINVAL, "ray buffer must be 16-byte aligned");
-  if (((uintptr_t)d_ids & 7u) != 0u) return fail(RTOW_EINVAL, "ids buffer must be 8-byte aligned");
-  QueryRun q;
-  if ((rc = query_begin(c, cfg->precision, cfg->kernel, nullptr, q, false, false))) return rc;
-  if (n == 0) return RTOW_OK;
-  rtow::CameraRaysLaunchFn *const launch[2] = {rtow::launch_camera_rays_strict, rtow::launch_camera_rays_fast};
-  return query_launch(c, q, n, 8, hip_stream, nullptr, [&](const rtow::TraceParams &P0, unsigned long long *, int grid) {
-    rtow::TraceParams P = P0;
-    camera_params(c, cfg, k, P);
-    return launch[q.strict ? 0 : 1](P, d_rays, d_ids, (uint32_t)n, k.sample_first, (int32_t)k.samples, grid, q.shape.block,
-                                    hip_stream);
-  });
-}
-
-static int camera_rays_host(rtow_ctx *c, const rtow_config_t *cfg, rtow_ray_t *rays, uint32_t *ids) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  CameraCall k;
-  int rc;
-  if ((rc = camera_call(cfg, k))) return rc;
-  const long long n = k.npix * k.samples;  // (< 2^62)
-  if (n > kMaxQueryRays) return fail(RTOW_EINVAL, "rows * width * samples = %lld beyond 2^31 - 64", n);
-  if (n > 0 && !rays) return fail(RTOW_EINVAL, "NULL ray array");
-  if (n == 0) return camera_rays_device(c, cfg, nullptr, nullptr, nullptr);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  if ((rc = c->q_rays.ensure((size_t)n * sizeof(rtow_ray_t))) || (ids && (rc = c->q_ids.ensure((size_t)n * 8)))) return rc;
-  if ((rc = camera_rays_device(c, cfg, c->q_rays.p, ids ? c->q_ids.p : nullptr, nullptr))) return rc;
-  HIPCHK(hipMemcpy(rays, c->q_rays.p, (size_t)n * sizeof(rtow_ray_t), hipMemcpyDeviceToHost));
-  if (ids) HIPCHK(hipMemcpy(ids, c->q_ids.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-
-static int guides_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_guides, void *hip_stream, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  CameraCall k;
-  int rc;
-  if ((rc = camera_call(cfg, k))) return rc;
-  // queue positions: 8 x 8 tiles over the rank's rows, 64 positions each (csrc/rtow_guides.h)
-  const long long tiles = (((long long)cfg->image_width + 7) / 8) * (((long long)k.rows + 7) / 8);
-  if (tiles * 64 > 0xfffffff0LL) return fail(RTOW_EINVAL, "too many pixels (%lld)", k.npix);
-  if (k.npix > 0 && !d_guides) return fail(RTOW_EINVAL, "NULL guide buffer");
-  if (((uintptr_t)d_guides & 15u) != 0u) return fail(RTOW_EINVAL, "guide buffer must be 16-byte aligned");
-  QueryRun q;
-  if ((rc = query_begin(c, cfg->precision, cfg->kernel, stats, q))) return rc;
-  if (stats) stats->local_rows = k.rows;
-  if (k.npix == 0) return RTOW_OK;
-  if (k.samples == 0) {  // fewer samples than streams: zero effective samples (src/render.cpp:174), zero sums
-    HIPCHK(hipMemsetAsync(d_guides, 0, (size_t)k.npix * sizeof(rtow_guide_t), (hipStream_t)hip_stream));
-    if (stats) HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
-    return RTOW_OK;
-  }
-  q.block_cap = c->knobs.guides_blocks;
-
-  const int kernel = q.kernel;
-  const int block = q.shape.block;
-  const unsigned lds = q.shape.lds_bytes;
-  const int build = q.strict ? 0 : 1;
-  rtow::GuidesLaunchFn *const launch[2] = {rtow::launch_guides_strict, rtow::launch_guides_fast};
-  rtow::QueryOccupancyFn *const occupancy[2] = {rtow::guides_occupancy_strict, rtow::guides_occupancy_fast};
-  const int occ = occupancy[build](kernel, block, lds, nullptr);
-  rc = query_launch(c, q, tiles * 64, occ, hip_stream, stats, [&](const rtow::TraceParams &P0, unsigned long long *counters, int grid) {
-    rtow::TraceParams P = P0;
-    camera_params(c, cfg, k, P);
-    return launch[build](P, d_guides, (uint32_t)(tiles * 64), k.sample_first, (int32_t)k.samples, counters, kernel, grid, block,
-                         lds, hip_stream);
-  });
-  if (rc == RTOW_OK && stats) {
-    stats->samples = stats->segments = (uint64_t)k.npix * (uint64_t)k.samples;
-    if (kernel == RTOW_KERNEL_BRUTE) stats->prim_tests = stats->segments * (uint64_t)c->n_prims;  // (its walk tests all, uncounted)
-  }
-  return rc;
-}
-
-static int guides_host(rtow_ctx *c, const rtow_config_t *cfg, rtow_guide_t *guides, rtow_stats_t *stats) {
-  if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
-  CameraCall k;
-  int rc;
-  if ((rc = camera_call(cfg, k))) return rc;
-  if (k.npix > 0 && !guides) return fail(RTOW_EINVAL, "NULL guide array");
-  if (k.npix == 0) return guides_device(c, cfg, nullptr, nullptr, stats);
-  if (!c->have_scene) return fail(RTOW_ENOSCENE, "no scene uploaded");
-  HIPCHK(hipSetDevice(c->device));
-  if ((rc = c->q_guides.ensure((size_t)k.npix * sizeof(rtow_guide_t)))) return rc;
-  if ((rc = guides_device(c, cfg, c->q_guides.p, nullptr, stats))) return rc;
-  HIPCHK(hipMemcpy(guides, c->q_guides.p, (size_t)k.npix * sizeof(rtow_guide_t), hipMemcpyDeviceToHost));
-  return RTOW_OK;
-}
-static_assert(sizeof(rtow_guide_t) == 64, "rtow_guide_t is four 16-byte stores");
-
-int64_t rtow_camera_ray_count(const rtow_config_t *cfg) {
-  CameraCall k;
-  if (int rc = camera_call(cfg, k)) return rc;
-  return (int64_t)(k.npix * k.samples);
-}
-
 // Diagnostic: the 16 device counters of the last launch (work queue, segments, prim
 // tests, node tests, ... region cycle sums of the RTOW_STAMPS build at [8..12]).
 int rtow_debug_counters(rtow_ctx *c, unsigned long long *out48) {
@@ -1814,91 +1110,6 @@ int rtow_render_rgb8(rtow_ctx *c, const rtow_scene_t *scene, const rtow_config_t
 }
 int rtow_render_device_rgb8(rtow_ctx *c, const rtow_config_t *cfg, void *d_rgb8, void *hip_stream, rtow_stats_t *stats) {
   return guarded("rtow_render_device_rgb8", [&] { return impl_render_device_rgb8(c, cfg, d_rgb8, hip_stream, stats); });
-}
-int rtow_intersect_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays, void *d_hits,
-                          void *hip_stream, rtow_stats_t *stats) {
-  return guarded("rtow_intersect_device",
-                 [&] { return query_device(c, kIntersect, precision, kernel, d_rays, n_rays, d_hits, hip_stream, stats); });
-}
-int rtow_intersect(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, rtow_hit_t *hits,
-                   rtow_stats_t *stats) {
-  return guarded("rtow_intersect", [&] { return query_host(c, kIntersect, precision, kernel, rays, n_rays, hits, stats); });
-}
-int rtow_occluded_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays,
-                         void *d_occluded, void *hip_stream, rtow_stats_t *stats) {
-  return guarded("rtow_occluded_device",
-                 [&] { return query_device(c, kOccluded, precision, kernel, d_rays, n_rays, d_occluded, hip_stream, stats); });
-}
-int rtow_occluded(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, uint8_t *occluded,
-                  rtow_stats_t *stats) {
-  return guarded("rtow_occluded", [&] { return query_host(c, kOccluded, precision, kernel, rays, n_rays, occluded, stats); });
-}
-int rtow_closest_point_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_queries, int64_t n,
-                              void *d_hits, void *hip_stream, rtow_stats_t *stats) {
-  return guarded("rtow_closest_point_device",
-                 [&] { return query_device(c, kClosestPoint, precision, kernel, d_queries, n, d_hits, hip_stream, stats); });
-}
-int rtow_closest_point(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n,
-                       rtow_point_hit_t *hits, rtow_stats_t *stats) {
-  return guarded("rtow_closest_point", [&] { return query_host(c, kClosestPoint, precision, kernel, queries, n, hits, stats); });
-}
-int rtow_nearest_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_queries, int64_t n, int32_t k,
-                        void *d_hits, void *d_counts, void *hip_stream, rtow_stats_t *stats) {
-  return guarded("rtow_nearest_device", [&] {
-    return nearest_device(c, precision, kernel, d_queries, n, k, d_hits, d_counts, hip_stream, stats);
-  });
-}
-int rtow_nearest(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_point_query_t *queries, int64_t n, int32_t k,
-                 rtow_point_hit_t *hits, int32_t *counts, rtow_stats_t *stats) {
-  return guarded("rtow_nearest", [&] { return nearest_host(c, precision, kernel, queries, n, k, hits, counts, stats); });
-}
-int rtow_first_hits_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_rays, int64_t n_rays,
-                           int32_t max_hits, void *d_hits, void *d_counts, void *hip_stream, rtow_stats_t *stats) {
-  return guarded("rtow_first_hits_device", [&] {
-    return first_hits_device(c, precision, kernel, d_rays, n_rays, max_hits, d_hits, d_counts, hip_stream, stats);
-  });
-}
-int rtow_first_hits(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ray_t *rays, int64_t n_rays, int32_t max_hits,
-                    rtow_hit_t *hits, int32_t *counts, rtow_stats_t *stats) {
-  return guarded("rtow_first_hits",
-                 [&] { return first_hits_host(c, precision, kernel, rays, n_rays, max_hits, hits, counts, stats); });
-}
-int rtow_radiance_device(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params,
-                         const void *d_rays, int64_t n_rays, const void *d_ids, void *d_rgb_sums, void *hip_stream,
-                         rtow_stats_t *stats) {
-  return guarded("rtow_radiance_device", [&] {
-    return radiance_device(c, precision, kernel, params, d_rays, n_rays, d_ids, d_rgb_sums, hip_stream, stats);
-  });
-}
-int rtow_path_step_device(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_step_params_t *params, const void *d_rays,
-                          int64_t n_rays, const void *d_ids, void *d_next, void *d_atten, void *d_status, void *d_hits,
-                          void *hip_stream, rtow_stats_t *stats) {
-  return guarded("rtow_path_step_device", [&] {
-    return step_device(c, precision, kernel, params, d_rays, n_rays, d_ids, d_next, d_atten, d_status, d_hits, hip_stream, stats);
-  });
-}
-int rtow_path_step(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_step_params_t *params, const rtow_ray_t *rays,
-                   int64_t n_rays, const uint32_t *ids, rtow_ray_t *next, double *atten, int32_t *status, rtow_hit_t *hits,
-                   rtow_stats_t *stats) {
-  return guarded("rtow_path_step", [&] {
-    return step_host(c, precision, kernel, params, rays, n_rays, ids, next, atten, status, hits, stats);
-  });
-}
-int rtow_radiance(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_radiance_params_t *params, const rtow_ray_t *rays,
-                  int64_t n_rays, const uint32_t *ids, double *rgb_sums, rtow_stats_t *stats) {
-  return guarded("rtow_radiance", [&] { return radiance_host(c, precision, kernel, params, rays, n_rays, ids, rgb_sums, stats); });
-}
-int rtow_camera_rays_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_rays, void *d_ids, void *hip_stream) {
-  return guarded("rtow_camera_rays_device", [&] { return camera_rays_device(c, cfg, d_rays, d_ids, hip_stream); });
-}
-int rtow_camera_rays(rtow_ctx *c, const rtow_config_t *cfg, rtow_ray_t *rays, uint32_t *ids) {
-  return guarded("rtow_camera_rays", [&] { return camera_rays_host(c, cfg, rays, ids); });
-}
-int rtow_guides_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_guides, void *hip_stream, rtow_stats_t *stats) {
-  return guarded("rtow_guides_device", [&] { return guides_device(c, cfg, d_guides, hip_stream, stats); });
-}
-int rtow_guides(rtow_ctx *c, const rtow_config_t *cfg, rtow_guide_t *guides, rtow_stats_t *stats) {
-  return guarded("rtow_guides", [&] { return guides_host(c, cfg, guides, stats); });
 }
 int rtow_scene_refit(rtow_ctx *c, const rtow_scene_t *s) {
   return guarded("rtow_scene_refit", [&] { return impl_scene_refit(c, s); });

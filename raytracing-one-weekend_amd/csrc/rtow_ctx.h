@@ -1,6 +1,7 @@
-// rtow_ctx.h — the context behind include/rtow.h, for the two host translation units of the C ABI: rtow_scene.cpp
-// (what makes a scene resident: upload, refit, the diagnostics that read the images back) and rtow_capi.cpp (everything
-// that renders or queries the resident scene).  Host code only: no .hip file includes this.
+// rtow_ctx.h — the context behind include/rtow.h, for the three host translation units of the C ABI: rtow_scene.cpp
+// (what makes a scene resident: upload, refit, the diagnostics that read the images back), rtow_capi.cpp (the context
+// itself and everything that renders the resident scene) and rtow_queries.cpp (every query over it).  Host code only: no
+// .hip file includes this.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,8 +39,24 @@ using rtow::fail;
       return fail(RTOW_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
+// No C++ exception crosses the C ABI (include/rtow.h): the entry points that allocate or start threads run
+// their bodies through this.
+template <class F>
+int guarded(const char *what, F &&f) noexcept {
+  try {
+    return f();
+  } catch (const std::bad_alloc &) {
+    return fail(RTOW_ENOMEM, "%s: out of host memory", what);
+  } catch (const std::exception &e) {
+    return fail(RTOW_EINVAL, "%s: %s", what, e.what());
+  } catch (...) {
+    return fail(RTOW_EINVAL, "%s: unknown C++ exception", what);
+  }
+}
+
 constexpr unsigned kLdsLimit = 160u * 1024u;
 constexpr int kEventRing = 256;
+constexpr int kBlock = 256;  // STREAM kernel workgroup
 
 namespace rtow {
 
@@ -314,7 +331,17 @@ struct rtow_ctx {
 // (round 5: 6, was 8 — suzanne's host tree walks at the same rate with 8, 7 and 6 entries per lane in LDS, and two more
 // entry levels are 8 KB = 64 nodes of room for a mesh near the limit: the device-built suzanne tree, 276 nodes against
 // the host's 261, is staged whole with 7)
-static uint32_t bvh4_min_stack(const rtow_ctx *c) { return c->knobs.bvh4_stack_k > 0 ? (uint32_t)c->knobs.bvh4_stack_k : 6u; }
+inline uint32_t bvh4_min_stack(const rtow_ctx *c) { return c->knobs.bvh4_stack_k > 0 ? (uint32_t)c->knobs.bvh4_stack_k : 6u; }
+
+// Launch shape of a strategy on the resident scene (shared by the render and the queries): workgroup size, LDS
+// bytes and the DevScene fields that go with them (STREAM tiles; BVH4: what is staged, the stack's place and depth).
+struct LaunchShape {
+  rtow::DevScene scene;
+  int block = 0;
+  unsigned lds_bytes = 0;
+  int stack_bound = 0;  // BVH4: traversal stack entries a lane may need (3 x depth + 1)
+  bool image_kernel = false;
+};
 
 namespace rtow {
 // the device builders' scratch, kept across uploads (csrc/rtow_build.hip, rtow_build_grid.hip): freed with the context
@@ -328,7 +355,20 @@ int upload_for(rtow_ctx *c, const rtow_scene_t *scene, const rtow_config_t *cfg)
 int impl_scene_refit(rtow_ctx *c, const rtow_scene_t *s);
 // Record slot of a leaf-ordered image -> class-order triangle index (which: 1 the host-built mesh BVH image, 2 the 4-wide image)
 int match_slots(rtow_ctx *c, int which, std::vector<int32_t> &slot2tri);
+// ---- rtow_capi.cpp, for rtow_queries.cpp ------------------------------------------------------------------------------
+int validate_cfg(const rtow_config_t *cfg);
+// The strategy a request resolves to, with the render's fallbacks and residency rules (shared by the render and the
+// ray queries); the first RTOW_KERNEL_REFTREE request builds the reference's tree.
+int resolve_kernel(rtow_ctx *c, int precision, int requested, int *out);
+// The fallbacks and residency rules of a chosen strategy.  stream_records: BRUTE reads the STREAM kernel's triangle
+// records (the render and the ray queries; the point queries read the class records every upload keeps).
+int resident_kernel(rtow_ctx *c, int precision, int kernel, bool stream_records, int *out);
+int launch_shape(rtow_ctx *c, int kernel, bool f32, LaunchShape &s);
 }  // namespace rtow
+using rtow::launch_shape;
+using rtow::resident_kernel;
+using rtow::resolve_kernel;
+using rtow::validate_cfg;
 using rtow::impl_scene_refit;
 using rtow::impl_scene_upload;
 using rtow::match_slots;

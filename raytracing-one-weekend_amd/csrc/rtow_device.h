@@ -185,6 +185,29 @@ struct ReduceParams {
   double spp;
 };
 
+// What a query launcher takes beside TraceParams: the union of the query families' buffers and scalars.  Every family
+// exports `int launch_<family>_<build>(const TraceParams &, const QueryArgs &, int kernel, int grid, int block, unsigned
+// lds_bytes, void *stream)` (0 or a hipError_t), copies the fields its kernel's *Params has and ignores the rest.
+struct QueryArgs {
+  const void *in = nullptr;   // rays or point queries
+  void *ids = nullptr;        // optional sample ids: read by the radiance and path-step queries, written by camera rays
+  void *hits = nullptr;       // hit records: n, or n * k
+  void *next = nullptr, *atten = nullptr, *status = nullptr;  // path step: scattered rays, attenuations, status words
+  void *counts = nullptr;     // optional: entries written per query (first hits, k nearest)
+  void *result = nullptr;     // occlusion bytes, radiance sums, guide records, camera rays
+  uint32_t n = 0;             // queries (the guides: queue positions)
+  int32_t k = 0;              // entries kept per query (max_hits, k)
+  uint32_t request = 0;       // path step: 1 + bounce
+  uint32_t sample_first = 0;  // offset of every ray's or pixel's first sample index
+  int32_t samples = 0;        // samples per ray or pixel
+  const int32_t *map = nullptr;            // walk's primitive id -> insertion index
+  unsigned long long *counters = nullptr;  // [0] primitive tests, [1] node tests, [2] segments, [3] queue head
+};
+
+// name ## RTOW_SUFFIX, for the kernels and launchers of a unit that is compiled once per arithmetic mode
+#define RTOW_CAT2(a, b) a##b
+#define RTOW_CAT(a, b) RTOW_CAT2(a, b)
+
 // launchers, one pair per arithmetic mode (separate translation units compiled
 // with -ffp-contract=off / -ffp-contract=fast)
 // `lds_bytes` > 0 selects the variant that stages the scene blob in LDS

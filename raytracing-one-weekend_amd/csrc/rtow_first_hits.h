@@ -34,8 +34,6 @@
 #ifndef RTOW_SUFFIX
 #error "define RTOW_SUFFIX"
 #endif
-#define RTOW_FCAT2(a, b) a##b
-#define RTOW_FCAT(a, b) RTOW_FCAT2(a, b)
 
 namespace rtow {
 namespace {
@@ -201,7 +199,7 @@ __device__ __forceinline__ void first_hits_stream(const DevScene &sc, V3d o, V3d
 // KERNEL: 1 = STREAM, 2 = BVH, 3 = GRID, 4 = BVH4; LDS: the scene image is staged in LDS (stage_scene)
 template <int KERNEL, bool LDS>
 __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
-    RTOW_FCAT(rtow_first_hits_, RTOW_SUFFIX)(const FirstHitsParams Q) {
+    RTOW_CAT(rtow_first_hits_, RTOW_SUFFIX)(const FirstHitsParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
   const unsigned lane = lane_id();
@@ -271,7 +269,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 
 template <int K, bool L>
 static KernelVariant<FirstHitsParams> first_hits_kernel(unsigned lds_bytes) {
-  return kernel_variant<RTOW_FCAT(rtow_first_hits_, RTOW_SUFFIX)<K, L>, FirstHitsParams>(lds_bytes);
+  return kernel_variant<RTOW_CAT(rtow_first_hits_, RTOW_SUFFIX)<K, L>, FirstHitsParams>(lds_bytes);
 }
 
 // kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4.  `lds_bytes` > 0 selects the variant that stages the image in LDS (2, 3); for
@@ -286,26 +284,23 @@ static KernelVariant<FirstHitsParams> first_hits_variant(int kernel, unsigned ld
   }
 }
 
-int RTOW_FCAT(launch_first_hits_, RTOW_SUFFIX)(const TraceParams &p, const void *rays, void *hits, int32_t *counts,
-                                               uint32_t n, int32_t max_hits, const int32_t *map,
-                                               unsigned long long *counters, int kernel, int grid, int block,
-                                               unsigned lds_bytes, void *stream) {
+int RTOW_CAT(launch_first_hits_, RTOW_SUFFIX)(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block,
+                                              unsigned lds_bytes, void *stream) {
   FirstHitsParams q;
   q.P = p;
-  q.rays = (const unsigned char *)rays;
-  q.hits = (unsigned char *)hits;
-  q.counts = counts;
-  q.n = n;
-  q.max_hits = max_hits;
-  q.map = map;
-  q.counters = counters;
-  const KernelVariant<FirstHitsParams> v = first_hits_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
-  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
+  q.rays = (const unsigned char *)a.in;
+  q.hits = (unsigned char *)a.hits;
+  q.counts = (int32_t *)a.counts;
+  q.n = a.n;
+  q.max_hits = a.k;
+  q.map = a.map;
+  q.counters = a.counters;
+  return launch_variant(first_hits_variant(kernel, lds_bytes, p.sc.b4_half == 0u), q, grid, block, stream);
 }
 
 // Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h).  Both 4-wide variants have the same
 // launch bounds; the full-LDS one stands for both.
-int RTOW_FCAT(first_hits_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+int RTOW_CAT(first_hits_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
   const KernelVariant<FirstHitsParams> v = first_hits_variant(kernel, lds_bytes, true);
   return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }

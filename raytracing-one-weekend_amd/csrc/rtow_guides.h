@@ -47,8 +47,6 @@
 #ifndef RTOW_SUFFIX
 #error "define RTOW_SUFFIX"
 #endif
-#define RTOW_GCAT2(a, b) a##b
-#define RTOW_GCAT(a, b) RTOW_GCAT2(a, b)
 
 namespace rtow {
 namespace {
@@ -120,7 +118,7 @@ __device__ __forceinline__ void camera_ray(const TraceParams &P, const Rng &g, u
 }
 
 // ---- the primaries ------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) RTOW_GCAT(rtow_camera_rays_, RTOW_SUFFIX)(const GuideParams Q) {
+__global__ void __launch_bounds__(256) RTOW_CAT(rtow_camera_rays_, RTOW_SUFFIX)(const GuideParams Q) {
   const TraceParams &P = Q.P;
   const uint32_t stride = gridDim.x * blockDim.x;
   const uint32_t S = (uint32_t)Q.samples, W = (uint32_t)P.W;
@@ -195,7 +193,7 @@ __device__ __forceinline__ void add_rounded(double &acc, double v) {
 // LDS (2 and 3; for 4: the whole image, else the top of its tree — the traversal stack is in LDS either way)
 template <int KERNEL, bool LDS>
 __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
-    RTOW_GCAT(rtow_guides_, RTOW_SUFFIX)(const GuideParams Q) {
+    RTOW_CAT(rtow_guides_, RTOW_SUFFIX)(const GuideParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
   const uint32_t k0 = P.seed_lo, k1 = P.seed_hi;
@@ -398,7 +396,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 // kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE (strict build): the instantiations of rtow_query.h
 template <int K, bool L>
 static KernelVariant<GuideParams> guides_kernel(unsigned lds_bytes) {
-  return kernel_variant<RTOW_GCAT(rtow_guides_, RTOW_SUFFIX)<K, L>, GuideParams>(lds_bytes);
+  return kernel_variant<RTOW_CAT(rtow_guides_, RTOW_SUFFIX)<K, L>, GuideParams>(lds_bytes);
 }
 
 static KernelVariant<GuideParams> guides_variant(int kernel, unsigned lds_bytes, bool b4_full) {
@@ -414,15 +412,15 @@ static KernelVariant<GuideParams> guides_variant(int kernel, unsigned lds_bytes,
   }
 }
 
-static GuideParams guide_params(const TraceParams &p, void *out, void *ids, uint32_t n, uint32_t sample_first,
-                                int32_t samples, unsigned long long *counters) {
+// a.result: the guide records or the rays; a.ids: the camera rays' optional sample ids
+static GuideParams guide_params(const TraceParams &p, const QueryArgs &a, void *ids, unsigned long long *counters) {
   GuideParams q;
   q.P = p;
-  q.out = (unsigned char *)out;
+  q.out = (unsigned char *)a.result;
   q.ids = (uint32_t *)ids;
-  q.n = n;
-  q.sample_first = sample_first;
-  q.samples = samples;
+  q.n = a.n;
+  q.sample_first = a.sample_first;
+  q.samples = a.samples;
   q.tiles_x = ((uint32_t)p.W + 7u) / 8u;
   q.counters = counters;
   return q;
@@ -430,25 +428,24 @@ static GuideParams guide_params(const TraceParams &p, void *out, void *ids, uint
 
 // p: the scene, the camera, W / H and their reciprocals, the rank's rows, seed_lo / seed_hi and the walk fields;
 // n: queue positions = tiles of the rank's rows * 64
-int RTOW_GCAT(launch_guides_, RTOW_SUFFIX)(const TraceParams &p, void *out, uint32_t n, uint32_t sample_first,
-                                           int32_t samples, unsigned long long *counters, int kernel, int grid, int block,
-                                           unsigned lds_bytes, void *stream) {
-  const GuideParams q = guide_params(p, out, nullptr, n, sample_first, samples, counters);
-  const KernelVariant<GuideParams> v = guides_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
-  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
+int RTOW_CAT(launch_guides_, RTOW_SUFFIX)(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block,
+                                          unsigned lds_bytes, void *stream) {
+  const GuideParams q = guide_params(p, a, nullptr, a.counters);
+  return launch_variant(guides_variant(kernel, lds_bytes, p.sc.b4_half == 0u), q, grid, block, stream);
 }
 
 // Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h), as query_occupancy_*.
-int RTOW_GCAT(guides_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+int RTOW_CAT(guides_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
   const KernelVariant<GuideParams> v = guides_variant(kernel, lds_bytes, true);
   return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }
 
 // p: the camera, W / H and their reciprocals, the rank's rows, seed_lo / seed_hi; n = local_rows * W * samples rays
-int RTOW_GCAT(launch_camera_rays_, RTOW_SUFFIX)(const TraceParams &p, void *rays, void *ids, uint32_t n,
-                                                uint32_t sample_first, int32_t samples, int grid, int block, void *stream) {
-  const GuideParams q = guide_params(p, rays, ids, n, sample_first, samples, nullptr);
-  return launch_kernel<RTOW_GCAT(rtow_camera_rays_, RTOW_SUFFIX), GuideParams>(q, grid, block, 0u, (hipStream_t)stream);
+// (one kernel that walks nothing: `kernel`, `lds_bytes` and the counters of the common signature are not used)
+int RTOW_CAT(launch_camera_rays_, RTOW_SUFFIX)(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block,
+                                               unsigned lds_bytes, void *stream) {
+  const GuideParams q = guide_params(p, a, a.ids, nullptr);
+  return launch_kernel<RTOW_CAT(rtow_camera_rays_, RTOW_SUFFIX), GuideParams>(q, grid, block, 0u, (hipStream_t)stream);
 }
 
 }  // namespace rtow

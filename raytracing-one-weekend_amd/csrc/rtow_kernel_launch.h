@@ -1,7 +1,7 @@
 // rtow_kernel_launch.h — the host side of the kernel frame (rtow_kernel_frame.h): how one instantiation of a render or
 // query kernel is launched, and how many of its workgroups stay resident per CU.  Included inside `namespace rtow {`,
-// after the kernels' anonymous namespace, by rtow_trace_body.h, rtow_query.h, rtow_occlude.h, rtow_first_hits.h,
-// rtow_pointq.h, rtow_radiance.h and rtow_guides.h.
+// after the kernels' anonymous namespace, by rtow_trace_body.h and by every query family's header (rtow_query.h,
+// rtow_occlude.h, rtow_pointq.h, rtow_first_hits.h, rtow_nearest.h, rtow_radiance.h, rtow_step.h, rtow_guides.h).
 #pragma once
 
 // The kernels address the dynamic LDS block from 0 (lds_read / lds_write, rtow_trace_math.h): an instantiation that had
@@ -39,6 +39,12 @@ struct KernelVariant {
 template <auto Kernel, class Params>
 static KernelVariant<Params> kernel_variant(unsigned lds_bytes) {
   return {reinterpret_cast<const void *>(Kernel), &launch_kernel<Kernel, Params>, lds_bytes};
+}
+
+// The end of every launcher: launches `v` as its family's `switch (kernel)` picked it, or fails where it picked none.
+template <class Params>
+static int launch_variant(const KernelVariant<Params> &v, const Params &p, int grid, int block, void *stream) {
+  return v.fn ? v.launch(p, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
 }
 
 // Workgroups per CU that stay resident, or -1: min over the register file (512 VGPRs per SIMD lane, allocated in

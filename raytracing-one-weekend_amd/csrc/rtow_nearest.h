@@ -31,8 +31,6 @@
 #ifndef RTOW_SUFFIX
 #error "define RTOW_SUFFIX"
 #endif
-#define RTOW_NCAT2(a, b) a##b
-#define RTOW_NCAT(a, b) RTOW_NCAT2(a, b)
 
 namespace rtow {
 namespace {
@@ -79,7 +77,7 @@ struct NearestSink {
 
 // KERNEL: 1 = BRUTE, 2 = BVH, 4 = BVH4; LDS: the scene image is staged in LDS (stage_scene, rtow_kernel_frame.h)
 template <int KERNEL, bool LDS>
-__global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_NCAT(rtow_nearest_, RTOW_SUFFIX)(const NearestParams Q) {
+__global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_CAT(rtow_nearest_, RTOW_SUFFIX)(const NearestParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
   const unsigned lane = lane_id();
@@ -146,7 +144,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_NCAT(rtow_neare
 
 template <int K, bool L>
 static KernelVariant<NearestParams> nearest_kernel(unsigned lds_bytes) {
-  return kernel_variant<RTOW_NCAT(rtow_nearest_, RTOW_SUFFIX)<K, L>, NearestParams>(lds_bytes);
+  return kernel_variant<RTOW_CAT(rtow_nearest_, RTOW_SUFFIX)<K, L>, NearestParams>(lds_bytes);
 }
 
 // kernel: 1 BRUTE, 2 BVH, 4 BVH4.  `lds_bytes` > 0 selects the BVH variant that stages the image in LDS; for 4 the image
@@ -160,25 +158,23 @@ static KernelVariant<NearestParams> nearest_variant(int kernel, unsigned lds_byt
   }
 }
 
-int RTOW_NCAT(launch_nearest_, RTOW_SUFFIX)(const TraceParams &p, const void *queries, void *hits, int32_t *counts,
-                                            uint32_t n, int32_t k, const int32_t *map, unsigned long long *counters,
-                                            int kernel, int grid, int block, unsigned lds_bytes, void *stream) {
+int RTOW_CAT(launch_nearest_, RTOW_SUFFIX)(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block,
+                                           unsigned lds_bytes, void *stream) {
   NearestParams q;
   q.P = p;
-  q.queries = (const unsigned char *)queries;
-  q.hits = (unsigned char *)hits;
-  q.counts = counts;
-  q.n = n;
-  q.k = k;
-  q.map = map;
-  q.counters = counters;
-  const KernelVariant<NearestParams> v = nearest_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
-  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
+  q.queries = (const unsigned char *)a.in;
+  q.hits = (unsigned char *)a.hits;
+  q.counts = (int32_t *)a.counts;
+  q.n = a.n;
+  q.k = a.k;
+  q.map = a.map;
+  q.counters = a.counters;
+  return launch_variant(nearest_variant(kernel, lds_bytes, p.sc.b4_half == 0u), q, grid, block, stream);
 }
 
 // Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h).  Both 4-wide variants have the same
 // launch bounds; the full-LDS one stands for both.
-int RTOW_NCAT(nearest_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+int RTOW_CAT(nearest_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
   const KernelVariant<NearestParams> v = nearest_variant(kernel, lds_bytes, true);
   return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }

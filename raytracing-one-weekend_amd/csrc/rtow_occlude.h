@@ -19,8 +19,6 @@
 #ifndef RTOW_SUFFIX
 #error "define RTOW_SUFFIX"
 #endif
-#define RTOW_OCAT2(a, b) a##b
-#define RTOW_OCAT(a, b) RTOW_OCAT2(a, b)
 
 namespace rtow {
 namespace {
@@ -263,7 +261,7 @@ __device__ __forceinline__ bool any_hit_stream(const DevScene &sc, V3d o, V3d d,
 // LDS (stage_scene, rtow_kernel_frame.h)
 template <int KERNEL, bool LDS>
 __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
-    RTOW_OCAT(rtow_occlude_, RTOW_SUFFIX)(const OccludeParams Q) {
+    RTOW_CAT(rtow_occlude_, RTOW_SUFFIX)(const OccludeParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
   const unsigned lane = lane_id();
@@ -317,7 +315,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 
 template <int K, bool L>
 static KernelVariant<OccludeParams> occlude_kernel(unsigned lds_bytes) {
-  return kernel_variant<RTOW_OCAT(rtow_occlude_, RTOW_SUFFIX)<K, L>, OccludeParams>(lds_bytes);
+  return kernel_variant<RTOW_CAT(rtow_occlude_, RTOW_SUFFIX)<K, L>, OccludeParams>(lds_bytes);
 }
 
 // kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE (strict build).  `lds_bytes` > 0 selects the variant that stages
@@ -335,23 +333,20 @@ static KernelVariant<OccludeParams> occlude_variant(int kernel, unsigned lds_byt
   }
 }
 
-// (`map`: the query launchers' common signature; an occlusion result names no primitive)
-int RTOW_OCAT(launch_occlude_, RTOW_SUFFIX)(const TraceParams &p, const void *rays, void *occluded, uint32_t n,
-                                            const int32_t *map, unsigned long long *counters, int kernel, int grid,
-                                            int block, unsigned lds_bytes, void *stream) {
+int RTOW_CAT(launch_occlude_, RTOW_SUFFIX)(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block,
+                                           unsigned lds_bytes, void *stream) {
   OccludeParams q;
   q.P = p;
-  q.rays = (const unsigned char *)rays;
-  q.occluded = (unsigned char *)occluded;
-  q.n = n;
-  q.counters = counters;
-  const KernelVariant<OccludeParams> v = occlude_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
-  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
+  q.rays = (const unsigned char *)a.in;
+  q.occluded = (unsigned char *)a.result;
+  q.n = a.n;
+  q.counters = a.counters;
+  return launch_variant(occlude_variant(kernel, lds_bytes, p.sc.b4_half == 0u), q, grid, block, stream);
 }
 
 // Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h).  Both 4-wide variants have the same
 // launch bounds; the full-LDS one stands for both.
-int RTOW_OCAT(occlude_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+int RTOW_CAT(occlude_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
   const KernelVariant<OccludeParams> v = occlude_variant(kernel, lds_bytes, true);
   return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }

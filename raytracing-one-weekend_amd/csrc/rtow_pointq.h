@@ -25,8 +25,6 @@
 #ifndef RTOW_SUFFIX
 #error "define RTOW_SUFFIX"
 #endif
-#define RTOW_PCAT2(a, b) a##b
-#define RTOW_PCAT(a, b) RTOW_PCAT2(a, b)
 
 namespace rtow {
 namespace {
@@ -63,7 +61,7 @@ struct PBest {
 
 // KERNEL: 1 = BRUTE, 2 = BVH, 4 = BVH4; LDS: the scene image is staged in LDS (stage_scene, rtow_kernel_frame.h)
 template <int KERNEL, bool LDS>
-__global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_PCAT(rtow_pointq_, RTOW_SUFFIX)(const PointParams Q) {
+__global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_CAT(rtow_pointq_, RTOW_SUFFIX)(const PointParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
   const unsigned lane = lane_id();
@@ -119,7 +117,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 ? 1024 : 256) RTOW_PCAT(rtow_point
 
 template <int K, bool L>
 static KernelVariant<PointParams> pointq_kernel(unsigned lds_bytes) {
-  return kernel_variant<RTOW_PCAT(rtow_pointq_, RTOW_SUFFIX)<K, L>, PointParams>(lds_bytes);
+  return kernel_variant<RTOW_CAT(rtow_pointq_, RTOW_SUFFIX)<K, L>, PointParams>(lds_bytes);
 }
 
 // kernel: 1 BRUTE, 2 BVH, 4 BVH4.  `lds_bytes` > 0 selects the BVH variant that stages the image in LDS; for 4 the image
@@ -133,23 +131,15 @@ static KernelVariant<PointParams> pointq_variant(int kernel, unsigned lds_bytes,
   }
 }
 
-int RTOW_PCAT(launch_pointq_, RTOW_SUFFIX)(const TraceParams &p, const void *queries, void *hits, uint32_t n,
-                                           const int32_t *map, unsigned long long *counters, int kernel, int grid,
-                                           int block, unsigned lds_bytes, void *stream) {
-  PointParams q;
-  q.P = p;
-  q.queries = (const unsigned char *)queries;
-  q.hits = (unsigned char *)hits;
-  q.n = n;
-  q.map = map;
-  q.counters = counters;
-  const KernelVariant<PointParams> v = pointq_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
-  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
+int RTOW_CAT(launch_pointq_, RTOW_SUFFIX)(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block,
+                                          unsigned lds_bytes, void *stream) {
+  const PointParams q = {p, (const unsigned char *)a.in, (unsigned char *)a.hits, a.n, a.map, a.counters};
+  return launch_variant(pointq_variant(kernel, lds_bytes, p.sc.b4_half == 0u), q, grid, block, stream);
 }
 
 // Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h).  Both 4-wide variants have the same
 // launch bounds; the full-LDS one stands for both.
-int RTOW_PCAT(pointq_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+int RTOW_CAT(pointq_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
   const KernelVariant<PointParams> v = pointq_variant(kernel, lds_bytes, true);
   return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }

@@ -17,7 +17,7 @@
 // The scene image is staged in LDS per workgroup once, exactly as the trace kernel stages it for the same strategy.
 //
 // Walk-order primitive ids -> the caller's insertion order: `map` (built by the host on first use after an upload,
-// rtow_capi.cpp).  The STREAM, GRID and REFTREE walks and a device-built BVH return class-major ids; the 4-wide image and
+// rtow_queries.cpp).  The STREAM, GRID and REFTREE walks and a device-built BVH return class-major ids; the 4-wide image and
 // a host-built mesh BVH hold their triangle records in leaf order and return record slots.  The kind follows from the
 // class-major ranges either way (a leaf-ordered image is a triangle mesh).
 
@@ -29,8 +29,6 @@
 #ifndef RTOW_SUFFIX
 #error "define RTOW_SUFFIX"
 #endif
-#define RTOW_QCAT2(a, b) a##b
-#define RTOW_QCAT(a, b) RTOW_QCAT2(a, b)
 
 namespace rtow {
 namespace {
@@ -71,7 +69,7 @@ __device__ __forceinline__ double plus_zero(double v) {
 // LDS (2 and 3; for 4: the whole image, else the top of its tree — the traversal stack is in LDS either way)
 template <int KERNEL, bool LDS>
 __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
-    RTOW_QCAT(rtow_query_, RTOW_SUFFIX)(const QueryParams Q) {
+    RTOW_CAT(rtow_query_, RTOW_SUFFIX)(const QueryParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
   const unsigned lane = lane_id();
@@ -147,7 +145,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 // the image in LDS (2, 3); for 4 the image staged whole (b4_half == 0) selects the full-LDS variant, as in the render.
 template <int K, bool L>
 static KernelVariant<QueryParams> query_kernel(unsigned lds_bytes) {
-  return kernel_variant<RTOW_QCAT(rtow_query_, RTOW_SUFFIX)<K, L>, QueryParams>(lds_bytes);
+  return kernel_variant<RTOW_CAT(rtow_query_, RTOW_SUFFIX)<K, L>, QueryParams>(lds_bytes);
 }
 
 static KernelVariant<QueryParams> query_variant(int kernel, unsigned lds_bytes, bool b4_full) {
@@ -163,23 +161,15 @@ static KernelVariant<QueryParams> query_variant(int kernel, unsigned lds_bytes, 
   }
 }
 
-int RTOW_QCAT(launch_query_, RTOW_SUFFIX)(const TraceParams &p, const void *rays, void *hits, uint32_t n,
-                                          const int32_t *map, unsigned long long *counters, int kernel, int grid,
-                                          int block, unsigned lds_bytes, void *stream) {
-  QueryParams q;
-  q.P = p;
-  q.rays = (const unsigned char *)rays;
-  q.hits = (unsigned char *)hits;
-  q.n = n;
-  q.map = map;
-  q.counters = counters;
-  const KernelVariant<QueryParams> v = query_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
-  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
+int RTOW_CAT(launch_query_, RTOW_SUFFIX)(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block,
+                                         unsigned lds_bytes, void *stream) {
+  const QueryParams q = {p, (const unsigned char *)a.in, (unsigned char *)a.hits, a.n, a.map, a.counters};
+  return launch_variant(query_variant(kernel, lds_bytes, p.sc.b4_half == 0u), q, grid, block, stream);
 }
 
 // Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h).  Both 4-wide variants have the same
 // launch bounds; the full-LDS one stands for both.
-int RTOW_QCAT(query_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+int RTOW_CAT(query_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
   const KernelVariant<QueryParams> v = query_variant(kernel, lds_bytes, true);
   return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }

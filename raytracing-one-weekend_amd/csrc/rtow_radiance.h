@@ -35,8 +35,6 @@
 #ifndef RTOW_SUFFIX
 #error "define RTOW_SUFFIX"
 #endif
-#define RTOW_RCAT2(a, b) a##b
-#define RTOW_RCAT(a, b) RTOW_RCAT2(a, b)
 
 namespace rtow {
 namespace {
@@ -116,7 +114,7 @@ __device__ __forceinline__ unsigned long long take_rays(RayPool &pool, unsigned 
 // LDS (2 and 3; for 4: the whole image, else the top of its tree — the traversal stack is in LDS either way)
 template <int KERNEL, bool LDS>
 __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
-    RTOW_RCAT(rtow_radiance_, RTOW_SUFFIX)(const RadianceParams Q) {
+    RTOW_CAT(rtow_radiance_, RTOW_SUFFIX)(const RadianceParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
   const uint32_t k0 = P.seed_lo, k1 = P.seed_hi;
@@ -290,7 +288,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 // kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE (strict build): the instantiations of rtow_query.h
 template <int K, bool L>
 static KernelVariant<RadianceParams> radiance_kernel(unsigned lds_bytes) {
-  return kernel_variant<RTOW_RCAT(rtow_radiance_, RTOW_SUFFIX)<K, L>, RadianceParams>(lds_bytes);
+  return kernel_variant<RTOW_CAT(rtow_radiance_, RTOW_SUFFIX)<K, L>, RadianceParams>(lds_bytes);
 }
 
 static KernelVariant<RadianceParams> radiance_variant(int kernel, unsigned lds_bytes, bool b4_full) {
@@ -307,24 +305,22 @@ static KernelVariant<RadianceParams> radiance_variant(int kernel, unsigned lds_b
 }
 
 // p: the scene, seed_lo / seed_hi, max_child_rays, stack (strict), n_lanes, spill and the walk fields
-int RTOW_RCAT(launch_radiance_, RTOW_SUFFIX)(const TraceParams &p, const void *rays, const void *ids, void *out, uint32_t n,
-                                             int32_t samples_per_ray, uint32_t sample_first, unsigned long long *counters,
-                                             int kernel, int grid, int block, unsigned lds_bytes, void *stream) {
+int RTOW_CAT(launch_radiance_, RTOW_SUFFIX)(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block,
+                                            unsigned lds_bytes, void *stream) {
   RadianceParams q;
   q.P = p;
-  q.rays = (const unsigned char *)rays;
-  q.ids = (const uint32_t *)ids;
-  q.out = (double *)out;
-  q.n = n;
-  q.samples_per_ray = samples_per_ray;
-  q.sample_first = sample_first;
-  q.counters = counters;
-  const KernelVariant<RadianceParams> v = radiance_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
-  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
+  q.rays = (const unsigned char *)a.in;
+  q.ids = (const uint32_t *)a.ids;
+  q.out = (double *)a.result;
+  q.n = a.n;
+  q.samples_per_ray = a.samples;
+  q.sample_first = a.sample_first;
+  q.counters = a.counters;
+  return launch_variant(radiance_variant(kernel, lds_bytes, p.sc.b4_half == 0u), q, grid, block, stream);
 }
 
 // Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h), as query_occupancy_*.
-int RTOW_RCAT(radiance_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+int RTOW_CAT(radiance_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
   const KernelVariant<RadianceParams> v = radiance_variant(kernel, lds_bytes, true);
   return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }

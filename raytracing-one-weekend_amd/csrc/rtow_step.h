@@ -24,8 +24,6 @@
 #ifndef RTOW_SUFFIX
 #error "define RTOW_SUFFIX"
 #endif
-#define RTOW_SCAT2(a, b) a##b
-#define RTOW_SCAT(a, b) RTOW_SCAT2(a, b)
 
 namespace rtow {
 namespace {
@@ -65,7 +63,7 @@ constexpr int32_t kStepMiss = 0, kStepScattered = 1, kStepAbsorbed = 2, kStepSki
 // LDS (2 and 3; for 4: the whole image, else the top of its tree — the traversal stack is in LDS either way)
 template <int KERNEL, bool LDS>
 __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
-    RTOW_SCAT(rtow_step_, RTOW_SUFFIX)(const StepParams Q) {
+    RTOW_CAT(rtow_step_, RTOW_SUFFIX)(const StepParams Q) {
   const TraceParams &P = Q.P;
   const DevScene &sc = P.sc;
   const unsigned lane = lane_id();
@@ -171,7 +169,7 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
 // kernel: 1 STREAM, 2 BVH, 3 GRID, 4 BVH4, 5 REFTREE (strict build): the instantiations of rtow_query.h
 template <int K, bool L>
 static KernelVariant<StepParams> step_kernel(unsigned lds_bytes) {
-  return kernel_variant<RTOW_SCAT(rtow_step_, RTOW_SUFFIX)<K, L>, StepParams>(lds_bytes);
+  return kernel_variant<RTOW_CAT(rtow_step_, RTOW_SUFFIX)<K, L>, StepParams>(lds_bytes);
 }
 
 static KernelVariant<StepParams> step_variant(int kernel, unsigned lds_bytes, bool b4_full) {
@@ -188,29 +186,26 @@ static KernelVariant<StepParams> step_variant(int kernel, unsigned lds_bytes, bo
 }
 
 // p: the scene, seed_lo / seed_hi, n_lanes, spill and the walk fields
-int RTOW_SCAT(launch_step_, RTOW_SUFFIX)(const TraceParams &p, const void *rays, const void *ids, void *next, void *atten,
-                                         void *status, void *hits, uint32_t n, uint32_t request, uint32_t sample_first,
-                                         const int32_t *map, unsigned long long *counters, int kernel, int grid, int block,
-                                         unsigned lds_bytes, void *stream) {
+int RTOW_CAT(launch_step_, RTOW_SUFFIX)(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block,
+                                        unsigned lds_bytes, void *stream) {
   StepParams q;
   q.P = p;
-  q.rays = (const unsigned char *)rays;
-  q.ids = (const uint32_t *)ids;
-  q.next = (unsigned char *)next;
-  q.atten = (double *)atten;
-  q.status = (int32_t *)status;
-  q.hits = (unsigned char *)hits;
-  q.n = n;
-  q.request = request;
-  q.sample_first = sample_first;
-  q.map = map;
-  q.counters = counters;
-  const KernelVariant<StepParams> v = step_variant(kernel, lds_bytes, p.sc.b4_half == 0u);
-  return v.fn ? v.launch(q, grid, block, v.lds_bytes, (hipStream_t)stream) : (int)hipErrorInvalidValue;
+  q.rays = (const unsigned char *)a.in;
+  q.ids = (const uint32_t *)a.ids;
+  q.next = (unsigned char *)a.next;
+  q.atten = (double *)a.atten;
+  q.status = (int32_t *)a.status;
+  q.hits = (unsigned char *)a.hits;
+  q.n = a.n;
+  q.request = a.request;
+  q.sample_first = a.sample_first;
+  q.map = a.map;
+  q.counters = a.counters;
+  return launch_variant(step_variant(kernel, lds_bytes, p.sc.b4_half == 0u), q, grid, block, stream);
 }
 
 // Workgroups per CU that stay resident (resident_blocks, rtow_kernel_launch.h), as query_occupancy_*.
-int RTOW_SCAT(step_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
+int RTOW_CAT(step_occupancy_, RTOW_SUFFIX)(int kernel, int block, unsigned lds_bytes, int *vgprs) {
   const KernelVariant<StepParams> v = step_variant(kernel, lds_bytes, true);
   return resident_blocks(v.fn, block, v.lds_bytes, vgprs);
 }

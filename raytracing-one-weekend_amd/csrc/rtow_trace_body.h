@@ -58,8 +58,6 @@
 #ifndef RTOW_SUFFIX
 #error "define RTOW_SUFFIX"
 #endif
-#define RTOW_CAT2(a, b) a##b
-#define RTOW_CAT(a, b) RTOW_CAT2(a, b)
 
 namespace rtow {
 namespace {
