@@ -718,6 +718,93 @@ int rtow_path_step(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_
                    const rtow_ray_t *rays, int64_t n_rays, const uint32_t *ids, rtow_ray_t *next, double *atten,
                    int32_t *status, rtow_hit_t *hits, rtow_stats_t *stats);
 
+/* ---- ambient queries: hemisphere visibility at caller surface points ----------------------------------------------------
+ * "How much of the hemisphere above this surface point is open, which way is it open, and how much sky arrives through
+ * it?" — ambient occlusion, bent normals and sky-light baking for lightmap texels and probes, and the direct sky term for
+ * callers who drive their own bounces with rtow_path_step.  For every point the kernel draws `samples` cosine-weighted
+ * directions over the hemisphere of the normal from the point's Philox identity, asks rtow_occluded's question of each,
+ * and adds up the samples that are not occluded.  The n x samples rays (64 B each) a caller of rtow_occluded would
+ * generate, write and fold never reach memory, unless they are asked for (d_rays_out).
+ *
+ *   identity   sample j of point i draws Philox REQUEST 0 of (pixel, sample) = (ids[i][0], ids[i][1] + sample_first + j),
+ *              the sums mod 2^32; without ids (NULL) of (i, sample_first + j).  Request 0 is the camera's (jitter, shutter
+ *              time, lens point); no other query draws it.
+ *   direction  (px, py) = the lens point of that block (lens_from_block, csrc/rtow_trace_rng.h: uniform on the unit disk);
+ *              pz = sqrt(max(1 - (px px + py py), 0)) — the clamp acts: with the sampler's sine polynomial (error 7e-9)
+ *              px px + py py reaches 1 + 1.3e-8 at the largest radii; n = normal / sqrt(normal . normal); (t, b, n) the
+ *              branch-free orthonormal frame of Duff et al., "Building an orthonormal basis, revisited" (JCGT 6(1), 2017):
+ *              s = copysign(1, n.z), a = -1 / (s + n.z), c = n.x n.y a, t = (1 + s n.x^2 a, s c, -s n.x),
+ *              b = (c, s + n.y^2 a, -n.y);  d = (t px + b py) + n pz, NOT renormalised: cosine-weighted over the hemisphere
+ *              of n, |d| = 1 to rounding and up to 1 + 1e-8 where the clamp acted — so max_dist is a distance to that
+ *              relative accuracy.  The operand order of every expression is written once, in csrc/rtow_ambient.h.
+ *   visibility the ray (point, d, time, tmax = max_dist) is occluded exactly when rtow_occluded of the same precision and
+ *              kernel says so: some primitive's hit test accepts a t in [0.001, max_dist]; triangles are hit only where
+ *              det >= 1e-6, as everywhere else in the library.  The GRID walk takes d as it is, as rtow_occluded's does
+ *              (a -0.0 component steps the way its reciprocal points; the answer is the same as for +0.0).  tmin = 0.001
+ *              is the library's: a caller who needs a larger offset moves the point.
+ *   sums       for each sample that is NOT occluded, in sample order, by one lane, starting from +0.0:  open += 1;
+ *              bent += d;  sky += the reference's background for d (src/render.cpp:122-128: what rtow_path_step reports
+ *              as the attenuation of a MISS).  The caller divides: open / samples is the cosine-weighted visibility
+ *              (1 - ambient occlusion), bent / |bent| the bent normal, sky / samples the irradiance of the sky over pi.
+ *              A call with samples = k equals the in-order sum of k one-sample calls with sample_first + j, bit for bit
+ *              in both builds; no result depends on the batch's shape or on scheduling.
+ *   skipped    a point whose normal . normal is 0, NaN or infinite, or whose max_dist is NaN or below 0.001, does no walk:
+ *              all eight doubles of its record are +0.0 (samples included), and its rays_out slots hold the dead ray of
+ *              rtow_path_step (every field 0, tmax = -1).
+ *   d_rays_out optional (NULL: nothing is exported): rtow_ray_t[n][samples], point-major — exactly the rays the walks took
+ *              (origin = point, direction = d, time, tmax = max_dist).  rtow_occluded on them and the sums above ARE the
+ *              record; a caller can also reuse the directions.
+ *   buffers    d_points: rtow_surface_point_t[n]; d_out: rtow_ambient_t[n]; d_rays_out — all 16-byte aligned; d_ids:
+ *              uint32_t[n][2], 8-byte aligned, or NULL.  All DEVICE pointers.  Nothing is written beyond n records and
+ *              n x samples rays.
+ *   precision  RTOW_F64_STRICT: bit-identical to the definition above evaluated in IEEE binary64 without contraction, in
+ *                               the operand order of csrc/rtow_ambient.h, under BRUTE, BVH, GRID and BVH4 (for time in
+ *                               [0, 1]) and under REFTREE against its own closest hit, with either builder;
+ *              RTOW_F64_FAST:   the same expressions contracted, with the fast build's sqrt, rcp and div, and the fast
+ *                               build's any-hit walks (the band of rtow_occluded_device);
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ *   kernel     as rtow_occluded_device: the same resolution, fallbacks, residency rules (RTOW_ENOSCENE after a lean
+ *              upload) and kernel_used; RTOW_KERNEL_REFTREE is strict only.
+ * Enqueued on hip_stream with the ordering rule of rtow_intersect_device; returns without synchronising unless stats !=
+ * NULL, which synchronises and fills samples = segments = n * params->samples, prim_tests, node_tests, kernel_ms,
+ * total_ms, kernel_used.
+ * Errors: those of rtow_radiance_device, and RTOW_EINVAL for samples outside [1, RTOW_MAX_AMBIENT_SAMPLES], for
+ * n * samples > 2^31 - 64 when d_rays_out is given, for points, results or rays that are not 16-byte aligned and ids that
+ * are not 8-byte aligned.  n == 0 returns RTOW_OK and launches nothing.  One call in flight per context.  The render path
+ * is not involved: the profile ring and the dropped-sample word are untouched, and a render or any other query after any
+ * number of ambient queries is bit-identical to one without them. */
+typedef struct rtow_surface_point_t { /* 64 B, 16-byte aligned: the layout of rtow_ray_t */
+  double point[3];
+  double time;      /* shutter time of the moving spheres, as in the ray queries */
+  double normal[3]; /* need not be unit length */
+  double max_dist;  /* occluders count within [0.001, max_dist]; +inf: unbounded */
+} rtow_surface_point_t;
+
+typedef struct rtow_ambient_params_t { /* 16 B */
+  uint64_t seed;          /* Philox key, as rtow_config_t::seed */
+  int32_t samples;        /* 1 .. RTOW_MAX_AMBIENT_SAMPLES per point */
+  uint32_t sample_first;  /* added (mod 2^32) to every point's first sample index */
+} rtow_ambient_params_t;
+
+typedef struct rtow_ambient_t { /* 64 B, 16-byte aligned: four 16-byte stores per point */
+  double open;     /* number of samples that are not occluded */
+  double bent[3];  /* sum of their directions */
+  double sky[3];   /* sum of the reference's sky colour over their directions */
+  double samples;  /* samples taken: params->samples, or 0 for a skipped point */
+} rtow_ambient_t;
+
+#define RTOW_MAX_AMBIENT_SAMPLES 65536
+
+int rtow_ambient_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_ambient_params_t *params,
+                        const void *d_points /* rtow_surface_point_t[n] */, int64_t n,
+                        const void *d_ids /* uint32_t[n][2] or NULL */, void *d_out /* rtow_ambient_t[n] */,
+                        void *d_rays_out /* rtow_ray_t[n][samples] or NULL */, void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous.  ids and rays_out
+ * may be NULL. */
+int rtow_ambient(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_ambient_params_t *params,
+                 const rtow_surface_point_t *points, int64_t n, const uint32_t *ids, rtow_ambient_t *out,
+                 rtow_ray_t *rays_out, rtow_stats_t *stats);
+
 /* ---- the camera stage: primaries of the resident camera, first-hit guide buffers ----------------------------------------
  * The one piece of the render the queries above leave out: Camera::get_ray (src/render.cpp:158-159,
  * src/common-model.cpp:156-167) for the camera of the scene resident in ctx (after the last upload or refit), fed from

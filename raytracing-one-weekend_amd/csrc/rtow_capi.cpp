@@ -117,6 +117,7 @@ void rtow_ctx_destroy(rtow_ctx *c) {
                     &c->partials, &c->stack, &c->counters, &c->spill, &c->out, &c->out8, &c->rtree, &c->counters_init,
                     &c->dropped, &c->q_counters, &c->q_spill, &c->q_rays, &c->q_hits, &c->q_occ, &c->q_map[0], &c->q_map[1],
                     &c->q_map[2], &c->q_stack, &c->q_ids, &c->q_rgb, &c->q_status, &c->q_guides, &c->q_khits, &c->q_kcounts,
+                    &c->q_ambient, &c->q_ambient_rays,
                     &c->rf.map2, &c->rf.map4, &c->rf.par2, &c->rf.par4, &c->rf.need4, &c->rf.flags,
                     &c->rf.nbox2, &c->rf.nbox4, &c->rf.sbox4, &c->rf.pbox, &c->rf.partials, &c->rf.area, &c->rf.g_sph,
                     &c->rf.g_mov, &c->rf.g_tri, &c->tile_table})

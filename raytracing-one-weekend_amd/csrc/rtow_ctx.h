@@ -309,6 +309,8 @@ struct rtow_ctx {
                                  // attenuations and hits go through q_rgb and q_hits)
   DevBuf q_guides;               // rtow_guides: the host form's staging (rtow_camera_rays stages in q_rays / q_ids)
   DevBuf q_khits, q_kcounts;     // rtow_first_hits, rtow_nearest: the host forms' staging (their inputs go through q_rays)
+  DevBuf q_ambient, q_ambient_rays;  // rtow_ambient: the host form's records and, when the caller asks for the sampled rays,
+                                     // n x samples of them (its points and ids go through q_rays / q_ids)
   bool q_map_ok[3] = {false, false, false};
   hipEvent_t q_ev[4] = {};
   unsigned long long *h_qcounters = nullptr;

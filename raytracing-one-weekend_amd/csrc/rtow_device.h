@@ -194,7 +194,8 @@ struct QueryArgs {
   void *hits = nullptr;       // hit records: n, or n * k
   void *next = nullptr, *atten = nullptr, *status = nullptr;  // path step: scattered rays, attenuations, status words
   void *counts = nullptr;     // optional: entries written per query (first hits, k nearest)
-  void *result = nullptr;     // occlusion bytes, radiance sums, guide records, camera rays
+  void *result = nullptr;     // occlusion bytes, radiance sums, guide records, camera rays, ambient records
+  void *rays_out = nullptr;   // ambient: optional export of the sampled rays, `samples` per point
   uint32_t n = 0;             // queries (the guides: queue positions)
   int32_t k = 0;              // entries kept per query (max_hits, k)
   uint32_t request = 0;       // path step: 1 + bounce

@@ -1,5 +1,5 @@
 // rtow_queries.cpp — every query over the resident scene: rtow_intersect*, rtow_occluded*, rtow_closest_point*,
-// rtow_first_hits*, rtow_nearest*, rtow_radiance*, rtow_path_step* and the camera stage (rtow_camera_rays*, rtow_guides*).
+// rtow_first_hits*, rtow_nearest*, rtow_radiance*, rtow_path_step*, rtow_ambient* and the camera stage (rtow_camera_rays*, rtow_guides*).
 //
 // One host path serves them all.  A QueryKind row says what tells an entry-point pair apart — its buffers, its strategy
 // resolver, its launchers — and query_device / query_host are the two entry forms of every row; the camera stage, whose
@@ -13,18 +13,19 @@
 
 namespace rtow {
 // csrc/rtow_<family>_{strict,fast}.hip (rtow_query.h, rtow_occlude.h, rtow_pointq.h, rtow_first_hits.h, rtow_nearest.h,
-// rtow_radiance.h, rtow_step.h, rtow_guides.h): every family exports one launcher and one occupancy function per build
+// rtow_radiance.h, rtow_step.h, rtow_guides.h, rtow_ambient.h): every family exports one launcher and one occupancy function per build
 using QueryLaunchFn = int(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block, unsigned lds_bytes,
                           void *stream);
 using QueryOccupancyFn = int(int kernel, int block, unsigned lds_bytes, int *vgprs);
 QueryLaunchFn launch_query_strict, launch_query_fast, launch_occlude_strict, launch_occlude_fast, launch_pointq_strict,
     launch_pointq_fast, launch_first_hits_strict, launch_first_hits_fast, launch_nearest_strict, launch_nearest_fast,
     launch_radiance_strict, launch_radiance_fast, launch_step_strict, launch_step_fast, launch_guides_strict,
-    launch_guides_fast, launch_camera_rays_strict, launch_camera_rays_fast;
+    launch_guides_fast, launch_camera_rays_strict, launch_camera_rays_fast, launch_ambient_strict, launch_ambient_fast;
 QueryOccupancyFn query_occupancy_strict, query_occupancy_fast, occlude_occupancy_strict, occlude_occupancy_fast,
     pointq_occupancy_strict, pointq_occupancy_fast, first_hits_occupancy_strict, first_hits_occupancy_fast,
     nearest_occupancy_strict, nearest_occupancy_fast, radiance_occupancy_strict, radiance_occupancy_fast,
-    step_occupancy_strict, step_occupancy_fast, guides_occupancy_strict, guides_occupancy_fast;
+    step_occupancy_strict, step_occupancy_fast, guides_occupancy_strict, guides_occupancy_fast, ambient_occupancy_strict,
+    ambient_occupancy_fast;
 }  // namespace rtow
 
 namespace {
@@ -84,7 +85,7 @@ struct QueryBuf {
   bool required;             // NULL is refused when there is anything to do
   unsigned align;            // alignment required of the device buffer
   size_t item_bytes;         // record size (include/rtow.h)
-  bool per_k;                // k (max_hits) records per query instead of one
+  bool per_k;                // k (max_hits; the ambient query: samples) records per query instead of one
   bool out;                  // the host form copies it back (otherwise: in)
   DevBuf rtow_ctx::*stage;   // the host form's device buffer; two buffers of one size may share one (a step in place)
   void *rtow::QueryArgs::*arg;  // where the launcher finds it; nullptr: the input, QueryArgs::in
@@ -94,8 +95,8 @@ struct QueryBuf {
 struct QueryCall {
   int32_t precision, kernel;
   int64_t n;
-  int32_t k;           // k / max_hits (rows with k_max)
-  const void *params;  // rtow_radiance_params_t / rtow_step_params_t (rows with has_params)
+  int32_t k;           // k / max_hits (rows with k_max); the ambient query: params->samples (checked by its own hook)
+  const void *params;  // rtow_radiance_params_t / rtow_step_params_t / rtow_ambient_params_t (rows with has_params)
   void *buf[kMaxQueryBufs];
   void *stream;
   rtow_stats_t *stats;
@@ -115,12 +116,15 @@ struct QueryKind {
   int32_t k_max = 0;
   bool k_first = false;          // k is checked before n (else behind it)
   bool has_params = false;       // NULL params are refused right behind ctx (device form)
+  bool check_sizes_staging = false;  // the host form, too, refuses NULL params and runs `check` before it stages anything:
+                                     // the row's params size a buffer (the ambient query's ray export)
   int Knobs::*block_cap = nullptr;            // nullptr, or the test knob that caps the workgroups
   rtow::QueryLaunchFn *launch[2] = {};        // [0] strict, [1] fast
   rtow::QueryOccupancyFn *occupancy[2] = {};  // nullptr: a kernel that walks nothing, 8 workgroups per CU
   // what is truly per family (each may be nullptr): the checks behind the alignments; what the kernel reads beyond the
   // walks' fields (the seed and stack of TraceParams, the scalars of QueryArgs); the stats beyond query_launch's
   int (*check)(const QueryCall &call) = nullptr;
+  int64_t (*grid_items)(const QueryCall &call) = nullptr;  // what the grid is sized for when that is not n
   int (*fill)(rtow_ctx *c, const QueryCall &call, bool strict, rtow::TraceParams &P, rtow::QueryArgs &a) = nullptr;
   void (*epilogue)(const rtow_ctx *c, const QueryCall &call, rtow_stats_t *stats) = nullptr;
 };
@@ -223,6 +227,42 @@ const QueryKind kStep = {
       a.sample_first = prm->sample_first;
       return (int)RTOW_OK;
     }};
+// ambient (csrc/rtow_ambient.h): `samples` any-hit walks per surface point, drawn in the kernel; one record per point and,
+// on request, the `samples` rays it walked.  The samples size that export, so the hook below runs before the host form
+// stages; QueryCall::k carries them to the staging (buf_bytes).
+const QueryKind kAmbient = {
+    .count = "n", .n_bufs = 4,
+    .bufs = {{"point", true, 16, sizeof(rtow_surface_point_t), false, false, &rtow_ctx::q_rays, nullptr},
+             {"ids", false, 8, 8, false, false, &rtow_ctx::q_ids, &QueryArgs::ids},
+             {"result", true, 16, sizeof(rtow_ambient_t), false, true, &rtow_ctx::q_ambient, &QueryArgs::result},
+             {"ray", false, 16, sizeof(rtow_ray_t), true, true, &rtow_ctx::q_ambient_rays, &QueryArgs::rays_out}},
+    .walk = Walk::kRay, .has_params = true, .check_sizes_staging = true, RTOW_LAUNCHERS(ambient),
+    .check = [](const QueryCall &call) {
+      const int32_t samples = ((const rtow_ambient_params_t *)call.params)->samples;
+      if (samples < 1 || samples > RTOW_MAX_AMBIENT_SAMPLES)
+        return fail(RTOW_EINVAL, "samples %d outside [1, %d]", samples, RTOW_MAX_AMBIENT_SAMPLES);
+      if (call.buf[3] && call.n * (int64_t)samples > kMaxQueryRays)
+        return fail(RTOW_EINVAL, "n * samples = %lld rays to export, beyond 2^31 - 64", (long long)(call.n * (int64_t)samples));
+      return (int)RTOW_OK;
+    },
+    // a wave's 64 points are 64 x samples walks: from 16 samples on, one wave's step is a workgroup's worth of work, and
+    // the kernel numbers its waves across the workgroups
+    .grid_items = [](const QueryCall &call) {
+      return call.n * (int64_t)std::min(((const rtow_ambient_params_t *)call.params)->samples, 16);
+    },
+    .fill = [](rtow_ctx *, const QueryCall &call, bool, rtow::TraceParams &P, QueryArgs &a) {
+      const auto *prm = (const rtow_ambient_params_t *)call.params;
+      P.seed_lo = (uint32_t)(prm->seed & 0xffffffffu);
+      P.seed_hi = (uint32_t)(prm->seed >> 32);
+      a.samples = prm->samples;
+      a.sample_first = prm->sample_first;
+      return (int)RTOW_OK;
+    },
+    .epilogue = [](const rtow_ctx *, const QueryCall &call, rtow_stats_t *stats) {
+      stats->samples = stats->segments = (uint64_t)call.n * (uint64_t)((const rtow_ambient_params_t *)call.params)->samples;
+    }};
+static_assert(sizeof(rtow_surface_point_t) == 64 && sizeof(rtow_ambient_t) == 64 && sizeof(rtow_ambient_params_t) == 16,
+              "the ambient query's records: four 16-byte loads, four 16-byte stores");
 // the camera stage (csrc/rtow_guides.h): the primaries of the resident camera — a kernel that reads the camera alone —
 // and the first-hit guide buffers
 const QueryKind kCameraRays = {
@@ -430,7 +470,8 @@ int query_device(rtow_ctx *c, const QueryKind &k, const QueryCall &call) {
   a.n = (uint32_t)call.n;
   a.k = call.k;
   if (k.mapped && a.hits && (rc = query_map_for(c, q.kernel, &a.map))) return rc;
-  rc = query_launch(c, k, q, a, call.n, call.stream, call.stats, [&](rtow::TraceParams &P, QueryArgs &args) {
+  const int64_t n_items = k.grid_items ? k.grid_items(call) : call.n;
+  rc = query_launch(c, k, q, a, n_items, call.stream, call.stats, [&](rtow::TraceParams &P, QueryArgs &args) {
     return k.fill ? k.fill(c, call, q.strict, P, args) : (int)RTOW_OK;
   });
   if (rc == RTOW_OK && call.stats && k.epilogue) k.epilogue(c, call, call.stats);
@@ -442,6 +483,10 @@ int query_host(rtow_ctx *c, const QueryKind &k, const QueryCall &call) {
   if (!c) return fail(RTOW_EINVAL, "ctx is NULL");
   int rc;
   if ((rc = check_counts(k, call)) || (rc = check_buffers(k, call.buf, call.n, "array", false))) return rc;
+  if (k.check_sizes_staging) {
+    if (!call.params) return fail(RTOW_EINVAL, "params is NULL");
+    if ((rc = k.check(call))) return rc;
+  }
   QueryCall dev = call;
   dev.stream = nullptr;
   if (call.n == 0) {
@@ -662,6 +707,22 @@ int rtow_path_step(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_st
   return guarded("rtow_path_step", [&] {
     return query_host(c, kStep, {precision, kernel, n_rays, 0, params,
                                  {(void *)rays, (void *)ids, next, atten, status, hits}, nullptr, stats});
+  });
+}
+int rtow_ambient_device(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ambient_params_t *params,
+                        const void *d_points, int64_t n, const void *d_ids, void *d_out, void *d_rays_out, void *hip_stream,
+                        rtow_stats_t *stats) {
+  return guarded("rtow_ambient_device", [&] {
+    return query_device(c, kAmbient, {precision, kernel, n, params ? params->samples : 0, params,
+                                      {(void *)d_points, (void *)d_ids, d_out, d_rays_out}, hip_stream, stats});
+  });
+}
+int rtow_ambient(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ambient_params_t *params,
+                 const rtow_surface_point_t *points, int64_t n, const uint32_t *ids, rtow_ambient_t *out, rtow_ray_t *rays_out,
+                 rtow_stats_t *stats) {
+  return guarded("rtow_ambient", [&] {
+    return query_host(c, kAmbient, {precision, kernel, n, params ? params->samples : 0, params,
+                                    {(void *)points, (void *)ids, out, rays_out}, nullptr, stats});
   });
 }
 int rtow_camera_rays_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_rays, void *d_ids, void *hip_stream) {

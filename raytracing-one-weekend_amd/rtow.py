@@ -155,6 +155,24 @@ class StepParams(C.Structure):
 STEP_MISS, STEP_SCATTERED, STEP_ABSORBED, STEP_SKIPPED = 0, 1, 2, 3
 
 
+class SurfacePoint(C.Structure):
+    """rtow_surface_point_t (64 B, the layout of rtow_ray_t): occluders count within [0.001, max_dist] of the point."""
+    _fields_ = [("point", d3), ("time", C.c_double), ("normal", d3), ("max_dist", C.c_double)]
+
+
+class AmbientParams(C.Structure):
+    """rtow_ambient_params_t (16 B): Philox key, samples per point, offset of every point's first sample index."""
+    _fields_ = [("seed", C.c_uint64), ("samples", C.c_int32), ("sample_first", C.c_uint32)]
+
+
+class Ambient(C.Structure):
+    """rtow_ambient_t (64 B): SUMS over a point's unoccluded samples (count, directions, sky colour) and the samples taken."""
+    _fields_ = [("open", C.c_double), ("bent", d3), ("sky", d3), ("samples", C.c_double)]
+
+
+MAX_AMBIENT_SAMPLES = 65536  # RTOW_MAX_AMBIENT_SAMPLES: the most samples rtow_ambient takes per point
+
+
 # numpy views of the same layouts (arrays of rays / hits for rtow_intersect*)
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("time", "<f8"), ("direction", "<f8", (3,)), ("tmax", "<f8")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("prim", "<i4"), ("kind", "<i4"),
@@ -168,6 +186,22 @@ GUIDE_DTYPE = np.dtype([("albedo", "<f8", (3,)), ("normal", "<f8", (3,)), ("dept
 POINT_QUERY_DTYPE = np.dtype([("point", "<f8", (3,)), ("time", "<f8"), ("max_dist", "<f8"), ("pad_", "<f8")])
 POINT_HIT_DTYPE = np.dtype([("dist", "<f8"), ("point", "<f8", (3,)), ("prim", "<i4"), ("kind", "<i4"),
                             ("material", "<i4"), ("pad_", "<i4")])
+
+
+# rtow_surface_point_t / rtow_ambient_t (rtow_ambient*)
+SURFACE_POINT_DTYPE = np.dtype([("point", "<f8", (3,)), ("time", "<f8"), ("normal", "<f8", (3,)), ("max_dist", "<f8")])
+AMBIENT_DTYPE = np.dtype([("open", "<f8"), ("bent", "<f8", (3,)), ("sky", "<f8", (3,)), ("samples", "<f8")])
+
+
+def make_surface_points(points, normals, time=0.0, max_dist=float("inf")):
+    """A SURFACE_POINT_DTYPE array from [n, 3] points and normals (time and max_dist: scalars or [n])."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    q = np.empty(len(p), dtype=SURFACE_POINT_DTYPE)
+    q["point"] = p
+    q["normal"] = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    q["time"] = time
+    q["max_dist"] = max_dist
+    return q
 
 
 def make_point_queries(points, time=0.0, max_dist=float("inf")):
@@ -211,6 +245,7 @@ EXPORTS = [
     "rtow_camera_rays_device", "rtow_camera_rays", "rtow_camera_ray_count", "rtow_guides_device", "rtow_guides",
     "rtow_debug_last_spec", "rtow_first_hits_device", "rtow_first_hits", "rtow_nearest_device", "rtow_nearest",
     "rtow_debug_last_counted", "rtow_debug_walk_consts", "rtow_path_step_device", "rtow_path_step",
+    "rtow_ambient_device", "rtow_ambient",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -323,6 +358,11 @@ def lib():
                                             C.POINTER(Stats)]
         L.rtow_path_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(StepParams), C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    if hasattr(L, "rtow_ambient"):
+        L.rtow_ambient_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AmbientParams), C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rtow_ambient.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AmbientParams), C.c_void_p, C.c_int64,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     if hasattr(L, "rtow_guides"):
         L.rtow_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]
         L.rtow_camera_rays.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p]
@@ -757,6 +797,45 @@ class Context:
                                           C.c_void_p(d_ids) if d_ids else None, C.c_void_p(d_next), C.c_void_p(d_atten),
                                           C.c_void_p(d_status), C.c_void_p(d_hits) if d_hits else None, C.c_void_p(stream),
                                           C.byref(st) if st is not None else None), "rtow_path_step_device")
+        return st
+
+    def ambient(self, points, samples, seed=1, ids=None, sample_first=0, precision=F64_FAST, kernel=KERNEL_AUTO,
+                want_rays=False, want_stats=False):
+        """Hemisphere visibility at every surface point (a SURFACE_POINT_DTYPE array, host memory): `samples`
+        cosine-weighted directions per point drawn from its Philox identity, and over those that reach max_dist
+        unoccluded their count, the sum of the directions and the sum of the sky colour — an AMBIENT_DTYPE array
+        (rtow_ambient).  `ids`: [n, 2] uint32 (pixel, first sample) identities; None: (i, 0).  With `want_rays` also the
+        [n, samples] RAY_DTYPE array of the rays the walks took, and Stats with `want_stats`: out[, rays][, stats]."""
+        p = np.ascontiguousarray(points, dtype=SURFACE_POINT_DTYPE).reshape(-1)
+        n = len(p)
+        idp = None
+        if ids is not None:
+            ida = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1, 2)
+            if len(ida) != n:
+                raise ValueError("ids must be [n, 2]")
+            idp = ida.ctypes.data_as(C.c_void_p)
+        out = np.empty(n, dtype=AMBIENT_DTYPE)
+        rays = np.empty((n, min(max(int(samples), 0), MAX_AMBIENT_SAMPLES)), dtype=RAY_DTYPE) if want_rays else None
+        prm = AmbientParams(seed, int(samples), sample_first)
+        st = Stats() if want_stats else None
+        check(lib().rtow_ambient(self._h, precision, kernel, C.byref(prm), p.ctypes.data_as(C.c_void_p), n, idp,
+                                 out.ctypes.data_as(C.c_void_p),
+                                 rays.ctypes.data_as(C.c_void_p) if rays is not None else None,
+                                 C.byref(st) if st is not None else None), "rtow_ambient")
+        res = (out,) + ((rays,) if want_rays else ()) + ((st,) if want_stats else ())
+        return res if len(res) > 1 else out
+
+    def ambient_device(self, d_points: int, n: int, d_ids: int, d_out: int, samples: int, d_rays_out: int = 0, seed=1,
+                       sample_first=0, precision=F64_FAST, kernel=KERNEL_AUTO, stream: int = 0, want_stats=False):
+        """The same on device buffers (raw pointers: n x 64-byte points, n x 2 uint32 ids or 0, n x 64-byte records,
+        n x samples x 64-byte rays or 0 for none), enqueued on `stream` (rtow_ambient_device); returns Stats with
+        `want_stats` (then synchronised), else None."""
+        prm = AmbientParams(seed, int(samples), sample_first)
+        st = Stats() if want_stats else None
+        check(lib().rtow_ambient_device(self._h, precision, kernel, C.byref(prm), C.c_void_p(d_points), n,
+                                        C.c_void_p(d_ids) if d_ids else None, C.c_void_p(d_out),
+                                        C.c_void_p(d_rays_out) if d_rays_out else None, C.c_void_p(stream),
+                                        C.byref(st) if st is not None else None), "rtow_ambient_device")
         return st
 
     def camera_rays(self, cfg: Config):
