@@ -805,6 +805,94 @@ int rtow_ambient(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_am
                  const rtow_surface_point_t *points, int64_t n, const uint32_t *ids, rtow_ambient_t *out,
                  rtow_ray_t *rays_out, rtow_stats_t *stats);
 
+/* ---- swept-sphere (sphere cast) queries ---------------------------------------------------------------------------------
+ * "Where does a ball travelling along this segment first touch the scene, and what does it touch?" — a camera that must
+ * not clip through geometry, a character or particle with a size, a thick ray, continuous collision, clearance along a path.
+ *
+ * Definition.  The geometry is that of rtow_closest_point: the device's records, the sphere SURFACE | |p - c| - R | with
+ * R = sqrt(|r^2|), a moving sphere's centre at the query's `time`.  A hollow (negative-radius) sphere is the same surface,
+ * so a sphere cast inside a large sphere touches its inner side.  For a query (o, d, time, tmax, rho) write
+ * p(t) = o + d t and D(x, c) for the distance from x to primitive c.  Primitive c answers with the smallest t in
+ * [0, tmax] with D(p(t), c) <= rho — none when the sphere never comes that close; t is in units of |d|.  The scene's
+ * answer is the minimum over the primitives by (t, insertion index): the lowest index wins an exact tie (the tie rule of
+ * rtow_first_hits), so the strict answer does not depend on kernel, builder or schedule.
+ *
+ * Per-primitive formulas (csrc/rtow_sweep_walks.h; written once, in a fixed operation order; tests/sweep_ref.py mirrors
+ * them).  Every root of |w + d t| = r is taken through the perpendicular q = w + d t0, t0 = -(w.d) / (d.d), as
+ * t0 -+ sqrt((r^2 - q.q) / d.d): well conditioned for a far origin and for a sweep nearly parallel to an edge.
+ *   start overlap  (all primitives) the formulas of rtow_closest_point at o give a distance <= rho: t = 0 and
+ *                  start_overlap = 1.  In the strict build start_overlap == 1 exactly when strict
+ *                  rtow_closest_point(o, time, max_dist = rho) reports a hit.
+ *   sphere         otherwise, with oc = o - c, L2 = oc.oc, h = oc.d: outside (L2 > (R + rho)^2) the near root of
+ *                  |p - c| = R + rho, a hit iff the perpendicular is no longer than R + rho and h < 0 — a tangent pass
+ *                  touches: the contact set is closed; inside (L2 < (R - rho)^2, R > rho) the far root of |p - c| = R - rho.
+ *   triangle       otherwise, the minimum over the accepted candidates of the pieces of the Minkowski sum:
+ *                  face — only when n.n > 0, the centre starts outside the slab |n.(o - a)| > rho |n| and approaches the
+ *                    plane: where the centre reaches the offset plane on its own side, accepted when the Gram-form
+ *                    barycentrics of p(t) - a lie inside (sn, tn in [0, n.n], sn + tn <= n.n, as in rtow_closest_point);
+ *                  three edges — for each edge with e.e > 0 the near root of the infinite cylinder of radius rho about the
+ *                    edge line, accepted when the sweep starts outside that cylinder, approaches its axis and the axial
+ *                    parameter at contact lies in [0, e.e];
+ *                  three vertices — the near root of the sphere of radius rho about each vertex, when the sweep starts
+ *                    outside it and approaches.
+ *                  Exact over the reals: the sum is the union of a prism and three capsules; the first entry into a union
+ *                  is the minimum of the first entries into its convex parts; a lateral entry into the prism, or an entry
+ *                  through a cylinder cap, lies inside a capsule or a vertex sphere; every accepted candidate is a point
+ *                  of the union.  A degenerate triangle answers as its edges and vertices do.  No division is unguarded and
+ *                  no field is ever NaN for a finite query.  rho = 0 is allowed: a two-sided ray against the surfaces,
+ *                  with no determinant cut and t from 0.
+ *   acceptance     a candidate is accepted when t <= bound, inclusive; the bound starts at tmax and shrinks to the best t;
+ *                  every member of a tie at the bound is still visited.
+ *   skipped        the miss record and no walk when: o, time, d, tmax or radius is NaN; radius is negative or infinite;
+ *                  tmax is negative; d.d is 0 or infinite; o or time is infinite.  (pad_ is not read.)  tmax = +inf is
+ *                  unbounded.
+ *   time           results are independent of the kernel for time in [0, 1] only, as for every other query.
+ *
+ *   precision  RTOW_F64_STRICT: the whole record is bit-identical to the definition evaluated by those formulas in IEEE
+ *                               binary64 in their written order, under BRUTE, BVH, BVH4 and AUTO, with either builder and
+ *                               after a refit;
+ *              RTOW_F64_FAST:   the same formulas contracted (FMA) with the fast build's square root and reciprocal.  Its
+ *                               promise is semantic, with the band B(c) = 96 u S(c), u = 2^-53, S(c) = |o|_1 + |t d|_1 +
+ *                               rho + the magnitudes of primitive c (|a|_1 + |e1|_1 + |e2|_1; |c|_1 + R; |c0|_1 +
+ *                               |time (c1 - c0)|_1 + R), t the reported t (tmax on a miss):
+ *                                 a hit on c* at t <= tmax: | D(centre, c*) - rho | <= B(c*) — on a start overlap t == 0 and
+ *                                   D(o, c*) <= rho + B(c*); dist and point meet rtow_closest_point's two point clauses at
+ *                                   centre; and no primitive was passed through on the way: the distance from the segment
+ *                                   [o, centre] to every primitive c is >= rho - B(c);
+ *                                 a miss: the distance from the segment [o, p(tmax)] to every c is >= rho - B(c).
+ *                               Where a primitive's segment distance is within its band of rho either answer is allowed.
+ *                               The strict build meets the same with 48 u (tests/sweep_ref.py counts the roundings);
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ *   kernel     BRUTE, BVH and BVH4 run their own walks (ray walks against boxes inflated by rho); GRID has no sweep walk
+ *              and is answered by BVH (kernel_used says BVH); AUTO takes BVH4, else BVH, else BRUTE; the fallbacks and
+ *              RTOW_ENOSCENE rules are rtow_closest_point's.  RTOW_KERNEL_REFTREE: RTOW_EINVAL.
+ * dist and point are exactly what the formulas of rtow_closest_point compute at centre for the winning primitive: the
+ * contact normal is centre - point, and a caller who wants it unit-length divides by dist.  d_queries / d_hits are DEVICE
+ * pointers, both 16-byte aligned; nothing beyond n is written.  Stream ordering, stats (segments = n, prim_tests,
+ * node_tests, kernel_ms, total_ms, kernel_used) and errors are those of rtow_closest_point_device.  n == 0 launches
+ * nothing.  One call in flight per context; the render path (profile ring, dropped-sample word) is not involved. */
+typedef struct rtow_sweep_t {      /* 80 B, 16-byte aligned: five 16-byte loads */
+  double origin[3]; double time;
+  double direction[3]; double tmax;
+  double radius; double pad_;
+} rtow_sweep_t;
+
+typedef struct rtow_sweep_hit_t {  /* 80 B, 16-byte aligned: five 16-byte stores */
+  double t;          /* +inf on a miss */
+  double dist;       /* closest-point distance from centre to the primitive: ~radius at a contact, below it on a start
+                        overlap (radius - dist is the penetration depth); +inf on a miss */
+  double centre[3];  /* origin + direction*t; 0 on a miss */
+  double point[3];   /* the closest point of that primitive to centre: the contact point; 0 on a miss */
+  int32_t prim, kind, material;   /* as rtow_point_hit_t; -1 on a miss */
+  int32_t start_overlap;          /* 1 when t == 0 because the sphere already touches at the origin */
+} rtow_sweep_hit_t;
+
+int rtow_sweep_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const void *d_queries, int64_t n,
+                      void *d_hits, void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
+int rtow_sweep(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_sweep_t *queries, int64_t n,
+               rtow_sweep_hit_t *hits, rtow_stats_t *stats);
+
 /* ---- the camera stage: primaries of the resident camera, first-hit guide buffers ----------------------------------------
  * The one piece of the render the queries above leave out: Camera::get_ray (src/render.cpp:158-159,
  * src/common-model.cpp:156-167) for the camera of the scene resident in ctx (after the last upload or refit), fed from

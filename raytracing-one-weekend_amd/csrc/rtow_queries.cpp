@@ -1,5 +1,5 @@
 // rtow_queries.cpp — every query over the resident scene: rtow_intersect*, rtow_occluded*, rtow_closest_point*,
-// rtow_first_hits*, rtow_nearest*, rtow_radiance*, rtow_path_step*, rtow_ambient* and the camera stage (rtow_camera_rays*, rtow_guides*).
+// rtow_first_hits*, rtow_nearest*, rtow_radiance*, rtow_path_step*, rtow_ambient*, rtow_sweep* and the camera stage (rtow_camera_rays*, rtow_guides*).
 //
 // One host path serves them all.  A QueryKind row says what tells an entry-point pair apart — its buffers, its strategy
 // resolver, its launchers — and query_device / query_host are the two entry forms of every row; the camera stage, whose
@@ -13,19 +13,20 @@
 
 namespace rtow {
 // csrc/rtow_<family>_{strict,fast}.hip (rtow_query.h, rtow_occlude.h, rtow_pointq.h, rtow_first_hits.h, rtow_nearest.h,
-// rtow_radiance.h, rtow_step.h, rtow_guides.h, rtow_ambient.h): every family exports one launcher and one occupancy function per build
+// rtow_radiance.h, rtow_step.h, rtow_guides.h, rtow_ambient.h, rtow_sweep.h): every family exports one launcher and one occupancy function per build
 using QueryLaunchFn = int(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block, unsigned lds_bytes,
                           void *stream);
 using QueryOccupancyFn = int(int kernel, int block, unsigned lds_bytes, int *vgprs);
 QueryLaunchFn launch_query_strict, launch_query_fast, launch_occlude_strict, launch_occlude_fast, launch_pointq_strict,
     launch_pointq_fast, launch_first_hits_strict, launch_first_hits_fast, launch_nearest_strict, launch_nearest_fast,
     launch_radiance_strict, launch_radiance_fast, launch_step_strict, launch_step_fast, launch_guides_strict,
-    launch_guides_fast, launch_camera_rays_strict, launch_camera_rays_fast, launch_ambient_strict, launch_ambient_fast;
+    launch_guides_fast, launch_camera_rays_strict, launch_camera_rays_fast, launch_ambient_strict, launch_ambient_fast,
+    launch_sweep_strict, launch_sweep_fast;
 QueryOccupancyFn query_occupancy_strict, query_occupancy_fast, occlude_occupancy_strict, occlude_occupancy_fast,
     pointq_occupancy_strict, pointq_occupancy_fast, first_hits_occupancy_strict, first_hits_occupancy_fast,
     nearest_occupancy_strict, nearest_occupancy_fast, radiance_occupancy_strict, radiance_occupancy_fast,
     step_occupancy_strict, step_occupancy_fast, guides_occupancy_strict, guides_occupancy_fast, ambient_occupancy_strict,
-    ambient_occupancy_fast;
+    ambient_occupancy_fast, sweep_occupancy_strict, sweep_occupancy_fast;
 }  // namespace rtow
 
 namespace {
@@ -263,6 +264,14 @@ const QueryKind kAmbient = {
     }};
 static_assert(sizeof(rtow_surface_point_t) == 64 && sizeof(rtow_ambient_t) == 64 && sizeof(rtow_ambient_params_t) == 16,
               "the ambient query's records: four 16-byte loads, four 16-byte stores");
+// swept sphere (csrc/rtow_sweep.h): the closest-point query's contract with the sweep walks; one 80-byte record in and out
+const QueryKind kSweep = {
+    .count = "n", .n_bufs = 2,
+    .bufs = {{"query", true, 16, sizeof(rtow_sweep_t), false, false, &rtow_ctx::q_rays, nullptr},
+             {"hit", true, 16, sizeof(rtow_sweep_hit_t), false, true, &rtow_ctx::q_hits, &QueryArgs::hits}},
+    .walk = Walk::kPoint, .mapped = true, .brute_no_lds = true, RTOW_LAUNCHERS(sweep)};
+static_assert(sizeof(rtow_sweep_t) == 80 && sizeof(rtow_sweep_hit_t) == 80,
+              "the sweep query's records: five 16-byte loads, five 16-byte stores");
 // the camera stage (csrc/rtow_guides.h): the primaries of the resident camera — a kernel that reads the camera alone —
 // and the first-hit guide buffers
 const QueryKind kCameraRays = {
@@ -723,6 +732,18 @@ int rtow_ambient(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_ambi
   return guarded("rtow_ambient", [&] {
     return query_host(c, kAmbient, {precision, kernel, n, params ? params->samples : 0, params,
                                     {(void *)points, (void *)ids, out, rays_out}, nullptr, stats});
+  });
+}
+int rtow_sweep_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_queries, int64_t n, void *d_hits,
+                      void *hip_stream, rtow_stats_t *stats) {
+  return guarded("rtow_sweep_device", [&] {
+    return query_device(c, kSweep, {precision, kernel, n, 0, nullptr, {(void *)d_queries, d_hits}, hip_stream, stats});
+  });
+}
+int rtow_sweep(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_sweep_t *queries, int64_t n, rtow_sweep_hit_t *hits,
+               rtow_stats_t *stats) {
+  return guarded("rtow_sweep", [&] {
+    return query_host(c, kSweep, {precision, kernel, n, 0, nullptr, {(void *)queries, hits}, nullptr, stats});
   });
 }
 int rtow_camera_rays_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_rays, void *d_ids, void *hip_stream) {

@@ -170,6 +170,20 @@ class Ambient(C.Structure):
     _fields_ = [("open", C.c_double), ("bent", d3), ("sky", d3), ("samples", C.c_double)]
 
 
+class SweepQuery(C.Structure):
+    """rtow_sweep_t (80 B): a sphere of `radius` whose centre travels origin + direction * t, t in [0, tmax]."""
+    _fields_ = [("origin", d3), ("time", C.c_double), ("direction", d3), ("tmax", C.c_double),
+                ("radius", C.c_double), ("pad_", C.c_double)]
+
+
+class SweepHit(C.Structure):
+    """rtow_sweep_hit_t (80 B): t = dist = inf, centre = point = 0 and prim = kind = material = -1 on a miss."""
+    _fields_ = [
+        ("t", C.c_double), ("dist", C.c_double), ("centre", d3), ("point", d3),
+        ("prim", C.c_int32), ("kind", C.c_int32), ("material", C.c_int32), ("start_overlap", C.c_int32),
+    ]
+
+
 MAX_AMBIENT_SAMPLES = 65536  # RTOW_MAX_AMBIENT_SAMPLES: the most samples rtow_ambient takes per point
 
 
@@ -191,6 +205,26 @@ POINT_HIT_DTYPE = np.dtype([("dist", "<f8"), ("point", "<f8", (3,)), ("prim", "<
 # rtow_surface_point_t / rtow_ambient_t (rtow_ambient*)
 SURFACE_POINT_DTYPE = np.dtype([("point", "<f8", (3,)), ("time", "<f8"), ("normal", "<f8", (3,)), ("max_dist", "<f8")])
 AMBIENT_DTYPE = np.dtype([("open", "<f8"), ("bent", "<f8", (3,)), ("sky", "<f8", (3,)), ("samples", "<f8")])
+
+
+# rtow_sweep_t / rtow_sweep_hit_t (rtow_sweep*)
+SWEEP_QUERY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("time", "<f8"), ("direction", "<f8", (3,)), ("tmax", "<f8"),
+                              ("radius", "<f8"), ("pad_", "<f8")])
+SWEEP_HIT_DTYPE = np.dtype([("t", "<f8"), ("dist", "<f8"), ("centre", "<f8", (3,)), ("point", "<f8", (3,)),
+                            ("prim", "<i4"), ("kind", "<i4"), ("material", "<i4"), ("start_overlap", "<i4")])
+
+
+def make_sweeps(origins, directions, radius, time=0.0, tmax=float("inf")):
+    """A SWEEP_QUERY_DTYPE array from [n, 3] origins and directions (radius, time and tmax: scalars or [n])."""
+    o = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+    q = np.empty(len(o), dtype=SWEEP_QUERY_DTYPE)
+    q["origin"] = o
+    q["direction"] = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+    q["time"] = time
+    q["tmax"] = tmax
+    q["radius"] = radius
+    q["pad_"] = 0.0
+    return q
 
 
 def make_surface_points(points, normals, time=0.0, max_dist=float("inf")):
@@ -245,7 +279,7 @@ EXPORTS = [
     "rtow_camera_rays_device", "rtow_camera_rays", "rtow_camera_ray_count", "rtow_guides_device", "rtow_guides",
     "rtow_debug_last_spec", "rtow_first_hits_device", "rtow_first_hits", "rtow_nearest_device", "rtow_nearest",
     "rtow_debug_last_counted", "rtow_debug_walk_consts", "rtow_path_step_device", "rtow_path_step",
-    "rtow_ambient_device", "rtow_ambient",
+    "rtow_ambient_device", "rtow_ambient", "rtow_sweep_device", "rtow_sweep",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -363,6 +397,10 @@ def lib():
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rtow_ambient.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AmbientParams), C.c_void_p, C.c_int64,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    if hasattr(L, "rtow_sweep"):
+        L.rtow_sweep_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.POINTER(Stats)]
+        L.rtow_sweep.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Stats)]
     if hasattr(L, "rtow_guides"):
         L.rtow_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]
         L.rtow_camera_rays.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p]
@@ -836,6 +874,42 @@ class Context:
                                         C.c_void_p(d_ids) if d_ids else None, C.c_void_p(d_out),
                                         C.c_void_p(d_rays_out) if d_rays_out else None, C.c_void_p(stream),
                                         C.byref(st) if st is not None else None), "rtow_ambient_device")
+        return st
+
+    def sweep(self, queries, precision=F64_FAST, kernel=KERNEL_AUTO, want_stats=False):
+        """The first primitive a travelling sphere touches, for every sweep (rtow_sweep / rtow_sweep_device).  `queries`
+        is a SWEEP_QUERY_DTYPE array in host memory — the answer is a SWEEP_HIT_DTYPE array — or a torch device tensor
+        holding n 80-byte records (any dtype, contiguous, 16-byte aligned): the answer is then a uint8 [n, 80] tensor on
+        the same device, enqueued on torch's current stream (view it through SWEEP_HIT_DTYPE after .cpu().numpy()).
+        With `want_stats` also Stats."""
+        st = Stats() if want_stats else None
+        if hasattr(queries, "data_ptr"):  # a torch device tensor
+            import torch
+            if not queries.is_cuda or not queries.is_contiguous():
+                raise ValueError("a sweep tensor must be a contiguous device tensor")
+            nbytes = queries.numel() * queries.element_size()
+            if nbytes % SWEEP_QUERY_DTYPE.itemsize:
+                raise ValueError("a sweep tensor must hold whole 80-byte records")
+            n = nbytes // SWEEP_QUERY_DTYPE.itemsize
+            hits = torch.empty((n, SWEEP_HIT_DTYPE.itemsize), dtype=torch.uint8, device=queries.device)
+            stream = torch.cuda.current_stream(queries.device).cuda_stream
+            check(lib().rtow_sweep_device(self._h, precision, kernel, C.c_void_p(queries.data_ptr()), n,
+                                          C.c_void_p(hits.data_ptr()), C.c_void_p(stream),
+                                          C.byref(st) if st is not None else None), "rtow_sweep_device")
+            return (hits, st) if want_stats else hits
+        q = np.ascontiguousarray(queries, dtype=SWEEP_QUERY_DTYPE).reshape(-1)
+        hits = np.empty(len(q), dtype=SWEEP_HIT_DTYPE)
+        check(lib().rtow_sweep(self._h, precision, kernel, q.ctypes.data_as(C.c_void_p), len(q),
+                               hits.ctypes.data_as(C.c_void_p), C.byref(st) if st is not None else None), "rtow_sweep")
+        return (hits, st) if want_stats else hits
+
+    def sweep_device(self, d_q: int, n: int, d_hits: int, precision=F64_FAST, kernel=KERNEL_AUTO, stream: int = 0,
+                     want_stats=False):
+        """The same on raw device pointers (both 16-byte aligned: n x 80-byte queries, n x 80-byte hits), enqueued on
+        `stream` (rtow_sweep_device); returns Stats with `want_stats` (then synchronised), else None."""
+        st = Stats() if want_stats else None
+        check(lib().rtow_sweep_device(self._h, precision, kernel, C.c_void_p(d_q), n, C.c_void_p(d_hits),
+                                      C.c_void_p(stream), C.byref(st) if st is not None else None), "rtow_sweep_device")
         return st
 
     def camera_rays(self, cfg: Config):
