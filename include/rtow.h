@@ -748,9 +748,10 @@ int rtow_path_step(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_
  *              (1 - ambient occlusion), bent / |bent| the bent normal, sky / samples the irradiance of the sky over pi.
  *              A call with samples = k equals the in-order sum of k one-sample calls with sample_first + j, bit for bit
  *              in both builds; no result depends on the batch's shape or on scheduling.
- *   skipped    a point whose normal . normal is 0, NaN or infinite, or whose max_dist is NaN or below 0.001, does no walk:
- *              all eight doubles of its record are +0.0 (samples included), and its rays_out slots hold the dead ray of
- *              rtow_path_step (every field 0, tmax = -1).
+ *   skipped    a point whose normal . normal (in binary64) is 0, subnormal (below 2^-1022: a length under about 1.5e-154),
+ *              NaN or infinite (a length over about 1.3e154), or whose max_dist is NaN or below 0.001, does no walk: a
+ *              subnormal normal . normal has too few bits left to normalise by.  All eight doubles of its record are +0.0
+ *              (samples included), and its rays_out slots hold the dead ray of rtow_path_step (every field 0, tmax = -1).
  *   d_rays_out optional (NULL: nothing is exported): rtow_ray_t[n][samples], point-major — exactly the rays the walks took
  *              (origin = point, direction = d, time, tmax = max_dist).  rtow_occluded on them and the sums above ARE the
  *              record; a caller can also reuse the directions.
@@ -776,7 +777,7 @@ int rtow_path_step(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_
 typedef struct rtow_surface_point_t { /* 64 B, 16-byte aligned: the layout of rtow_ray_t */
   double point[3];
   double time;      /* shutter time of the moving spheres, as in the ray queries */
-  double normal[3]; /* need not be unit length */
+  double normal[3]; /* need not be unit length (a length outside [1.5e-154, 1.3e154] is skipped) */
   double max_dist;  /* occluders count within [0.001, max_dist]; +inf: unbounded */
 } rtow_surface_point_t;
 

@@ -14,6 +14,7 @@
 //   disk    (px, py) = lens_from_block(block)                                      rtow_trace_rng.h: uniform on the disk
 //   height  pz = sqrt(max(1 - (px * px + py * py), 0))                             (the clamp: px^2 + py^2 reaches 1 + 1.3e-8)
 //   normal  nn = (N.x * N.x + N.y * N.y) + N.z * N.z  (dot);  len = sqrt(nn);  n = (N.x / len, N.y / len, N.z / len)
+//           (nn is a normal binary64, 2^-1022 <= nn < inf, or the point is skipped: a subnormal nn has too few bits)
 //   frame   s = copysign(1, n.z);  a = -1 / (s + n.z);  c = (n.x * n.y) * a        (Duff et al., "Building an orthonormal
 //           t = (1 + ((s * n.x) * n.x) * a,  s * c,  -(s * n.x))                    basis, revisited", JCGT 6(1), 2017)
 //           b = (c,  s + ((n.y * n.y) * a),  -n.y)
@@ -124,13 +125,15 @@ __global__ void __launch_bounds__(KERNEL >= 2 && KERNEL <= 4 ? 1024 : 256)
         pixel = id.x;
         sample = id.y + Q.sample_first;
       }
-      // a skipped point: normal . normal is 0, NaN or infinite, or the interval [0.001, max_dist] is empty (NaN included)
+      // a skipped point: normal . normal is 0, subnormal, NaN or infinite, or the interval [0.001, max_dist] is empty
+      // (NaN included).  A subnormal nn has lost bits to underflow and n = N / sqrt(nn) is no unit vector (a length of
+      // 1e-160 gives |d| - 1 = 5e-4); from 2^-1022 on, products that underflow cost nn at most 3 * 2^-1075 / 2^-1022 = 3 u.
       V3 po, nrm;
       real ptime;
       double tmax;
       load_ray(Q.points, i, po, nrm, ptime, tmax);  // (rtow_surface_point_t has the layout of rtow_ray_t)
       const real nn = dot(nrm, nrm);
-      active = nn > real(0.0) && nn < (real)__builtin_huge_val() && tmax >= RTOW_TMIN;
+      active = nn >= real(0x1p-1022) && nn < (real)__builtin_huge_val() && tmax >= RTOW_TMIN;
     }
 
     // Across a walk the lane keeps its seven sums and the sample's direction, nothing else of the point: the record (64

@@ -53,11 +53,12 @@ def disk_points(seed, pixel, sample):
 
 
 def skipped(points):
-    """The points that do no walk: normal . normal is 0, NaN or infinite, or max_dist is NaN or below 0.001."""
+    """The points that do no walk: normal . normal is 0, subnormal (below 2^-1022), NaN or infinite, or max_dist is NaN
+    or below 0.001."""
     N = points["normal"]
     with np.errstate(all="ignore"):
         nn = (N[:, 0] * N[:, 0] + N[:, 1] * N[:, 1]) + N[:, 2] * N[:, 2]
-        return ~((nn > 0.0) & (nn < np.inf) & (points["max_dist"] >= TMIN))
+        return ~((nn >= 2.0 ** -1022) & (nn < np.inf) & (points["max_dist"] >= TMIN))
 
 
 def unit_normal(N):

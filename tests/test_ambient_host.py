@@ -106,6 +106,13 @@ def test_mirror_skips_and_folds():
                                                       [0, 1, 0], [0, 1, 0]],
                                    max_dist=[1.0, 1.0, 1.0, 1.0, math.nan, 0.0009, -1.0])
     assert ambient_ref.skipped(pts).tolist() == [False] + [True] * 6
+    # a subnormal normal . normal (lengths 1e-155 to 1e-161) is skipped; 2e-154, whose square is a normal binary64, is live
+    small = rtow.make_surface_points(np.zeros((6, 3)), [[1e-155, 0, 0], [0, -1e-158, 0], [0, 0, 1e-160], [-1e-161, 0, 0],
+                                                        [0, 2e-154, 0], [2.0 ** -511, 0, 0]])
+    assert ambient_ref.skipped(small).tolist() == [True] * 4 + [False] * 2
+    rs = ambient_ref.rays(small, 3, seed=4)
+    assert np.all(rs["tmax"][:4] == -1.0) and not rs["direction"][:4].any()
+    assert np.abs(np.sqrt((rs["direction"][4:] ** 2).sum(axis=2)) - 1.0).max() <= 2e-8
     r = ambient_ref.rays(pts, 3, seed=4)
     assert np.all(r["tmax"][1:] == -1.0) and np.all(r["tmax"][0] == 1.0)
     dead = r[1:].copy()

@@ -14,6 +14,7 @@ import pytest
 
 import ambient_ref
 import rtow
+from ambient_cases import handmade_points, scene_extent
 from support_fixtures import big_mesh, logged  # noqa: F401
 from support_oracle import FAST_CASES, LOGGED, rays_of
 from support_scenes import SceneView, handmade_scene
@@ -32,20 +33,6 @@ def actx():
     c.close()
 
 
-def scene_extent(view):
-    """Largest side of the box of the scene's small primitives (not the cover scene's ground sphere)."""
-    pts = []
-    small = view.sph[np.abs(view.sph[:, 3]) < 100.0]
-    if len(small):
-        pts += [small[:, :3] - np.abs(small[:, 3:4]), small[:, :3] + np.abs(small[:, 3:4])]
-    if len(view.mov):
-        pts += [view.mov[:, 0:3] - view.mov[:, 6:7], view.mov[:, 3:6] + view.mov[:, 6:7]]
-    if len(view.tri):
-        pts.append(view.tri.reshape(-1, 3))
-    pts = np.concatenate(pts)
-    return float(np.max(pts.max(0) - pts.min(0)))
-
-
 def points_of_log(ctx, view, log, n, seed):
     """Hit points and hit normals of logged rays (strict closest hit on the resident scene) at the log's times: half with
     max_dist = 5 % of the scene's extent, half unbounded."""
@@ -55,32 +42,6 @@ def points_of_log(ctx, view, log, n, seed):
     idx = np.sort(g.choice(ok, size=min(n, len(ok)), replace=False))
     md = np.where(g.random(len(idx)) < 0.5, 0.05 * scene_extent(view), math.inf)
     return rtow.make_surface_points(hits["point"][idx], hits["normal"][idx], time=log[idx, 9], max_dist=md)
-
-
-def handmade_points():
-    """About 200 hand-placed points of handmade_scene(): inside the hollow glass sphere, on the triangles' front and back,
-    on the ground, and normals along the axes with signed zeros."""
-    g = np.random.default_rng(9)
-    p, nrm, md = [], [], []
-    for _ in range(60):  # inside the negative-radius sphere (centre (0, 1, 0), r = 0.8): the shell is all around
-        u = g.normal(size=3)
-        p.append(np.array([0, 1, 0]) + 0.5 * u / np.linalg.norm(u)), nrm.append(g.normal(size=3)), md.append(
-            g.choice([0.2, 0.4, math.inf]))
-    for _ in range(40):  # on the first triangle (z = -2), front and back, and on the second (z = -3)
-        a, b = sorted(g.random(2))
-        q = np.array([-1, 0, -2]) * a + np.array([1, 0, -2]) * (b - a) + np.array([0, 2, -2]) * (1 - b)
-        for nz in (1.0, -1.0):
-            p.append(q), nrm.append([0.0, -0.0, nz]), md.append(g.choice([1.5, math.inf]))
-    axes = [(1, 0.0, 0.0), (-1, 0.0, -0.0), (0.0, 1, -0.0), (-0.0, -1, 0.0), (0.0, -0.0, 1), (-0.0, 0.0, -1), (-0.0, -0.0, 1),
-            (0.0, 0.0, -1)]
-    for origin in ([0, 1e-9, 3], [2, 0.5, 1], [-3, 2.5, 0.5], [0.3, 0.9, 0.2], [3, 1, 4], [0, 3, 0], [0, 0.5, -1.5]):
-        for ax in axes:
-            p.append(origin), nrm.append(ax), md.append(g.choice([0.8, 4.0, math.inf]))
-    time = g.choice([0.0, 0.5, 1.0], size=len(p))
-    pts = rtow.make_surface_points(np.array(p, dtype=np.float64), np.array(nrm, dtype=np.float64), time=time,
-                                   max_dist=np.array(md))
-    assert np.signbit(pts["normal"]).any() and 190 <= len(pts) <= 210
-    return pts
 
 
 @pytest.fixture(scope="module")
@@ -198,10 +159,14 @@ def test_skipped_points_give_zero_records_and_leave_their_neighbours_alone(actx,
     scene, view, pts, ids = cases["cover_static"]
     upload(actx, scene)
     good, ids = pts[:130].copy(), ids[:130]
+    good[71]["normal"] = [0.0, 2e-154, 0.0]  # (live: its squared length, 4e-308, is a normal binary64)
     bad = good.copy()
     where = {0: ("normal", [0.0, 0.0, 0.0]), 5: ("normal", [math.nan, 1.0, 0.0]), 63: ("normal", [0.0, math.inf, 0.0]),
              64: ("max_dist", math.nan), 100: ("max_dist", 0.0009), 129: ("max_dist", -1.0), 7: ("normal", [0.0, -0.0, 0.0]),
-             65: ("normal", [1e200, 0.0, 0.0]), 66: ("normal", [1e-200, 0.0, 0.0])}
+             65: ("normal", [1e200, 0.0, 0.0]), 66: ("normal", [1e-200, 0.0, 0.0]),
+             # a subnormal normal . normal: too few bits to normalise by
+             67: ("normal", [1e-155, 0.0, 0.0]), 68: ("normal", [0.0, -1e-158, 0.0]), 69: ("normal", [0.0, 0.0, 1e-160]),
+             70: ("normal", [-1e-161, 0.0, 0.0])}
     for i, (field, value) in where.items():
         bad[i][field] = value
     skip = np.zeros(len(bad), dtype=bool)
@@ -217,6 +182,7 @@ def test_skipped_points_give_zero_records_and_leave_their_neighbours_alone(actx,
         dead["tmax"] = 0.0
         assert not dead.view(np.uint8).any(), kn
         assert np.all(out["samples"][~skip] == 3.0)
+        assert np.abs(np.sqrt((rays["direction"][71] ** 2).sum(axis=1)) - 1.0).max() <= 2e-8, kn
 
 
 # ---------------------------------------------------------------------------------------------- 4. fast build ---
