@@ -824,18 +824,26 @@ int rtow_ambient(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_am
  *   start overlap  (all primitives) the formulas of rtow_closest_point at o give a distance <= rho: t = 0 and
  *                  start_overlap = 1.  In the strict build start_overlap == 1 exactly when strict
  *                  rtow_closest_point(o, time, max_dist = rho) reports a hit.
- *   sphere         otherwise, with oc = o - c, L2 = oc.oc, h = oc.d: outside (L2 > (R + rho)^2) the near root of
+ *                  Otherwise no piece asks again whether the sweep starts outside it: over the reals the failed
+ *                  overlap test says so, and a second test in other arithmetic would disagree with it on a shell a few
+ *                  ulps thick — exactly where a sweep starts that continues from the centre of an earlier contact.  Every
+ *                  near root is clamped at 0 instead: a start that a piece's own arithmetic puts inside it answers t = 0
+ *                  with start_overlap = 0, a contact at rho within the band like any other.
+ *   sphere         with oc = o - c, L2 = oc.oc, h = oc.d: from the outer side (L2 >= |r^2|) the near root of
  *                  |p - c| = R + rho, a hit iff the perpendicular is no longer than R + rho and h < 0 — a tangent pass
- *                  touches: the contact set is closed; inside (L2 < (R - rho)^2, R > rho) the far root of |p - c| = R - rho.
- *   triangle       otherwise, the minimum over the accepted candidates of the pieces of the Minkowski sum:
- *                  face — only when n.n > 0, the centre starts outside the slab |n.(o - a)| > rho |n| and approaches the
- *                    plane: where the centre reaches the offset plane on its own side, accepted when the Gram-form
- *                    barycentrics of p(t) - a lie inside (sn, tn in [0, n.n], sn + tn <= n.n, as in rtow_closest_point);
+ *                  touches: the contact set is closed; from the inner side (L2 < |r^2|, hence R > rho) the far root of
+ *                  |p - c| = R - rho, which exists for every direction (a negative term under its root is rounding: 0).
+ *   triangle       the minimum over the accepted candidates of the pieces of the Minkowski sum:
+ *                  face — only when n.n > 0 and the centre approaches the plane: where the centre reaches the offset plane
+ *                    on its own side, t = max(|n.(o - a)| - rho |n|, 0) / |n.d|, accepted when the Gram-form barycentrics
+ *                    of p(t) - a lie inside (sn, tn in [0, n.n], sn + tn <= n.n, as in rtow_closest_point);
  *                  three edges — for each edge with e.e > 0 the near root of the infinite cylinder of radius rho about the
- *                    edge line, accepted when the sweep starts outside that cylinder, approaches its axis and the axial
- *                    parameter at contact lies in [0, e.e];
- *                  three vertices — the near root of the sphere of radius rho about each vertex, when the sweep starts
- *                    outside it and approaches.
+ *                    edge line, accepted when the sweep approaches its axis and the axial parameter at contact lies in
+ *                    [0, e.e];
+ *                  three vertices — the near root of the sphere of radius rho about each vertex, when the sweep
+ *                    approaches it.
+ *                  (A start inside a piece that the overlap test did not see lies beyond a cap or beside the prism, where
+ *                  the axial or barycentric test rejects it, or in the shell.)
  *                  Exact over the reals: the sum is the union of a prism and three capsules; the first entry into a union
  *                  is the minimum of the first entries into its convex parts; a lateral entry into the prism, or an entry
  *                  through a cylinder cap, lies inside a capsule or a vertex sphere; every accepted candidate is a point

@@ -16,14 +16,23 @@
 //
 // Per primitive (sweep_sphere, sweep_triangle):
 //   * start overlap: point_sphere / point_triangle at o gives a distance <= rho: t = 0 and the overlap flag;
-//   * sphere otherwise, R = sqrt(|r^2|): outside (w.w > (R + rho)^2) the near root of |p - c| = R + rho if the centre
-//     approaches (h < 0) and the perpendicular is short enough (r^2 - q.q >= 0: a tangent pass touches); inside
-//     (w.w < (R - rho)^2, R > rho) the far root of |p - c| = R - rho;
-//   * triangle otherwise, the minimum of: the face (n.n > 0, the centre outside the slab and approaching: where it
-//     reaches the offset plane on its side, if the Gram-form barycentrics of that point lie inside), the three edges
-//     (e.e > 0: the near root of the cylinder of radius rho about the edge line in the plane across the edge, if the
-//     sweep starts outside it, approaches and the axial parameter at contact lies in [0, e.e]) and the three vertices
-//     (the near root of the sphere of radius rho, if the sweep starts outside it and approaches).
+//   * otherwise NO piece asks again whether the sweep starts outside it.  Over the reals a failed overlap test implies
+//     it; in binary64 the overlap test (a rounded distance against rho) and a second test (rounded squares against
+//     rho^2, (R +- rho)^2) disagree on a shell a few ulps thick, and a sweep that starts there — one that continues
+//     from the centre of an earlier contact — would belong to neither branch and pass through the primitive it rests
+//     on.  Instead every near root is clamped at 0 (sweep_root), so a start that a piece's own arithmetic puts inside
+//     it answers t = 0 (without the overlap flag: the contact is at rho within the band);
+//   * sphere, R = sqrt(|r^2|): from the outer side (w.w >= |r^2|) the near root of |p - c| = R + rho if the centre
+//     approaches (h < 0) and the perpendicular is short enough (r^2 - q.q >= 0: a tangent pass touches); from the
+//     inner side (w.w < |r^2|, which with no overlap means R > rho) the far root of |p - c| = R - rho, which exists
+//     for every direction: a negative r^2 - q.q there is rounding and counts as 0;
+//   * triangle, the minimum of: the face (n.n > 0, the centre approaching the plane: where it reaches the offset
+//     plane on its side — at once when it starts within the slab — if the Gram-form barycentrics of that point lie
+//     inside), the three edges (e.e > 0: the near root of the cylinder of radius rho about the edge line in the plane
+//     across the edge, if the sweep approaches the axis and the axial parameter at contact lies in [0, e.e]) and the
+//     three vertices (the near root of the sphere of radius rho, if the sweep approaches).  A start inside a piece
+//     that the overlap test did not see lies outside the triangle's own region of that piece (beyond a cap, beside the
+//     prism), where the axial or barycentric test rejects it, or in the shell.
 // A candidate whose terms overflow or are NaN fails a comparison and is no candidate: no NaN leaves these functions for
 // a finite query, and +inf means "none".
 //
@@ -45,12 +54,14 @@ struct SweepRay {
 constexpr double kNoSweep = __builtin_huge_val();
 
 // The near (FAR: far) root of |w + d t| = r given h = w.d and inv_a = 1 / d.d, clamped to t >= 0; +inf when the line
-// passes farther than r.
+// passes farther than r.  The far root is asked for from inside the ball only, where the line cannot pass farther: a
+// negative r^2 - q.q is then 0 (a NaN stays one and is no candidate).
 template <bool FAR>
 __device__ __forceinline__ double sweep_root(V3d w, V3d d, double h, double inv_a, double r) {
   const double t0 = -(h * inv_a);
   const V3d q = w + d * t0;
-  const double dd = r * r - dot(q, q);
+  double dd = r * r - dot(q, q);
+  if (FAR && dd < 0.0) dd = 0.0;
   if (!(dd >= 0.0)) return kNoSweep;
   const double s = pq_sqrt(dd * inv_a);
   const double t = FAR ? t0 + s : t0 - s;
@@ -65,29 +76,28 @@ __device__ __forceinline__ double sweep_sphere(const SweepRay &r, double cx, dou
   const V3d w = {r.o.x - cx, r.o.y - cy, r.o.z - cz};
   const double L2 = dot(w, w), h = dot(w, r.d);
   const double ro = R + r.rho, ri = R - r.rho;
-  if (L2 > ro * ro) return h < 0.0 ? sweep_root<false>(w, r.d, h, r.inv_a, ro) : kNoSweep;
-  if (ri > 0.0 && L2 < ri * ri) return sweep_root<true>(w, r.d, h, r.inv_a, ri);
-  return kNoSweep;
+  if (L2 < fabs(r2)) return ri > 0.0 ? sweep_root<true>(w, r.d, h, r.inv_a, ri) : kNoSweep;
+  return h < 0.0 ? sweep_root<false>(w, r.d, h, r.inv_a, ro) : kNoSweep;
 }
 
 // The sphere of radius rho about a vertex, w = o - vertex.
-__device__ __forceinline__ double sweep_vertex(const SweepRay &r, V3d w, double rr) {
-  const double L2 = dot(w, w), h = dot(w, r.d);
-  if (!(L2 > rr && h < 0.0)) return kNoSweep;
+__device__ __forceinline__ double sweep_vertex(const SweepRay &r, V3d w) {
+  const double h = dot(w, r.d);
+  if (!(h < 0.0)) return kNoSweep;
   return sweep_root<false>(w, r.d, h, r.inv_a, r.rho);
 }
 
 // The cylinder of radius rho about the line of edge e, w = o - (the edge's first vertex): the sweep and the origin are
 // projected across the edge (wp, dp: one rounding of |w|, |d| per component, so a nearly parallel sweep keeps a
 // leading coefficient dp.dp with a small RELATIVE error), the root is taken there.
-__device__ __forceinline__ double sweep_edge(const SweepRay &r, V3d w, V3d e, double rr) {
+__device__ __forceinline__ double sweep_edge(const SweepRay &r, V3d w, V3d e) {
   const double ee = dot(e, e);
   if (!(ee > 0.0)) return kNoSweep;
   const double ie = pq_div(1.0, ee);
   const double we = dot(w, e), de = dot(r.d, e);
   const V3d wp = w - e * (we * ie), dp = r.d - e * (de * ie);
   const double A = dot(dp, dp), h = dot(wp, dp);
-  if (!(A > 0.0 && h < 0.0 && dot(wp, wp) > rr)) return kNoSweep;
+  if (!(A > 0.0 && h < 0.0)) return kNoSweep;
   const double t = sweep_root<false>(wp, dp, h, pq_div(1.0, A), r.rho);
   const double ax = we + de * t;  // the axial parameter at contact, times e.e
   return (ax >= 0.0 && ax <= ee) ? t : kNoSweep;
@@ -99,15 +109,14 @@ __device__ __forceinline__ double sweep_triangle(const SweepRay &r, V3d a, V3d e
   ov = point_triangle<false, SERIAL>(r.o, a, e1, e2, n, q) <= r.rho;
   if (ov) return 0.0;
   const V3d w = r.o - a;
-  const double rr = r.rho * r.rho;
   double best = kNoSweep;
   candidate_fence<SERIAL>();
   const double nn = dot(n, n);
   if (nn > 0.0) {  // the face
     const double wn = dot(n, w), dn = dot(n, r.d);
     const double num = fabs(wn) - r.rho * pq_sqrt(nn);
-    if (num > 0.0 && (wn > 0.0 ? dn < 0.0 : dn > 0.0)) {
-      const double t = pq_div(num, fabs(dn));
+    if (wn > 0.0 ? dn < 0.0 : dn > 0.0) {  // (a start within the slab reaches its offset plane at once)
+      const double t = pq_div(num <= 0.0 ? 0.0 : num, fabs(dn));
       const V3d p = w + r.d * t;
       const double d1 = dot(p, e1), d2 = dot(p, e2);
       const double ee1 = dot(e1, e1), ee2 = dot(e2, e2), e12 = dot(e1, e2);
@@ -116,18 +125,18 @@ __device__ __forceinline__ double sweep_triangle(const SweepRay &r, V3d a, V3d e
     }
   }
   candidate_fence<SERIAL>();
-  best = fmin(best, sweep_edge(r, w, e1, rr));
+  best = fmin(best, sweep_edge(r, w, e1));
   candidate_fence<SERIAL>();
-  best = fmin(best, sweep_edge(r, w, e2, rr));
+  best = fmin(best, sweep_edge(r, w, e2));
   candidate_fence<SERIAL>();
-  best = fmin(best, sweep_vertex(r, w, rr));
+  best = fmin(best, sweep_vertex(r, w));
   candidate_fence<SERIAL>();
   const V3d g = w - e1;
-  best = fmin(best, sweep_edge(r, g, e2 - e1, rr));
+  best = fmin(best, sweep_edge(r, g, e2 - e1));
   candidate_fence<SERIAL>();
-  best = fmin(best, sweep_vertex(r, g, rr));
+  best = fmin(best, sweep_vertex(r, g));
   candidate_fence<SERIAL>();
-  best = fmin(best, sweep_vertex(r, w - e2, rr));
+  best = fmin(best, sweep_vertex(r, w - e2));
   return best;
 }
 

@@ -17,10 +17,11 @@ min(|m - R|, |M - R|); roots by the 130-bit isqrt.  A vectorised binary64 filter
 (`segdist_f64`: the same geometry in floating point; its error is below FILTER_U u S, see there) and only pairs within
 the band plus that bound of rho go to Fraction.
 
-(c) check_answers(rec, mats, sweeps, hits, prec): every query, no sampling, finite tmax.  A hit at t <= tmax (bitwise) on
+(c) check_answers(rec, mats, sweeps, hits, prec): every query, no sampling.  A hit at t <= tmax (bitwise) on
 c*: |D_exact(centre, c*) - rho| <= band (a start overlap: t == 0 and D_exact(o, c*) <= rho + band); dist and point meet
 point_ref's two point clauses at centre; for every primitive c segdist_exact(o, centre, c) >= rho - band(c).  A miss:
-segdist_exact(o, p(tmax), c) >= rho - band(c) for every c.  Where a primitive's segment distance is within its band of
+segdist_exact(o, p(tmax), c) >= rho - band(c) for every c — with tmax = +inf over [o, p(T)], T the smallest power of two
+at which the sweep has provably left the scene for good (Checker.horizon).  Where a primitive's segment distance is within its band of
 rho either answer is allowed (`open` counts those queries: a miss with such a primitive, a hit that grazed such a primitive
 on the way — one that is at rho from the hit's centre as well, across a shared edge or vertex, ties at the same t and
 leaves nothing open).  Also: the miss record, skipped queries, kind / material of
@@ -38,8 +39,10 @@ u S (a rounding of a quantity of magnitude <= S contributes <= u S to the positi
     about 14 on magnitudes <= S, and its own 1 / A: 28 in all, plus the axial test, which only selects;
   * the face: n.w and n.d: 5 each, sqrt(n.n): 1 (+5 halved), rho |n|: 1, the difference: 1, the quotient: 1: 17;
   * centre = o + d t: 2 per component, in every case.
+(A start that a piece's arithmetic puts inside it answers t = 0: no new path, the clamp of sweep_root and max(num, 0).)
 So K_strict = 32 would cover the longest path; the measured worst of the mirror against (b) over all the sets of
-test_sweep_host.py is printed there (0.98 u S) and 48 >= 4 x that, which leaves room for inputs outside the sets:
+test_sweep_host.py is printed there (1.24 u S, on the unbounded rows) and 48 >= 4 x that, which leaves room for inputs
+outside the sets:
 K_STRICT = 48, K_FAST = 2 K_STRICT = 96 (the project's allowance for contraction and the 4e-15 of the fast reciprocal
 and root).
 """
@@ -84,18 +87,28 @@ def skipped(q):
 _dot = pr._dot
 
 
-def _root(w, d, h, inv_a, r, far):
-    """sweep_root: the near (far) root of |w + d t| = r, clamped to t >= 0; +inf for none."""
+GUARDS = ("outer", "inner", "vertex", "edge", "face")
+"""The "starts outside this piece" tests of the rule before the present one, by piece.  They repeated the overlap test
+in other arithmetic (rounded squares against rho^2 and (R +- rho)^2, not a rounded distance against rho), and a start
+a few ulps from contact could fail both and belong to no branch.  `old` (a set of these names) puts a guard back into
+the mirror, one piece at a time: the mutants of test_sweep_host.py, each of which the exact checker must refuse."""
+
+
+def _root(w, d, h, inv_a, r, far, clamp=False):
+    """sweep_root: the near (far) root of |w + d t| = r, clamped to t >= 0; +inf for none.  clamp: a negative
+    r^2 - q.q counts as 0 (the kernel's far root)."""
     t0 = -(h * inv_a)
     qx, qy, qz = w[0] + d[0] * t0, w[1] + d[1] * t0, w[2] + d[2] * t0
     dd = r * r - _dot(qx, qy, qz, qx, qy, qz)
+    if clamp:
+        dd = np.where(dd < 0.0, 0.0, dd)
     ok = dd >= 0.0
     s = np.sqrt(np.where(ok, dd * inv_a, 0.0))
     t = t0 + s if far else t0 - s
     return np.where(ok, np.where(t > 0.0, t, np.where(t <= 0.0, 0.0, np.inf)), np.inf)
 
 
-def sphere_sweep(o, d, inv_a, rho, cx, cy, cz, r2):
+def sphere_sweep(o, d, inv_a, rho, cx, cy, cz, r2, old=()):
     """sweep_sphere: (t, start overlap), broadcast over the arguments (o, d: tuples of three arrays)."""
     with np.errstate(all="ignore"):
         ov = pr.sphere_point(o[0], o[1], o[2], cx, cy, cz, r2)[0] <= rho
@@ -103,20 +116,26 @@ def sphere_sweep(o, d, inv_a, rho, cx, cy, cz, r2):
         w = (o[0] - cx, o[1] - cy, o[2] - cz)
         L2, h = _dot(*w, *w), _dot(*w, *d)
         ro, ri = R + rho, R - rho
-        outside = L2 > ro * ro
-        inside = (ri > 0.0) & (L2 < ri * ri)
         t_out = np.where(h < 0.0, _root(w, d, h, inv_a, ro, False), np.inf)
-        t_in = _root(w, d, h, inv_a, ri, True)
-        t = np.where(outside, t_out, np.where(inside, t_in, np.inf))
+        if "outer" in old:
+            t_out = np.where(L2 > ro * ro, t_out, np.inf)
+        if "inner" in old:
+            t_in = np.where((ri > 0.0) & (L2 < ri * ri), _root(w, d, h, inv_a, ri, True), np.inf)
+        else:
+            t_in = np.where(ri > 0.0, _root(w, d, h, inv_a, ri, True, clamp=True), np.inf)
+        t = np.where(L2 < np.abs(r2), t_in, t_out)
         return np.where(ov, 0.0, t), ov
 
 
-def _vertex(w, d, inv_a, rho, rr):
-    L2, h = _dot(*w, *w), _dot(*w, *d)
-    return np.where((L2 > rr) & (h < 0.0), _root(w, d, h, inv_a, rho, False), np.inf)
+def _vertex(w, d, inv_a, rho, old):
+    h = _dot(*w, *d)
+    ok = h < 0.0
+    if "vertex" in old:
+        ok = (_dot(*w, *w) > rho * rho) & ok
+    return np.where(ok, _root(w, d, h, inv_a, rho, False), np.inf)
 
 
-def _edge(w, d, e, rho, rr):
+def _edge(w, d, e, rho, old):
     ee = _dot(*e, *e)
     pos = ee > 0.0
     ie = 1.0 / np.where(pos, ee, 1.0)
@@ -125,13 +144,15 @@ def _edge(w, d, e, rho, rr):
     wp = (w[0] - e[0] * sw, w[1] - e[1] * sw, w[2] - e[2] * sw)
     dp = (d[0] - e[0] * sd, d[1] - e[1] * sd, d[2] - e[2] * sd)
     A, h = _dot(*dp, *dp), _dot(*wp, *dp)
-    ok = pos & (A > 0.0) & (h < 0.0) & (_dot(*wp, *wp) > rr)
+    ok = pos & (A > 0.0) & (h < 0.0)
+    if "edge" in old:
+        ok &= _dot(*wp, *wp) > rho * rho
     t = _root(wp, dp, h, 1.0 / np.where(ok, A, 1.0), rho, False)
     ax = we + de * t
     return np.where(ok & (ax >= 0.0) & (ax <= ee), t, np.inf)
 
 
-def triangle_sweep(o, d, inv_a, rho, t):
+def triangle_sweep(o, d, inv_a, rho, t, old=()):
     """sweep_triangle on records t[..., 12]: (t, start overlap), broadcast over the arguments."""
     a = (t[..., 0], t[..., 1], t[..., 2])
     e1 = (t[..., 3], t[..., 4], t[..., 5])
@@ -140,26 +161,27 @@ def triangle_sweep(o, d, inv_a, rho, t):
     with np.errstate(all="ignore"):
         ov = pr.triangle_point(o[0], o[1], o[2], t)[0] <= rho
         w = (o[0] - a[0], o[1] - a[1], o[2] - a[2])
-        rr = rho * rho
         nn = _dot(*n, *n)
         wn, dn = _dot(*n, *w), _dot(*n, *d)
         num = np.abs(wn) - rho * np.sqrt(nn)
-        face = (nn > 0.0) & (num > 0.0) & np.where(wn > 0.0, dn < 0.0, dn > 0.0)
-        tf = num / np.where(face, np.abs(dn), 1.0)
+        face = (nn > 0.0) & np.where(wn > 0.0, dn < 0.0, dn > 0.0)
+        if "face" in old:
+            face &= num > 0.0
+        tf = np.where(num <= 0.0, 0.0, num) / np.where(face, np.abs(dn), 1.0)
         p = (w[0] + d[0] * tf, w[1] + d[1] * tf, w[2] + d[2] * tf)
         d1, d2 = _dot(*p, *e1), _dot(*p, *e2)
         ee1, ee2, e12 = _dot(*e1, *e1), _dot(*e2, *e2), _dot(*e1, *e2)
         sn, tn = ee2 * d1 - e12 * d2, ee1 * d2 - e12 * d1
         face &= (sn >= 0.0) & (tn >= 0.0) & (sn + tn <= nn) & (tf < np.inf)
         best = np.where(face, tf, np.inf)
-        best = np.fmin(best, _edge(w, d, e1, rho, rr))
-        best = np.fmin(best, _edge(w, d, e2, rho, rr))
-        best = np.fmin(best, _vertex(w, d, inv_a, rho, rr))
+        best = np.fmin(best, _edge(w, d, e1, rho, old))
+        best = np.fmin(best, _edge(w, d, e2, rho, old))
+        best = np.fmin(best, _vertex(w, d, inv_a, rho, old))
         g = (w[0] - e1[0], w[1] - e1[1], w[2] - e1[2])
         f = (e2[0] - e1[0], e2[1] - e1[1], e2[2] - e1[2])
-        best = np.fmin(best, _edge(g, d, f, rho, rr))
-        best = np.fmin(best, _vertex(g, d, inv_a, rho, rr))
-        best = np.fmin(best, _vertex((w[0] - e2[0], w[1] - e2[1], w[2] - e2[2]), d, inv_a, rho, rr))
+        best = np.fmin(best, _edge(g, d, f, rho, old))
+        best = np.fmin(best, _vertex(g, d, inv_a, rho, old))
+        best = np.fmin(best, _vertex((w[0] - e2[0], w[1] - e2[1], w[2] - e2[2]), d, inv_a, rho, old))
         return np.where(ov, 0.0, best), ov
 
 
@@ -221,7 +243,7 @@ def _tri_pairs(rec, q, rows, boxes):
     return a, order[b]
 
 
-def pair_times(rec, q, prefilter=True):
+def pair_times(rec, q, prefilter=True, old=()):
     """Mirror t and start-overlap flag of every (query, primitive) pair that can matter: (qi, cid, t, ov) — all pairs
     of the spheres, the preselected ones of the triangles; skipped queries have none."""
     rows = np.nonzero(~skipped(q))[0]
@@ -237,12 +259,13 @@ def pair_times(rec, q, prefilter=True):
     if rec.ns and len(rows):
         qi, ci = np.repeat(rows, rec.ns), np.tile(np.arange(rec.ns), len(rows))
         g = rec.sph[ci]
-        t, ov = sphere_sweep(*args(qi), g[:, 0], g[:, 1], g[:, 2], g[:, 3])
+        t, ov = sphere_sweep(*args(qi), g[:, 0], g[:, 1], g[:, 2], g[:, 3], old)
         parts.append((qi, ci, t, ov))
     if rec.nm and len(rows):
         qi, ci = np.repeat(rows, rec.nm), np.tile(np.arange(rec.nm), len(rows))
         g, tm = rec.mov[ci], q["time"][qi]
-        t, ov = sphere_sweep(*args(qi), g[:, 0] + tm * g[:, 3], g[:, 1] + tm * g[:, 4], g[:, 2] + tm * g[:, 5], g[:, 6])
+        t, ov = sphere_sweep(*args(qi), g[:, 0] + tm * g[:, 3], g[:, 1] + tm * g[:, 4], g[:, 2] + tm * g[:, 5], g[:, 6],
+                             old)
         parts.append((qi, rec.ns + ci, t, ov))
     if rec.nt and len(rows):
         if prefilter:
@@ -252,7 +275,7 @@ def pair_times(rec, q, prefilter=True):
         ts, ovs = [], []
         for i0 in range(0, len(qi), 1 << 18):
             sl = slice(i0, i0 + (1 << 18))
-            t, ov = triangle_sweep(*args(qi[sl]), rec.tri[ci[sl]])
+            t, ov = triangle_sweep(*args(qi[sl]), rec.tri[ci[sl]], old)
             ts.append(t), ovs.append(ov)
         if ts:
             parts.append((qi, rec.ns + rec.nm + ci, np.concatenate(ts), np.concatenate(ovs)))
@@ -262,12 +285,13 @@ def pair_times(rec, q, prefilter=True):
     return tuple(np.concatenate([p[k] for p in parts]) for k in range(4))
 
 
-def answers(rec, mats, q, prefilter=True):
-    """The mirror's answer records (HIT_DTYPE): the minimum by (t, insertion index) over the accepted pairs."""
+def answers(rec, mats, q, prefilter=True, old=()):
+    """The mirror's answer records (HIT_DTYPE): the minimum by (t, insertion index) over the accepted pairs.  old: the
+    guards of the earlier rule to put back (GUARDS)."""
     n = len(q)
     h = np.zeros(n, dtype=HIT_DTYPE)
     h["t"], h["dist"], h["prim"], h["kind"], h["material"] = np.inf, np.inf, -1, -1, -1
-    qi, cid, t, ov = pair_times(rec, q, prefilter)
+    qi, cid, t, ov = pair_times(rec, q, prefilter, old)
     ok = (t <= q["tmax"][qi]) & (t < np.inf)
     qi, cid, t, ov = qi[ok], cid[ok], t[ok], ov[ok]
     ins = rec.cls2ins[cid]
@@ -472,11 +496,10 @@ def _fr3(v):
 
 
 class Checker:
-    """check_answers for one batch of sweeps (finite tmax), reusable for many answers to it: the exact quantities are
-    memoised per (query, primitive, end of the segment)."""
+    """check_answers for one batch of sweeps, reusable for many answers to it: the exact quantities are memoised per
+    (query, primitive, end of the segment).  A miss with tmax = +inf is checked over [o, p(T)], T from `horizon`."""
 
     def __init__(self, rec, mats, q):
-        assert np.all(np.isfinite(q["tmax"]) | sr_skipped(q)), "check_answers takes finite tmax only"
         self.rec, self.mats, self.q = rec, np.asarray(mats), q
         self.skip = skipped(q)
         self._seg, self._memo = {}, {}
@@ -500,6 +523,50 @@ class Checker:
             self._seg[key] = exact_segdist(self.rec, c, _fr3(q["origin"]), p1, float(q["time"]))
             self.exact_pairs += 1
         return self._seg[key]
+
+    # ---- an unbounded miss: where the sweep has left the scene for good
+    def scene_bounds(self, time):
+        """(lo, hi, largest primitive magnitude) as Fractions: a box that CONTAINS every primitive at `time`.  The corners
+        are formed in binary64 and moved outwards by 8 u x the magnitudes of their terms (a vertex a + e, a sphere's
+        c +- R and a moving centre c0 + time dc +- R carry at most three roundings of terms of that magnitude)."""
+        rec = self.rec
+        los, his, mags = [], [], []
+        if rec.nt:
+            t = rec.tri
+            v = np.stack([t[:, 0:3], t[:, 0:3] + t[:, 3:6], t[:, 0:3] + t[:, 6:9]])
+            slack = 8 * U * (np.abs(t[:, 0:3]) + np.abs(t[:, 3:6]) + np.abs(t[:, 6:9]))
+            los.append((v.min(0) - slack).min(0)), his.append((v.max(0) + slack).max(0))
+            mags.append(np.abs(t[:, 0:9]).sum(1).max())
+        for g, c, R, m in ((rec.sph, rec.sph[:, 0:3], np.sqrt(np.abs(rec.sph[:, 3])), np.abs(rec.sph[:, 0:3])),
+                           (rec.mov, rec.mov[:, 0:3] + time * rec.mov[:, 3:6], np.sqrt(np.abs(rec.mov[:, 6])),
+                            np.abs(rec.mov[:, 0:3]) + np.abs(time * rec.mov[:, 3:6]))):
+            if len(g):
+                slack = 8 * U * (m + R[:, None])
+                los.append(((c - R[:, None]) - slack).min(0)), his.append(((c + R[:, None]) + slack).max(0))
+                mags.append((m.sum(1) + R).max())
+        lo, hi = np.min(los, axis=0), np.max(his, axis=0)
+        return _fr3(lo), _fr3(hi), _F(1.0001 * max(mags))
+
+    def horizon(self, i, prec):
+        """For a sweep with tmax = +inf: (T, axis).  T is the smallest power of two such that p(T) lies beyond the box
+        of all primitives grown by rho + band(T) on `axis`, along which the sweep moves away from the box — shown here
+        in exact arithmetic.  From T on the centre is farther than rho + band from that face of the box and receding,
+        so nothing is touched after T: the unbounded miss is the miss over [o, p(T)], with the band of t = T."""
+        q = self.q[i]
+        o, d, rho = _fr3(q["origin"]), _fr3(q["direction"]), _F(q["radius"])
+        lo, hi, mag = self.scene_bounds(float(q["time"]))
+        k = max(range(3), key=lambda j: abs(d[j]))  # |d_k| >= |d|_1 / 3: the band's growth K u T |d|_1 cannot keep up
+        l1o, l1d, ku = sum(abs(x) for x in o), sum(abs(x) for x in d), K[prec] * _F(U)
+        gap = (hi[k] - o[k]) if d[k] > 0 else (o[k] - lo[k])  # how far the face it leaves through is ahead (may be < 0)
+        est = float(max(gap + rho, 0) / abs(d[k]))
+        T = Fr(2) ** (math.frexp(est)[1] - 2 if est > 0.0 else -1074)
+        while not T * abs(d[k]) > gap + rho + ku * (l1o + T * l1d + rho + mag):
+            T *= 2
+        beyond = o[k] + T * d[k]  # the claim, once more, on the coordinate itself
+        band = ku * (l1o + T * l1d + rho + mag)
+        assert (beyond > hi[k] + rho + band) if d[k] > 0 else (beyond < lo[k] - rho - band)
+        assert float(T) < math.inf and math.frexp(float(T))[0] == 0.5
+        return T, k
 
     # ---- the clause over every primitive: nothing within rho - band of the segment [o, end]
     def _clear(self, i, t, end_f, end_fr, end_key, prec, skip_c=-1):
@@ -581,8 +648,10 @@ class Checker:
             if self.skip[i]:
                 return 0.0, 0.0, 0.0, 0
             o, d = _fr3(q["origin"]), _fr3(q["direction"])
+            if tmax == math.inf:
+                tmax = float(self.horizon(i, prec)[0])
             end = [o[k] + _F(tmax) * d[k] for k in range(3)]
-            opened = self._clear(i, tmax, [float(x) for x in end], end, "tmax", prec)
+            opened = self._clear(i, tmax, [float(x) for x in end], end, ("tmax", prec), prec)
             return 0.0, 0.0, 0.0, int(opened)
         # ---- a hit
         assert not self.skip[i], "a hit on a skipped query"
@@ -645,11 +714,8 @@ class Checker:
         return out
 
 
-sr_skipped = skipped
-
-
 def check_answers(rec, mats, q, hits, prec, what=""):
-    """Assert the whole contract of include/rtow.h on `hits` (the answers to the sweeps q, finite tmax) with the band of
+    """Assert the whole contract of include/rtow.h on `hits` (the answers to the sweeps q) with the band of
     `prec`, query by query, and return the statistics (see the module docstring)."""
     return Checker(rec, mats, q).check(hits, prec, what)
 

@@ -5,7 +5,11 @@ under BRUTE, BVH, GRID (answered by BVH), BVH4 and AUTO with both builders — o
 cover scene with moving spheres, suzanne (4-wide image whole in LDS) and the 96,800-triangle mesh (binary16 planes, the top
 of the tree in LDS, stack spill) — for batches of 1, 63, 64, 65 and 4,097 sweeps, after a refit, and against an actual
 strict rtow_closest_point for start_overlap.  The fast build is checked against the exact segment distances within its band
-(sweep_ref.check_answers).  The contracts close the file.
+(sweep_ref.check_answers).  Then the sweeps that start at contact (sweep_cases.contact_sets: chained from the centres of
+earlier answers, aimed at every piece, hand-made and pinned rests, far copies of the hand scene): the strict build against
+the mirror under every walk and builder and after a refit, a chain formed on the device from the device's own records, the
+fast build against the exact distances on chains from its OWN centres, walk by walk, and the unbounded rows.  The
+contracts close the file.
 """
 import math
 
@@ -32,9 +36,9 @@ def case(name):
     """(scene to upload, records, material per insertion index, is a triangle mesh), built once per name."""
     if name not in _CACHE:
         keep = []
-        if name in ("hand", "hand_mesh"):
-            hs = sc.hand_scene(name == "hand_mesh")
-            rec, mats = sc.hand_records(name == "hand_mesh")
+        if name in ("hand", "hand_mesh") or name in sc.FAR_OFFSETS:
+            hs = sc.hand_scene(name == "hand_mesh", sc.FAR_OFFSETS.get(name))
+            rec, mats = sc.hand_records(name == "hand_mesh", sc.FAR_OFFSETS.get(name))
             _CACHE[name] = (hs.c, rec, mats, name == "hand_mesh", [hs])
         else:
             G = ai.mesh_geometry(suzanne_tris(10)) if name == "mesh96k" else SMALL[name]
@@ -68,8 +72,7 @@ def assert_same(got, want, what):
 def strict_sets(rec):
     """4,097 sweeps: the hand-placed ones (they reach every scene: the origins are around the origin), every skipped
     kind, and random ones with finite, infinite and zero tmax."""
-    a, b = sc.placed_sweeps(), sc.skipped_sweeps()
-    return np.concatenate([a, b, sc.random_sweeps(rec, 4097 - len(a) - len(b), 5, finite=False)])
+    return sc.strict_sets(rec)
 
 
 # ------------------------------------------------------------------------------------------------- strict build ---
@@ -185,6 +188,142 @@ def test_fast_build_within_its_band(pctx, name):
         s = ck.check(hits, "fast", (name, kname))
         print(name, kname, sr.stats_line(s))
         assert s["open"] <= 0.02 * len(q), (name, kname, s["open"])
+
+
+# ------------------------------------------------------------------------------- sweeps that start at contact ---
+MESH_RADII = (0.0, 0.01, 0.05)  # of the 96,800-triangle mesh: a larger ball holds hundreds of triangles
+
+
+def contact_expected(name):
+    """(sweeps, the mirror's answers) of the contact set of a scene, chained from the mirror's own answers."""
+    _, rec, mats, _ = case(name)
+    big = name == "mesh96k"
+    return expected(name, "contact", lambda r: sc.contact_sets(
+        name, r, lambda x: sr.answers(r, mats, x), 100 if big else None, MESH_RADII if big else sc.RADII)[0])
+
+
+@pytest.mark.parametrize("builder", list(BUILDERS))
+@pytest.mark.parametrize("name", SCENES + list(sc.FAR_OFFSETS) + ["mesh96k"])
+def test_strict_equals_the_mirror_at_contact(pctx, name, builder):
+    _, rec, mats, mesh = case(name)
+    q, want = contact_expected(name)
+    assert len(q) <= 100 or name != "mesh96k"
+    assert np.any(want["prim"] >= 0) and np.any(want["prim"] < 0)
+    if name == "hand":  # a rest the overlap test does not see answers t = 0 without the flag
+        assert np.any((want["t"] == 0.0) & (want["start_overlap"] == 0) & (want["prim"] >= 0))
+    upload(pctx, name, BUILDERS[builder])
+    for kname, k in KERNELS.items():
+        if name == "mesh96k" and kname == "brute":
+            continue
+        hits, st = pctx.sweep(q, rtow.F64_STRICT, k, want_stats=True)
+        assert_same(hits, want, (name, builder, kname))
+        assert st.kernel_used == used(k, mesh), (name, kname, st.kernel_used)
+
+
+def refit_case():
+    """(undeformed geometry, deformed geometry, its records) of test_refit_equals_the_mirror."""
+    if "refit_geometry" not in _CACHE:
+        G = ai.mesh_geometry(suzanne_tris(1))
+        H = deform(G, lambda p: p * np.array([1.2, 0.9, 1.0]) + np.array([0.1, -0.2, 0.3]))
+        _CACHE["refit_geometry"] = (G, H, pr.make_records(H.sph, H.mov, H.tri))
+    return _CACHE["refit_geometry"]
+
+
+def test_refit_equals_the_mirror_at_contact(pctx):
+    G, H, rec = refit_case()
+    keep = []
+    if "refit_contact" not in _CACHE:
+        q = sc.contact_set(rec, sc.random_sweeps(rec, 200, 19), lambda x: sr.answers(rec, H.pmat, x), 4)[0]
+        _CACHE["refit_contact"] = (q, sr.answers(rec, H.pmat, q))
+    q, want = _CACHE["refit_contact"]
+    for builder in BUILDERS.values():
+        pctx.set_builder(builder)
+        pctx.upload(scene_of(G, keep))
+        pctx.refit(scene_of(H, keep))
+        for kname in ("brute", "bvh", "bvh4", "auto"):
+            assert_same(pctx.sweep(q, rtow.F64_STRICT, KERNELS[kname]), want, ("refit at contact", builder, kname))
+
+
+def test_a_chain_formed_on_the_device(pctx):
+    """Stage 2 from the device's own stage-1 records: the origin is copied from `centre` on the device, and both
+    launches are enqueued on the same stream with nothing read back in between.  Strict: equal to the host-built chain."""
+    import torch
+
+    for name in ("hand", "suzanne"):
+        _, rec, mats, _ = case(name)
+        first = sc.random_sweeps(rec, 600, 3)
+        if name == "hand":
+            first = np.concatenate([sc.aimed_sweeps(1), first])
+        q2, d, tmax = sc.chain_all(first, sr.answers(rec, mats, first), 8)
+        want = sr.answers(rec, mats, q2)
+        assert (q2["tmax"] > 0).sum() > 100 and np.any(want["prim"] >= 0)
+        upload(pctx, name)
+        d_first = torch.from_numpy(first.view(np.uint8).reshape(-1, 80).copy()).cuda()
+        d_dir, d_tmax = torch.from_numpy(d).cuda(), torch.from_numpy(tmax).cuda()
+        for kname in ("brute", "bvh", "auto"):
+            h1 = pctx.sweep(d_first, rtow.F64_STRICT, KERNELS[kname])          # uint8 [n, 80], on the current stream
+            f, prim = h1.view(torch.float64), h1.view(torch.int32)[:, 16]      # t, dist, centre[3], point[3] | prim ...
+            q = d_first.view(torch.float64).clone()                            # origin[3], time, direction[3], tmax, radius
+            q[:, 0:3], q[:, 4:7] = f[:, 2:5], d_dir
+            q[:, 7] = torch.where((prim >= 0) & (f[:, 0] > 0.0), d_tmax, torch.full_like(d_tmax, -1.0))
+            h2 = pctx.sweep(q.view(torch.uint8), rtow.F64_STRICT, KERNELS[kname])
+            got = h2.cpu().numpy().view(sr.HIT_DTYPE).reshape(-1)
+            assert_same(got, want, ("device chain", name, kname))
+            assert q.cpu().numpy().tobytes() == q2.tobytes(), (name, kname)
+
+
+FAST_CONTACT = {"hand": 300, "cover_moving": 200, "suzanne": 200, "mesh96k": 60, "far1e5": 300, "far1e7": 300}
+
+
+def fast_chain_check(ctx, name, rec, mats, walks, limit, first=None):
+    """For each walk: the contact set chained from the fast build's OWN answers under that walk, answered by it and
+    checked against the exact segment distances with a reference of its own (the centres differ in the last bits
+    between walks).  Every "into" sweep must come back a hit."""
+    radii = MESH_RADII if name == "mesh96k" else sc.RADII
+    for kname in walks:
+        own = lambda x: ctx.sweep(x, rtow.F64_FAST, KERNELS[kname])  # noqa: E731, B023
+        if first is None:
+            q, rest, into = sc.contact_sets(name, rec, own, limit, radii)
+        else:
+            q, rest, into = sc.thin(sc.contact_set(rec, first, own, 4), limit)
+        hits = own(q)
+        s = sr.Checker(rec, mats, q).check(hits, "fast", (name, kname))
+        print(name, kname, sr.stats_line(s))
+        assert np.all(hits["prim"][into] >= 0), (name, kname)
+        assert s["hits"] > 0.5 * len(q) and into.sum() > 0.1 * min(len(q), limit or len(q))
+
+
+@pytest.mark.parametrize("builder", list(BUILDERS))
+@pytest.mark.parametrize("name", list(FAST_CONTACT))
+def test_fast_build_at_contact_within_its_band(pctx, name, builder):
+    _, rec, mats, _ = case(name)
+    upload(pctx, name, BUILDERS[builder])
+    fast_chain_check(pctx, name, rec, mats, ("bvh", "bvh4") if name == "mesh96k" else ("brute", "bvh", "bvh4"), FAST_CONTACT[name])
+
+
+def test_fast_build_at_contact_after_a_refit(pctx):
+    G, H, rec = refit_case()
+    keep = []
+    for builder in BUILDERS.values():
+        pctx.set_builder(builder)
+        pctx.upload(scene_of(G, keep))
+        pctx.refit(scene_of(H, keep))
+        fast_chain_check(pctx, "refit", rec, H.pmat, ("brute", "bvh", "bvh4"), 200, first=sc.random_sweeps(rec, 200, 19))
+
+
+@pytest.mark.parametrize("name", list(FAST))
+def test_fast_build_on_unbounded_sweeps(pctx, name):
+    """The tmax = +inf rows of the strict sets: a miss is checked up to the horizon where the sweep has left the scene."""
+    _, rec, mats, _ = case(name)
+    q = expected(name, "strict", strict_sets)[0] if name != "mesh96k" else np.concatenate([
+        sc.random_sweeps(rec, 1500, 9, finite=True, radii=MESH_RADII), sc.random_sweeps(rec, 29, 10, finite=False, radii=(0.0, 0.01))])
+    q = q[np.isinf(q["tmax"]) & ~sr.skipped(q)]
+    assert len(q) > (3 if name == "mesh96k" else 400)
+    upload(pctx, name)
+    ck = sr.Checker(rec, mats, q)
+    for kname in ("bvh", "bvh4") if name == "mesh96k" else ("brute", "bvh4"):
+        s = ck.check(pctx.sweep(q, rtow.F64_FAST, KERNELS[kname]), "fast", (name, kname))
+        print(name, kname, sr.stats_line(s))
 
 
 # ---------------------------------------------------------------------------------------------------- contracts ---
