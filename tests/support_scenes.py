@@ -223,6 +223,9 @@ def _set_order(sc, G, keep, perm=None):
     return sc
 
 
+set_order = _set_order  # (the name other modules import)
+
+
 def scene_of(G, keep, cam_shift=None, shutter=None):
     """An rtow.Scene of G (to_scene: the cover scene's camera) with its class-major insertion order (the oracle reads
     one), the camera translated by cam_shift and its shutter replaced; G.cam follows the camera origin."""

@@ -14,6 +14,7 @@ import pytest
 import ambient_cases as ac
 import ambient_exact as ax
 import ambient_ref
+import big_mixed as bm
 import exact_hits as ex
 import rtow
 from exact_cases import BUILDS, SHARE, big_mesh, logged, refit_case  # noqa: F401
@@ -61,22 +62,27 @@ def test_directions_lie_within_the_bound_of_the_exact_ones(qctx, dirs, build):
 
 
 # ---- records -------------------------------------------------------------------------------------------------------
-def run_records(ctx, name, upload, sc, pts, ids, samples, build, refit=None, after=None):
-    """Every walk x builder of `build` on the points; `after(out)`: further assertions on every answer."""
+def run_records(ctx, name, upload, sc, pts, ids, samples, build, refit=None, after=None, resident=None, used=None):
+    """Every walk x builder of `build` on the points; `after(out)`: further assertions on every answer; resident and used:
+    as in test_gpu_exact_hits.run_case.  Returns walk name -> the host builder's (records, exported rays)."""
     refs = {}
     has_tri = len(sc.tri) > 0
-    lines = []
+    lines, got = [], {}
     for bname, builder in BUILDERS.items():
         ctx.set_builder(builder)
         try:
             ctx.upload(upload)
             if refit is not None:
                 ctx.refit(refit)
+            if resident is not None:
+                resident(ctx, bname)
             for wname, walk in WALKS.items():
                 if wname == "brute" and (bname == "device" or len(sc.kind) > 4096):
                     continue  # (the brute force does not depend on the builder; 96,800 tests per ray are not a test)
                 out, rays, st = ctx.ambient(pts, samples, ac.SEED, ids, 0, BUILDS[build], walk, want_rays=True,
                                             want_stats=True)
+                assert used is None or st.kernel_used == used[wname], (name, bname, wname, build, st.kernel_used)
+                got.setdefault(wname, (out, rays))
                 unit_cut = build == ex.FAST and st.kernel_used == rtow.KERNEL_GRID and has_tri
                 key = (rays.tobytes(), unit_cut)
                 if key not in refs:  # (one reference, one set of exact directions per exported ray set)
@@ -96,6 +102,7 @@ def run_records(ctx, name, upload, sc, pts, ids, samples, build, refit=None, aft
     # last bits (each instantiation is contracted on its own), and every set is checked against its own reference
     assert build != ex.STRICT or len(refs) == 1, "the strict build's exported rays depend on the walk"
     print(f"\n{name}: {len(pts)} points x {samples} samples, {len(refs)} references\n" + "\n".join(lines))
+    return got
 
 
 @pytest.mark.parametrize("build", list(BUILDS))
@@ -137,3 +144,16 @@ def test_records_after_a_refit(qctx, logged, build):
     base, new, sc, rays, keep = refit_case(hs, "translate", 200)
     pts, ids = ac.box_points(sc, rays[200:400], 5)
     run_records(qctx, "records/refit/cover_moving/translate", base, sc, pts, ids, SAMPLES, build, refit=new)
+
+
+# ---- the mixed scene beyond LDS (tests/big_mixed.py): the <BVH, false> and <GRID, false> forms ----
+@pytest.mark.parametrize("build", list(BUILDS))
+@pytest.mark.parametrize("samples", bm.AMBIENT_SAMPLES)
+def test_big_mixed(qctx, samples, build):
+    c = bm.case()
+    pts, ids = bm.ambient_points(c)
+    got = run_records(qctx, f"big_mixed/{samples}", c.hs.c, c.exact, pts, ids, samples, build, resident=bm.resident,
+                      used=bm.used())
+    if build == ex.STRICT:  # strict answers do not depend on the walk
+        for w in ("bvh", "grid", "bvh4"):
+            assert got[w][0].tobytes() == got["brute"][0].tobytes() and got[w][1].tobytes() == got["brute"][1].tobytes(), w

@@ -11,11 +11,12 @@ field are printed; DESIGN.md §4.13 records them.
 import numpy as np
 import pytest
 
+import big_mixed as bm
 import guides_exact as gx
 import rtow
 from guides_ref import SCENES, Logged, Parts, guide_values, logged, moved_cover, row_list, within_cap  # noqa: F401
 from support_fixtures import qctx  # noqa: F401
-from support_oracle import expected_kernel, same_bits
+from support_oracle import expected_kernel, primaries, same_bits
 from support_tables import BUILDERS, WALKS as KERNELS
 
 pytestmark = pytest.mark.gpu
@@ -128,3 +129,37 @@ def test_fast_guides_after_a_refit(logged, moved, kernel):
         checked(c, moved, lg.config(rtow.F64_FAST, KERNELS[kernel]), gx.FAST, "cover_moving refitted", KERNELS[kernel])
     finally:
         c.close()
+
+
+# ---- the mixed scene beyond LDS (tests/big_mixed.py): the <BVH, false> and <GRID, false> forms ----
+@pytest.mark.parametrize("builder", list(BUILDERS))
+def test_big_mixed(qctx, builder):
+    """The fast guides under every walk; the strict ones under BRUTE (the host builder's: the brute force reads no tree),
+    BVH and GRID, each through the checker and BVH's and GRID's equal to BRUTE's bit for bit; the strict camera rays are the
+    oracle's primaries."""
+    c = bm.case()
+    if "big_mixed" not in _refs:
+        _refs["big_mixed"] = Parts(c.hs)
+    parts, used = _refs["big_mixed"], bm.used()
+    strict = lambda wname: c.config(rtow.F64_STRICT, max_child_rays=0, kernel=KERNELS[wname])  # noqa: E731
+    try:
+        if "big_mixed strict brute" not in _refs:
+            qctx.set_builder(rtow.BUILDER_HOST_SAH)
+            qctx.upload(c.hs.c)
+            _refs["big_mixed strict brute"] = checked(qctx, parts, strict("brute"), gx.STRICT, "big_mixed", used["brute"])[0]
+        brute = _refs["big_mixed strict brute"]
+        qctx.set_builder(BUILDERS[builder])
+        qctx.upload(c.hs.c)
+        bm.resident(qctx, builder)
+        rays, ids = qctx.camera_rays(c.config(max_child_rays=0))
+        want_rays, want_ids = primaries(c.log)
+        assert same_bits(rays, want_rays) and np.array_equal(ids, want_ids)
+        for wname, walk in KERNELS.items():
+            if wname == "brute" and builder == "device":
+                continue
+            checked(qctx, parts, c.config(rtow.F64_FAST, max_child_rays=0, kernel=walk), gx.FAST, "big_mixed", used[wname])
+        for wname in ("bvh", "grid"):
+            g = checked(qctx, parts, strict(wname), gx.STRICT, "big_mixed", used[wname])[0]
+            assert same_bits(g, brute), (builder, wname, int((guide_values(g) != guide_values(brute)).any(axis=-1).sum()))
+    finally:
+        qctx.set_builder(rtow.BUILDER_HOST_SAH)

@@ -11,21 +11,24 @@ import numpy as np
 import pytest
 
 import accel_images as ai
+import big_mixed as bm
 import exact_hits as ex
 import rtow
 from exact_cases import (BUILDS, SHARE, big_mesh, cover_tangent_rays, det_cut_rays, edge_rays, far_case,  # noqa: F401
                          handmade_tangent_rays, logged, magnitude_rays, mesh_case, refit_case, subsample, surface_rays)
 from support_fixtures import qctx  # noqa: F401
 from support_oracle import LOGGED, rays_of
-from support_scenes import SceneView, handmade_scene
+from support_scenes import SceneView, handmade_scene, rays_for
 from support_tables import BUILDERS, WALKS
 
 pytestmark = pytest.mark.gpu
 
 
-def run_case(ctx, name, upload, scene, rays, share=None, refit=None):
+def run_case(ctx, name, upload, scene, rays, share=None, refit=None, resident=None, used=None):
     """Every walk x build x builder on `rays`; `upload` is what ctx.upload takes, `refit` (optional) a scene refitted
-    over it — `scene` (exact_hits.Scene) is then the refitted geometry."""
+    over it — `scene` (exact_hits.Scene) is then the refitted geometry.  resident(ctx, builder name): assertions on what
+    the upload left resident; used: walk name -> the kernel_used the closest-hit launch
+    must report (the any-hit launch of the same request returns no statistics).  Returns the stats of every combination."""
     refs = {}
     has_tri = len(scene.tri) > 0
 
@@ -35,21 +38,25 @@ def run_case(ctx, name, upload, scene, rays, share=None, refit=None):
             refs[key] = ex.Reference(scene, rays, build, unit_cut=key[1])
         return refs[key]
 
-    lines = []
+    lines, out = [], []
     for bname, builder in BUILDERS.items():
         ctx.set_builder(builder)
         try:
             ctx.upload(upload)
             if refit is not None:
                 ctx.refit(refit)
+            if resident is not None:
+                resident(ctx, bname)
             for wname, walk in WALKS.items():
                 if wname == "brute" and (bname == "device" or len(scene.kind) > 4096):
                     continue  # (the brute force does not depend on the builder; 96,800 tests per ray are not a test)
                 for build, prec in BUILDS.items():
                     hits, st = ctx.intersect(rays, prec, walk, want_stats=True)
                     occ = ctx.occluded(rays, prec, walk)
+                    assert used is None or st.kernel_used == used[wname], (name, bname, wname, build, st.kernel_used)
                     r = ref(build, build == ex.FAST and st.kernel_used == rtow.KERNEL_GRID)
                     s = ex.check(r, hits, occ, (name, bname, wname, build, st.kernel_used))
+                    out.append(dict(s, build=build, walk=wname, builder=bname, used=st.kernel_used))
                     lines.append(f"  {bname:6s} {wname:5s}(used {st.kernel_used}) {build:6s}: decided {s['decided']}, "
                                  f"undecided {s['undecided']} (any-hit {s['occ_undecided']}), t differs {s['t_differs']}, "
                                  f"worst t err {s['worst_t_err']:.3f} of bound")
@@ -58,6 +65,7 @@ def run_case(ctx, name, upload, scene, rays, share=None, refit=None):
         finally:
             ctx.set_builder(rtow.BUILDER_AUTO)
     print(f"\n{name}: {len(rays)} rays, {sum(r.n_exact for r in refs.values())} exact pairs\n" + "\n".join(lines))
+    return out
 
 
 # ---- logged and random rays ---------------------------------------------------------------------------------------
@@ -144,3 +152,18 @@ def test_after_refit(qctx, logged, big_mesh, name, motion):
     hs = logged["cover_moving"][0] if name == "cover_moving" else big_mesh[0]
     base, new, sc, rays, keep = refit_case(hs, motion, 1500 if name == "cover_moving" else 100)
     run_case(qctx, f"refit/{name}/{motion}", base, sc, rays, refit=new)
+
+
+# ---- the mixed scene beyond LDS (tests/big_mixed.py): the <BVH, false> and <GRID, false> forms ----
+@pytest.mark.parametrize("name", bm.RAY_SETS)
+def test_big_mixed(qctx, name):
+    c = bm.case()
+    rays, share = bm.ray_sets(c)[name]
+    run_case(qctx, f"big_mixed/{name}", c.hs.c, c.exact, rays, share=share, resident=bm.resident, used=bm.used())
+
+
+@pytest.mark.parametrize("motion", bm.REFITS)
+def test_big_mixed_after_refit(qctx, motion):
+    c, new = bm.case(), bm.refitted(motion)
+    run_case(qctx, f"big_mixed/refit/{motion}", c.hs.c, new.exact, rays_for(new.G, 160, 7), refit=new.hs.c,
+             resident=bm.resident, used=bm.used())

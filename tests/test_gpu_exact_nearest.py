@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 import accel_images as ai
+import big_mixed as bm
 import nearest_cases as nc
 import nearest_ref as nr
 import point_ref as pr
@@ -41,10 +42,11 @@ pytestmark = pytest.mark.gpu
 BUILDS = {"strict": (rtow.F64_STRICT, nc.KS_STRICT), "fast": (rtow.F64_FAST, nc.KS_FAST)}
 
 
-def run_case(ctx, name, upload, rec, mats, sets, refit=None, brute=True, node_bytes=None, fresh=None, kth=0):
+def run_case(ctx, name, upload, rec, mats, sets, refit=None, brute=True, node_bytes=None, fresh=None, kth=0, resident=None):
     """Every kernel x build x builder x k on every point set of `sets` (nearest_cases.nearest_sets); `upload` is what
     ctx.upload takes, `refit` (optional) a scene refitted over it — `rec` and `mats` are then the refitted geometry's,
-    and `fresh` a second context that uploads `refit` itself; `kth`: see nearest_cases.Batch."""
+    and `fresh` a second context that uploads `refit` itself; `kth`: see nearest_cases.Batch; resident(ctx, builder name): assertions on
+    what the upload left resident."""
     batches = [nc.Batch(rec, mats, *s, kth=kth) for s in sets]
     mesh = rec.ns + rec.nm == 0
     b4 = rtow.KERNEL_BVH4 if mesh else rtow.KERNEL_BVH
@@ -60,6 +62,8 @@ def run_case(ctx, name, upload, rec, mats, sets, refit=None, brute=True, node_by
                 fresh.upload(refit)
             if node_bytes is not None:
                 assert ctx.build_info().bvh4_node_bytes == node_bytes, (name, bname)
+            if resident is not None:
+                resident(ctx, bname)
             for kname, kern in KERNELS.items():
                 if kname == "brute" and (bname == "device" or not brute):
                     continue  # (the brute force does not depend on the builder; 96,800 tests per query are not a test)
@@ -186,3 +190,10 @@ def test_material_follows_the_primitive_on_coincident_triangles(pctx, builder, r
                 assert len({int(mats[p]) for p in seen if p < stack}) == 2, (what, sorted(seen)[:8])
     finally:
         pctx.set_builder(rtow.BUILDER_AUTO)
+
+
+# ---- the mixed scene beyond LDS (tests/big_mixed.py): the <BVH, false> and <GRID, false> forms ----
+def test_big_mixed(pctx):
+    c = bm.case()
+    total = run_case(pctx, "big_mixed", c.hs.c, c.rec, c.mats, bm.nearest_sets(c), resident=bm.resident)
+    assert total["strict"]["overflow"] > 0 and total["strict"]["short"] > 0 and total["fast"]["short"] > 0

@@ -16,6 +16,7 @@ exact pairs, the worst dist, on-surface and consistency errors in units of their
 import pytest
 
 import accel_images as ai
+import big_mixed as bm
 import point_ref as pr
 import rtow
 from point_cases import (EDGE_MESHES, KERNELS, REFITS, SEED, SPHERE_SCENES, check_strict, geometry_case, point_sets,
@@ -41,9 +42,10 @@ class Batch:
         self.dmin, self.ties = self.ck.mirror_dmin(), self.ck.ties
 
 
-def run_case(ctx, name, upload, rec, mats, sets, refit=None, brute=True, node_bytes=None):
+def run_case(ctx, name, upload, rec, mats, sets, refit=None, brute=True, node_bytes=None, resident=None):
     """Every kernel x build x builder on every point set of `sets` (point_ref.all_sets); `upload` is what ctx.upload
-    takes, `refit` (optional) a scene refitted over it — `rec` and `mats` are then the refitted geometry's."""
+    takes, `refit` (optional) a scene refitted over it — `rec` and `mats` are then the refitted geometry's;
+    resident(ctx, builder name): assertions on what the upload left resident."""
     batches = [Batch(rec, mats, *s) for s in sets]
     mesh = rec.ns + rec.nm == 0
     b4 = rtow.KERNEL_BVH4 if mesh else rtow.KERNEL_BVH
@@ -57,6 +59,8 @@ def run_case(ctx, name, upload, rec, mats, sets, refit=None, brute=True, node_by
                 ctx.refit(refit)
             if node_bytes is not None:
                 assert ctx.build_info().bvh4_node_bytes == node_bytes, (name, bname)
+            if resident is not None:
+                resident(ctx, bname)
             for kname, k in KERNELS.items():
                 if kname == "brute" and (bname == "device" or not brute):
                     continue  # (the brute force does not depend on the builder; 96,800 tests per query are not a test)
@@ -109,3 +113,18 @@ def test_after_refit(pctx, logged, big_mesh, name, motion):
     new, rec, mats = geometry_case(motions(G)[motion][0], keep)
     sets = pr.all_sets(rec, SEED, sizes=pr.SIZES_BIG if big else pr.SIZES, refit=True)
     run_case(pctx, f"refit/{name}/{motion}", base, rec, mats, sets, refit=new, brute=not big)
+
+
+# ---- the mixed scene beyond LDS (tests/big_mixed.py): the <BVH, false> and <GRID, false> forms ----
+def test_big_mixed(pctx):
+    c = bm.case()
+    total = run_case(pctx, "big_mixed", c.hs.c, c.rec, c.mats, bm.point_sets(c), resident=bm.resident)
+    assert total["strict"]["overflow"] > 0 and total["fast"]["overflow"] > 0
+
+
+@pytest.mark.parametrize("motion", bm.REFITS)
+def test_big_mixed_after_refit(pctx, motion):
+    c, new = bm.case(), bm.refitted(motion)
+    sets = pr.all_sets(new.rec, SEED, sizes=dict(bm.POINT_SIZES, random=50), refit=True)
+    assert sum(len(s[1]) for s in sets) <= 500
+    run_case(pctx, f"big_mixed/refit/{motion}", c.hs.c, new.rec, new.mats, sets, refit=new.hs.c, resident=bm.resident)

@@ -7,7 +7,7 @@ kernel walks) and on the logged rows of the three deep renders:
   * status, next ray and attenuation pass scatter_exact.check, and the undecided shares of scatter_cases.assert_shares
     hold for the reference of what ran;
   * strict build: the whole result equals orc_scatter fed with the step's own hit record, bit for bit, and GRID equals
-    BRUTE bit for bit;
+    BRUTE bit for bit (on the mixed scene beyond LDS, which has no exact ties among its rows: BVH and BVH4 too);
   * want_hits=False and stepping in place give the bits of the checked result, in both builds.
 Each test prints decided, undecided and the worst direction error over its bound, per family.
 
@@ -26,6 +26,7 @@ scatter_cases.Case.without_reftree_blind_hits.
 import numpy as np
 import pytest
 
+import big_mixed as bm
 import exact_hits as ex
 import orc
 import rtow
@@ -85,8 +86,10 @@ def oracle_on_hits(case, status, hits):
     return s_all, st, nx, at
 
 
-def run_case(ctx, whole, upload, view_like):
-    """REFTREE is checked on whole.without_reftree_blind_hits() (the reference's boxes of negative-radius spheres); its bits
+def run_case(ctx, whole, upload, view_like, resident=None, equal_brute=("grid",)):
+    """resident(ctx, builder name): assertions on what the upload left resident; equal_brute: the strict walks whose whole
+    result must equal strict BRUTE's bit for bit (a case without exact ties can name them all).
+    REFTREE is checked on whole.without_reftree_blind_hits() (the reference's boxes of negative-radius spheres); its bits
     against orc_scatter on every ray."""
     lines = []
     results = {}
@@ -94,6 +97,8 @@ def run_case(ctx, whole, upload, view_like):
         ctx.set_builder(builder)
         try:
             ctx.upload(upload)
+            if resident is not None:
+                resident(ctx, bname)
             for build, prec in BUILDS.items():
                 for kname, kernel in (KERNELS if build == ex.STRICT else WALKS).items():
                     if kname == "brute" and bname == "device":
@@ -127,10 +132,11 @@ def run_case(ctx, whole, upload, view_like):
                                          f"{int((hits['prim'] < 0).sum())} misses in all")
         finally:
             ctx.set_builder(rtow.BUILDER_AUTO)
-    for bname in BUILDERS:  # strict GRID == strict BRUTE (the brute force ran under the host builder)
-        if (bname, "grid") in results:
-            for x, y in zip(results[(bname, "grid")], results[("host", "brute")]):
-                assert same_bits(x, y), (whole.name, bname, "grid != brute")
+    # strict GRID (and the other walks of equal_brute) == strict BRUTE (the brute force ran under the host builder)
+    for (bname, kname), got in results.items():
+        if kname in equal_brute:
+            for x, y in zip(got, results[("host", "brute")]):
+                assert same_bits(x, y), (whole.name, bname, f"{kname} != brute")
     print(f"\n{whole.name}: {len(whole.rays)} rays\n" + "\n".join(lines))
 
 
@@ -168,3 +174,11 @@ def test_without_hits_and_in_place(qctx, edge):
         torch.cuda.synchronize()
         assert same_bits(d_st.cpu().numpy(), status) and same_bits(d_att.cpu().numpy(), atten)
         assert same_bits(d_rays.cpu().numpy().view(rtow.RAY_DTYPE).reshape(-1), nxt)
+
+
+# ---- the mixed scene beyond LDS (tests/big_mixed.py): the <BVH, false> and <GRID, false> forms ----
+def test_big_mixed(qctx):
+    """Rows of the scene's own log (all three materials, every segment depth); strict BVH, GRID and BVH4-as-BVH equal BRUTE
+    bit for bit."""
+    c = bm.case()
+    run_case(qctx, bm.scatter_case(c), c.hs.c, c.view, resident=bm.resident, equal_brute=("bvh", "grid", "bvh4"))

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import accel_images as ai
+import big_mixed as bm
 import exact_hits as ex
 import first_hits_ref as fr
 import rtow
@@ -29,10 +30,10 @@ pytestmark = pytest.mark.gpu
 DEEP = (8, 3, 1)  # max_hits on the deep and tie-rich families
 
 
-def run_case(ctx, name, upload, scene, rays, ks=(8,), share=None, refit=None, node_bytes=None):
+def run_case(ctx, name, upload, scene, rays, ks=(8,), share=None, refit=None, node_bytes=None, resident=None, used=None):
     """test_gpu_exact_hits.run_case for first_hits: every walk x build x builder x max_hits on `rays`.  The fast GRID
-    walk applies the triangle cut to the unit direction and sorts distances (unit_cut, sorted_by_index=False).  Returns
-    the stats of every combination."""
+    walk applies the triangle cut to the unit direction and sorts distances (unit_cut, sorted_by_index=False).  resident
+    and used: as in test_gpu_exact_hits.run_case.  Returns the stats of every combination."""
     refs = {}
     seen = {}
     has_tri = len(scene.tri) > 0
@@ -52,12 +53,15 @@ def run_case(ctx, name, upload, scene, rays, ks=(8,), share=None, refit=None, no
                 ctx.refit(refit)
             if node_bytes is not None:
                 assert ctx.build_info().bvh4_node_bytes == node_bytes, (name, bname)
+            if resident is not None:
+                resident(ctx, bname)
             for wname, walk in WALKS.items():
                 if wname == "brute" and (bname == "device" or len(scene.kind) > 4096):
                     continue  # (as in test_gpu_exact_hits.run_case)
                 for build, prec in BUILDS.items():
                     for k in ks:
                         hits, counts, st = ctx.first_hits(rays, k, prec, walk, want_stats=True)
+                        assert used is None or st.kernel_used == used[wname], (name, bname, wname, build, st.kernel_used)
                         grid_fast = build == ex.FAST and st.kernel_used == rtow.KERNEL_GRID
                         key, r = ref(build, grid_fast)
                         # the same bytes against the same reference under the same rules: the same verdict
@@ -190,3 +194,21 @@ def test_scene_of_exact_ties(qctx):
     """Bit-identical copies of a triangle and of a sphere: exact ties that straddle the cut at max_hits 1 and 3."""
     h = fr.ties_scene()
     run_case(qctx, "ties", h.c, ex.Scene.of(SceneView(h)), fr.ties_rays(), ks=DEEP + (2,))
+
+
+# ---- the mixed scene beyond LDS (tests/big_mixed.py, DESIGN.md §4.12a): the <BVH, false> and <GRID, false> forms ----
+@pytest.mark.parametrize("name", bm.SEQUENCE_SETS)
+def test_big_mixed(qctx, name):
+    c = bm.case()
+    rays, share = bm.sequence_sets(c)[name]
+    run_case(qctx, f"big_mixed/{name}", c.hs.c, c.exact, rays, ks=(8, 1), share=share, resident=bm.resident, used=bm.used())
+
+
+def test_big_mixed_tmax_at_and_around_hits(qctx):
+    c = bm.case()
+    rays = bm.sequence_sets(c)["logged"][0]
+    qctx.upload(c.hs.c)
+    h8, c8 = qctx.first_hits(rays, 8, rtow.F64_STRICT, rtow.KERNEL_BVH)
+    at = fr.tmax_at_hits(rays, h8["t"], c8)
+    assert len(at) > 300
+    run_case(qctx, "big_mixed/tmax_at_hits", c.hs.c, c.exact, at, ks=(8, 1), resident=bm.resident, used=bm.used())
