@@ -7,6 +7,7 @@ import pytest
 
 import orc
 import rtow
+from sampler_lattice import HALF_PI, sin_quarter  # (the polynomial, operation for operation: shared with the lattice test)
 from support_scenes import write_mesh_obj
 
 _pd = C.POINTER(C.c_double)
@@ -39,18 +40,6 @@ def test_mt19937_stream_and_double_mapping():
     assert L.orc_mt_random_double(0.0, 1.0) == want
     L.orc_mt_reset()
     assert L.orc_mt_random_double(-1.0, 1.0) == want * 2.0 + -1.0
-
-
-SIN_C = [float.fromhex(h) for h in ("0x1.ffffffdb33084p-1", "-0x1.555549a9260fdp-3", "0x1.110eb1f04c8ffp-7",
-                                     "-0x1.9f6d0201a288bp-13", "0x1.5da8d4e70fe23p-19")]
-HALF_PI = 1.5707963267948966
-
-
-def sin_quarter(x):
-    """The samplers' sine polynomial, operation for operation (oracle sin_quarter, csrc/rtow_trace_rng.h): Python floats
-    are binary64 and every operation below rounds once, like the strict build's."""
-    x2 = x * x
-    return x * (SIN_C[0] + x2 * (SIN_C[1] + x2 * (SIN_C[2] + x2 * (SIN_C[3] + x2 * SIN_C[4]))))
 
 
 def test_philox_requests():
