@@ -902,6 +902,73 @@ int rtow_sweep_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const vo
 int rtow_sweep(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_sweep_t *queries, int64_t n,
                rtow_sweep_hit_t *hits, rtow_stats_t *stats);
 
+/* ---- box overlap: which primitives are inside this region, and how many ----------------------------------------------------
+ * Per query a closed axis-aligned box [lo, hi], a shutter time and a first insertion index min_prim.  O is the set of
+ * primitives with insertion index >= min_prim (a negative min_prim acts as 0) whose geometry overlaps the box.  The
+ * geometry is that of rtow_closest_point and rtow_sweep, the device's records: a triangle is the closed triangle a, a + e1,
+ * a + e2 (a zero-area triangle its segment or point); a sphere or moving sphere is its SURFACE, centre taken at `time`
+ * (c0 + time (c1 - c0)), radius^2 = |r2|: it overlaps the box iff dmin^2 <= R^2 <= dmax^2, dmin the distance from the
+ * centre to the box and dmax that to the box's farthest corner, so a box wholly inside a sphere does not overlap it (the
+ * hollow sphere the closest-point query and the sweep see).  Touching counts: every comparison is inclusive.
+ *
+ *   counts[i]  |O|, uncapped.
+ *   ids[i][j]  for j < min(|O|, max_ids) the lowest insertion indices of O, ascending; the remaining slots -1.  Every slot
+ *              of every query is written; nothing is written beyond n.  d_ids may be NULL (counts only: the list is not
+ *              kept); d_counts is required.
+ *   max_ids    1 .. RTOW_MAX_OVERLAP_IDS, checked where rtow_nearest checks k: outside that range RTOW_EINVAL.
+ *   paging     while counts[i] > max_ids, the same query with min_prim = ids[i][max_ids - 1] + 1 continues the list: the
+ *              pages are disjoint, ascending, and together all of O (Context.overlap_all does this).
+ *   skipped    count 0, ids -1 and no walk when lo, hi or time holds a NaN or an infinity, or lo > hi in a component.
+ *              (pad_ is not read.)  lo == hi in one, two or three components is a rectangle, a segment, a point.
+ *   time       results are independent of the kernel for time in [0, 1] only, as for every other query.
+ *
+ * The predicate (csrc/rtow_overlap_walks.h; written once, in a fixed operation order, on the inputs as given;
+ * tests/overlap_ref.py mirrors it) is a separating-axis test with no division, square root or reciprocal:
+ *   sphere     per component near = max(max(lo - s, s - hi), 0), far = max(s - lo, hi - s), s the centre; dmin^2 and
+ *              dmax^2 the sums of their squares, (x + y) + z; overlap iff dmin^2 <= |r2| and |r2| <= dmax^2.
+ *   triangle   v1 = a + e1, v2 = a + e2, f = e2 - e1; thirteen axes: the three box normals (min(a, v1, v2) > hi or
+ *              max(a, v1, v2) < lo separates), the stored n (n.a against the box's interval [sum_k min(n_k lo_k, n_k hi_k),
+ *              sum_k max(n_k lo_k, n_k hi_k)]) and the nine edge x box-axis products, whose components are copies of the
+ *              edge's (e1 with vertices a, v2; e2 and f with a, v1), each against the box's interval on that axis.
+ *
+ *   precision  RTOW_F64_STRICT: counts and ids are bit-identical to that predicate evaluated in IEEE binary64 in its
+ *                               written order, under BRUTE, BVH, BVH4 and AUTO, with either builder and after a refit;
+ *              RTOW_F64_FAST:   the same predicate with FMA contraction; not promised to be the same under every kernel;
+ *              RTOW_F32:        refused (RTOW_EINVAL).
+ *              Both against exact arithmetic: for an axis L, s_L is the exact signed gap (triangle: the greater of
+ *              "least projection of the exact vertices a, a + e1, a + e2 minus the box's greatest" and "the box's least
+ *              minus their greatest", with the exact e1 x e2 for the normal; sphere: dmin^2 - R^2 and R^2 - dmax^2) and E_L
+ *              the sum of the magnitudes of the monomials of s_L expanded in the inputs as given — the record's fields,
+ *              lo, hi, time — taking of a min or max the branch the exact values select (the larger sum on an exact
+ *              tie: the two vertices of an edge project alike across it).  With u = 2^-53 a pair is DECIDED when some axis has s_L > K u E_L (it
+ *              is not reported) or every axis with L != 0 has s_L < -K u E_L (it is reported); any other pair may go
+ *              either way.  K = 10 for the strict build: no monomial of a gap passes more than 9 roundings (the moving
+ *              sphere: 2 in the centre, 1 in the difference, doubled by the square, 1 for the square and 2 for the sums;
+ *              a fixed sphere 5; the normal axis 5: 2 in the stored n, the product, two sums; a cross axis 4; a box
+ *              normal 1), and one more covers the terms of second order.  K = 20 for the fast build.
+ *              Where every intermediate is exactly representable — small-integer or dyadic coordinates — both builds
+ *              give the exact closed-set answer, touching at a face, along an edge and at a vertex included.
+ *   kernel     BRUTE, BVH and BVH4 run their own walks (a node is entered iff its box meets the query box inflated by
+ *              the point walks' slack, inclusive); GRID has no overlap walk and is answered by BVH (kernel_used says
+ *              BVH); AUTO takes BVH4, else BVH, else BRUTE and never fails on a resident scene; the fallbacks and
+ *              RTOW_ENOSCENE rules are rtow_closest_point's.  RTOW_KERNEL_REFTREE: RTOW_EINVAL.
+ * d_queries (16-byte aligned), d_counts and d_ids (4-byte aligned) are DEVICE pointers.  Stream ordering, stats
+ * (segments = n, prim_tests, node_tests, kernel_ms, total_ms, kernel_used) and errors are those of
+ * rtow_closest_point_device.  n == 0 launches nothing.  One call in flight per context. */
+typedef struct rtow_box_query_t {   /* 64 B, 16-byte aligned in device memory: four 16-byte loads */
+  double lo[3], hi[3];              /* the closed box [lo, hi] */
+  double time;                      /* moving-sphere centre c0 + time*(c1-c0), as in the point queries */
+  int32_t min_prim;                 /* only primitives with insertion index >= min_prim take part; < 0 acts as 0 */
+  int32_t pad_;
+} rtow_box_query_t;
+#define RTOW_MAX_OVERLAP_IDS 8
+int rtow_overlap_device(rtow_ctx *ctx, int32_t precision, int32_t kernel, const void *d_queries, int64_t n,
+                        int32_t max_ids, void *d_counts /* int32_t[n] */, void *d_ids /* int32_t[n][max_ids] or NULL */,
+                        void *hip_stream, rtow_stats_t *stats);
+/* The same from and to host memory (device staging owned by the context, the null stream); synchronous. */
+int rtow_overlap(rtow_ctx *ctx, int32_t precision, int32_t kernel, const rtow_box_query_t *queries, int64_t n,
+                 int32_t max_ids, int32_t *counts, int32_t *ids /* or NULL */, rtow_stats_t *stats);
+
 /* ---- the camera stage: primaries of the resident camera, first-hit guide buffers ----------------------------------------
  * The one piece of the render the queries above leave out: Camera::get_ray (src/render.cpp:158-159,
  * src/common-model.cpp:156-167) for the camera of the scene resident in ctx (after the last upload or refit), fed from

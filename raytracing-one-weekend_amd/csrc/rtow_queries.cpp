@@ -1,5 +1,5 @@
 // rtow_queries.cpp — every query over the resident scene: rtow_intersect*, rtow_occluded*, rtow_closest_point*,
-// rtow_first_hits*, rtow_nearest*, rtow_radiance*, rtow_path_step*, rtow_ambient*, rtow_sweep* and the camera stage (rtow_camera_rays*, rtow_guides*).
+// rtow_first_hits*, rtow_nearest*, rtow_radiance*, rtow_path_step*, rtow_ambient*, rtow_sweep*, rtow_overlap* and the camera stage (rtow_camera_rays*, rtow_guides*).
 //
 // One host path serves them all.  A QueryKind row says what tells an entry-point pair apart — its buffers, its strategy
 // resolver, its launchers — and query_device / query_host are the two entry forms of every row; the camera stage, whose
@@ -13,7 +13,7 @@
 
 namespace rtow {
 // csrc/rtow_<family>_{strict,fast}.hip (rtow_query.h, rtow_occlude.h, rtow_pointq.h, rtow_first_hits.h, rtow_nearest.h,
-// rtow_radiance.h, rtow_step.h, rtow_guides.h, rtow_ambient.h, rtow_sweep.h): every family exports one launcher and one occupancy function per build
+// rtow_radiance.h, rtow_step.h, rtow_guides.h, rtow_ambient.h, rtow_sweep.h, rtow_overlap.h): every family exports one launcher and one occupancy function per build
 using QueryLaunchFn = int(const TraceParams &p, const QueryArgs &a, int kernel, int grid, int block, unsigned lds_bytes,
                           void *stream);
 using QueryOccupancyFn = int(int kernel, int block, unsigned lds_bytes, int *vgprs);
@@ -21,12 +21,12 @@ QueryLaunchFn launch_query_strict, launch_query_fast, launch_occlude_strict, lau
     launch_pointq_fast, launch_first_hits_strict, launch_first_hits_fast, launch_nearest_strict, launch_nearest_fast,
     launch_radiance_strict, launch_radiance_fast, launch_step_strict, launch_step_fast, launch_guides_strict,
     launch_guides_fast, launch_camera_rays_strict, launch_camera_rays_fast, launch_ambient_strict, launch_ambient_fast,
-    launch_sweep_strict, launch_sweep_fast;
+    launch_sweep_strict, launch_sweep_fast, launch_overlap_strict, launch_overlap_fast;
 QueryOccupancyFn query_occupancy_strict, query_occupancy_fast, occlude_occupancy_strict, occlude_occupancy_fast,
     pointq_occupancy_strict, pointq_occupancy_fast, first_hits_occupancy_strict, first_hits_occupancy_fast,
     nearest_occupancy_strict, nearest_occupancy_fast, radiance_occupancy_strict, radiance_occupancy_fast,
     step_occupancy_strict, step_occupancy_fast, guides_occupancy_strict, guides_occupancy_fast, ambient_occupancy_strict,
-    ambient_occupancy_fast, sweep_occupancy_strict, sweep_occupancy_fast;
+    ambient_occupancy_fast, sweep_occupancy_strict, sweep_occupancy_fast, overlap_occupancy_strict, overlap_occupancy_fast;
 }  // namespace rtow
 
 namespace {
@@ -111,6 +111,7 @@ struct QueryKind {
   QueryBuf bufs[kMaxQueryBufs] = {};
   Walk walk = Walk::kRay;
   bool mapped = false;           // hit records name primitives by insertion index: needs query_map (when hits are asked for)
+  bool map_always = false;       // ... and so does the query itself (the overlap query's min_prim): query_map in every call
   bool brute_no_lds = false;     // its BRUTE walk reads the class-major arrays: launched without LDS
   bool brute_tests_all = false;  // its STREAM walk tests every primitive uncounted: prim_tests = n * n_prims
   const char *k_name = nullptr;  // nullptr: no k; else "k" / "max_hits", in [1, k_max]
@@ -272,6 +273,18 @@ const QueryKind kSweep = {
     .walk = Walk::kPoint, .mapped = true, .brute_no_lds = true, RTOW_LAUNCHERS(sweep)};
 static_assert(sizeof(rtow_sweep_t) == 80 && sizeof(rtow_sweep_hit_t) == 80,
               "the sweep query's records: five 16-byte loads, five 16-byte stores");
+// box overlap (csrc/rtow_overlap.h): one count and max_ids insertion indices per box; max_ids is checked where k nearest
+// checks k.  The ids travel as QueryArgs::hits; min_prim compares insertion indices, so the map is made for a call
+// without ids too.
+const QueryKind kOverlap = {
+    .count = "n", .n_bufs = 3,
+    .bufs = {{"query", true, 16, sizeof(rtow_box_query_t), false, false, &rtow_ctx::q_rays, nullptr},
+             {"count", true, 4, sizeof(int32_t), false, true, &rtow_ctx::q_kcounts, &QueryArgs::counts},
+             {"ids", false, 4, sizeof(int32_t), true, true, &rtow_ctx::q_khits, &QueryArgs::hits}},
+    .walk = Walk::kPoint, .mapped = true, .map_always = true, .brute_no_lds = true, .k_name = "max_ids",
+    .k_max = RTOW_MAX_OVERLAP_IDS, .k_first = true, RTOW_LAUNCHERS(overlap)};
+static_assert(sizeof(rtow_box_query_t) == 64 && offsetof(rtow_box_query_t, time) == 48 && offsetof(rtow_box_query_t, min_prim) == 56,
+              "the overlap query's record: four 16-byte loads");
 // the camera stage (csrc/rtow_guides.h): the primaries of the resident camera — a kernel that reads the camera alone —
 // and the first-hit guide buffers
 const QueryKind kCameraRays = {
@@ -478,7 +491,7 @@ int query_device(rtow_ctx *c, const QueryKind &k, const QueryCall &call) {
   QueryArgs a = query_args(k, call.buf);
   a.n = (uint32_t)call.n;
   a.k = call.k;
-  if (k.mapped && a.hits && (rc = query_map_for(c, q.kernel, &a.map))) return rc;
+  if (k.mapped && (a.hits || k.map_always) && (rc = query_map_for(c, q.kernel, &a.map))) return rc;
   const int64_t n_items = k.grid_items ? k.grid_items(call) : call.n;
   rc = query_launch(c, k, q, a, n_items, call.stream, call.stats, [&](rtow::TraceParams &P, QueryArgs &args) {
     return k.fill ? k.fill(c, call, q.strict, P, args) : (int)RTOW_OK;
@@ -744,6 +757,18 @@ int rtow_sweep(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_sweep_
                rtow_stats_t *stats) {
   return guarded("rtow_sweep", [&] {
     return query_host(c, kSweep, {precision, kernel, n, 0, nullptr, {(void *)queries, hits}, nullptr, stats});
+  });
+}
+int rtow_overlap_device(rtow_ctx *c, int32_t precision, int32_t kernel, const void *d_queries, int64_t n, int32_t max_ids,
+                        void *d_counts, void *d_ids, void *hip_stream, rtow_stats_t *stats) {
+  return guarded("rtow_overlap_device", [&] {
+    return query_device(c, kOverlap, {precision, kernel, n, max_ids, nullptr, {(void *)d_queries, d_counts, d_ids}, hip_stream, stats});
+  });
+}
+int rtow_overlap(rtow_ctx *c, int32_t precision, int32_t kernel, const rtow_box_query_t *queries, int64_t n, int32_t max_ids,
+                 int32_t *counts, int32_t *ids, rtow_stats_t *stats) {
+  return guarded("rtow_overlap", [&] {
+    return query_host(c, kOverlap, {precision, kernel, n, max_ids, nullptr, {(void *)queries, counts, ids}, nullptr, stats});
   });
 }
 int rtow_camera_rays_device(rtow_ctx *c, const rtow_config_t *cfg, void *d_rays, void *d_ids, void *hip_stream) {

@@ -184,6 +184,7 @@ class SweepHit(C.Structure):
     ]
 
 
+MAX_OVERLAP_IDS = 8  # RTOW_MAX_OVERLAP_IDS: the most ids rtow_overlap returns per box and call
 MAX_AMBIENT_SAMPLES = 65536  # RTOW_MAX_AMBIENT_SAMPLES: the most samples rtow_ambient takes per point
 
 
@@ -224,6 +225,22 @@ def make_sweeps(origins, directions, radius, time=0.0, tmax=float("inf")):
     q["tmax"] = tmax
     q["radius"] = radius
     q["pad_"] = 0.0
+    return q
+
+
+# rtow_box_query_t (rtow_overlap*)
+BOX_QUERY_DTYPE = np.dtype([("lo", "<f8", (3,)), ("hi", "<f8", (3,)), ("time", "<f8"), ("min_prim", "<i4"), ("pad_", "<i4")])
+
+
+def make_boxes(lo, hi, time=0.0, min_prim=0):
+    """A BOX_QUERY_DTYPE array from [n, 3] lower and upper corners (time and min_prim: scalars or [n])."""
+    l = np.asarray(lo, dtype=np.float64).reshape(-1, 3)
+    q = np.empty(len(l), dtype=BOX_QUERY_DTYPE)
+    q["lo"] = l
+    q["hi"] = np.asarray(hi, dtype=np.float64).reshape(-1, 3)
+    q["time"] = time
+    q["min_prim"] = min_prim
+    q["pad_"] = 0
     return q
 
 
@@ -279,7 +296,7 @@ EXPORTS = [
     "rtow_camera_rays_device", "rtow_camera_rays", "rtow_camera_ray_count", "rtow_guides_device", "rtow_guides",
     "rtow_debug_last_spec", "rtow_first_hits_device", "rtow_first_hits", "rtow_nearest_device", "rtow_nearest",
     "rtow_debug_last_counted", "rtow_debug_walk_consts", "rtow_path_step_device", "rtow_path_step",
-    "rtow_ambient_device", "rtow_ambient", "rtow_sweep_device", "rtow_sweep",
+    "rtow_ambient_device", "rtow_ambient", "rtow_sweep_device", "rtow_sweep", "rtow_overlap_device", "rtow_overlap",
 ]
 MULTI_BREAKDOWN = ("total", "handoff_enqueue", "place_enqueue", "wait_and_copy", "wait_only", "dev_trace", "dev_gather",
                    "dev_place_copy")  # RTOW_MB_* of include/rtow.h, milliseconds
@@ -401,6 +418,11 @@ def lib():
         L.rtow_sweep_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.POINTER(Stats)]
         L.rtow_sweep.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Stats)]
+    if hasattr(L, "rtow_overlap"):
+        L.rtow_overlap_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rtow_overlap.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.POINTER(Stats)]
     if hasattr(L, "rtow_guides"):
         L.rtow_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]
         L.rtow_camera_rays.argtypes = [C.c_void_p, C.POINTER(Config), C.c_void_p, C.c_void_p]
@@ -911,6 +933,66 @@ class Context:
         check(lib().rtow_sweep_device(self._h, precision, kernel, C.c_void_p(d_q), n, C.c_void_p(d_hits),
                                       C.c_void_p(stream), C.byref(st) if st is not None else None), "rtow_sweep_device")
         return st
+
+    def overlap(self, queries, max_ids=MAX_OVERLAP_IDS, precision=F64_FAST, kernel=KERNEL_AUTO, want_ids=True,
+                want_stats=False):
+        """The primitives whose geometry overlaps every box (rtow_overlap / rtow_overlap_device): (counts, ids) — int32
+        [n], the uncapped size of each box's set, and int32 [n, max_ids], its lowest insertion indices ascending with -1
+        in the unused slots (None without `want_ids`: counts only).  `queries` is a BOX_QUERY_DTYPE array in host memory
+        (make_boxes) — the answers are numpy arrays — or a torch device tensor holding n 64-byte records (any dtype,
+        contiguous, 16-byte aligned): the answers are then int32 tensors on the same device, enqueued on torch's current
+        stream.  With `want_stats` also Stats."""
+        st = Stats() if want_stats else None
+        if hasattr(queries, "data_ptr"):  # a torch device tensor
+            import torch
+            if not queries.is_cuda or not queries.is_contiguous():
+                raise ValueError("a box tensor must be a contiguous device tensor")
+            nbytes = queries.numel() * queries.element_size()
+            if nbytes % BOX_QUERY_DTYPE.itemsize:
+                raise ValueError("a box tensor must hold whole 64-byte records")
+            n = nbytes // BOX_QUERY_DTYPE.itemsize
+            counts = torch.empty((n,), dtype=torch.int32, device=queries.device)
+            ids = torch.empty((n, max(int(max_ids), 0)), dtype=torch.int32, device=queries.device) if want_ids else None
+            stream = torch.cuda.current_stream(queries.device).cuda_stream
+            check(lib().rtow_overlap_device(self._h, precision, kernel, C.c_void_p(queries.data_ptr()), n, int(max_ids),
+                                            C.c_void_p(counts.data_ptr()),
+                                            C.c_void_p(ids.data_ptr()) if want_ids else None, C.c_void_p(stream),
+                                            C.byref(st) if st is not None else None), "rtow_overlap_device")
+            return (counts, ids, st) if want_stats else (counts, ids)
+        q = np.ascontiguousarray(queries, dtype=BOX_QUERY_DTYPE).reshape(-1)
+        counts = np.empty(len(q), dtype=np.int32)
+        ids = np.empty((len(q), max(int(max_ids), 0)), dtype=np.int32) if want_ids else None
+        check(lib().rtow_overlap(self._h, precision, kernel, q.ctypes.data_as(C.c_void_p), len(q), int(max_ids),
+                                 counts.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p) if want_ids else None,
+                                 C.byref(st) if st is not None else None), "rtow_overlap")
+        return (counts, ids, st) if want_stats else (counts, ids)
+
+    def overlap_device(self, d_q: int, n: int, d_counts: int, d_ids: int = 0, max_ids=MAX_OVERLAP_IDS, precision=F64_FAST,
+                       kernel=KERNEL_AUTO, stream: int = 0, want_stats=False):
+        """The same on raw device pointers (n x 64-byte queries, 16-byte aligned; n int32 counts; n x max_ids int32 ids
+        or 0 for none), enqueued on `stream` (rtow_overlap_device); returns Stats with `want_stats` (then synchronised),
+        else None."""
+        st = Stats() if want_stats else None
+        check(lib().rtow_overlap_device(self._h, precision, kernel, C.c_void_p(d_q), n, int(max_ids), C.c_void_p(d_counts),
+                                        C.c_void_p(d_ids) if d_ids else None, C.c_void_p(stream),
+                                        C.byref(st) if st is not None else None), "rtow_overlap_device")
+        return st
+
+    def overlap_all(self, queries, precision=F64_FAST, kernel=KERNEL_AUTO, max_ids=MAX_OVERLAP_IDS):
+        """Every primitive that overlaps every box (a BOX_QUERY_DTYPE array, host memory): a list of n int32 arrays, each
+        ascending from the box's own min_prim.  Pages through rtow_overlap: a box whose count exceeds max_ids is asked
+        again with min_prim = its last id + 1, all such boxes in one call per round."""
+        q = np.ascontiguousarray(queries, dtype=BOX_QUERY_DTYPE).reshape(-1).copy()
+        pages = [[] for _ in range(len(q))]
+        todo = np.arange(len(q))
+        while len(todo):
+            counts, ids = self.overlap(q[todo], max_ids, precision, kernel)
+            for row, i in enumerate(todo):
+                pages[i].append(ids[row, :min(int(counts[row]), max_ids)])
+            more = counts > max_ids
+            todo = todo[more]
+            q["min_prim"][todo] = ids[more, max_ids - 1] + 1
+        return [np.concatenate(p).astype(np.int32) for p in pages]
 
     def camera_rays(self, cfg: Config):
         """The primaries a render of `cfg` generates on this rank, from the resident camera: (rays, ids) — a RAY_DTYPE
